@@ -12,7 +12,8 @@ classes -- ``MonodomainModel`` + ``DolfinODESolver`` + ``MonodomainSplittingSolv
 reference's demos build them: ionic step on every node, then right-hand-side build + Jacobi-PCG to
 ``--rtol`` relative to ||b||.  (``--direct`` drives the same kernels by bare C-ABI calls instead; at
 this size the two agree to the run-to-run spread.)  Inputs are synthetic and already resident in HBM when the timed
-region starts.  Rank 0 prints ONE JSON line.
+region starts.  Rank 0 prints ONE JSON line; with ``--dump-outputs DIR`` it also writes what the last timed step left to
+the caller (dump_outputs), so that two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -122,6 +123,41 @@ def developed_front_profile(ctx, n, ic, params, v_index, rtol):
         if up.numel() and int(up.max()) >= n // 2:
             break
     return sa.rows.clone(), steps
+
+
+DUMP_SEED = 20240601
+DUMP_V_NODES = 1 << 22  # 32 MB of potential
+DUMP_STATE_NODES = 1 << 17  # 19 rows: 20 MB of states
+
+
+def dump_outputs(out_dir, states, v_index, slab, plane, n_glob, rank, world, dist=None):
+    """--dump-outputs: what the caller of the timed path holds after its last step -- the membrane potential
+    (``pde.state``, the V row of the state array it aliases) and the (S, N) states (``ode.values``) -- as
+    ``v.npy`` (the potential at min(N, 2^22) nodes) and ``states.npy`` (every state at min(N, 2^17) nodes),
+    float64.  The nodes are a seeded sample of the global node indices, in ascending order, the same for every
+    build and every rank count; each rank contributes the nodes of its z-slab and rank 0 writes the files."""
+    import torch
+
+    rng = np.random.default_rng(DUMP_SEED)
+    lo, hi = slab.z0 * plane, slab.z1 * plane
+
+    def pick(m):
+        g = np.arange(n_glob) if m >= n_glob else np.sort(rng.choice(n_glob, size=m, replace=False))
+        loc = g[(g >= lo) & (g < hi)] - lo
+        return torch.from_numpy(loc).to(states.rows.device)
+
+    iv, i_s = pick(DUMP_V_NODES), pick(DUMP_STATE_NODES)
+    torch.cuda.synchronize()
+    part = (states.rows[v_index].index_select(0, iv).cpu().numpy(), states.rows.index_select(1, i_s).cpu().numpy())
+    if world > 1:  # the slabs lie in rank order along z: rank order is node order
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+    else:
+        parts = [part]
+    if rank == 0:
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / "v.npy", np.concatenate([p[0] for p in parts]).astype(np.float64))
+        np.save(out_dir / "states.npy", np.concatenate([p[1] for p in parts], axis=1).astype(np.float64))
 
 
 def cpu_baseline(n_side: int, steps: int, rtol: float):
@@ -469,6 +505,9 @@ def main():
                     "DiffusionSolver.solve) instead of the public API's MonodomainSplittingSolver.step")
     ap.add_argument("--size-z", "--nz", dest="nz", type=int, default=0, help="z planes of the global grid (default: --n); e.g. --nz 64 with "
                     "BEAT_FORCE_DISTRIBUTED=1 rehearses on one GPU the slab one of 8 ranks owns at 512^3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step left to the caller (v.npy: the membrane "
+                    "potential, states.npy: every TP06 state) into DIR, float64, at a fixed seeded sample of nodes (dump_outputs)")
     args = ap.parse_args()
     global ISOTROPIC
     ISOTROPIC = args.iso
@@ -765,6 +804,10 @@ def main():
              f"{solver.libcomm.info()['transport'] if getattr(solver, 'libcomm', None) is not None else 'none'}); timing")
     run = timed_run(0.0, args.warmup, args.steps)
     progress(f"headline timed: {run['wall'] / args.steps * 1e3:.3f} ms/step")
+    if args.dump_outputs:  # before anything below overwrites the state array
+        dump_outputs(Path(args.dump_outputs), states, v_index, slab, plane, n * n * nz_glob, rank, world,
+                     dist if world > 1 else None)
+        progress(f"outputs of the last timed step written to {args.dump_outputs}")
     wall, iters, pend_counts, ode_ms, pde_ms = run["wall"], run["iters"], run["pend_counts"], run["ode_ms"], run["pde_ms"]
     vmin, vmax = v_field.minmax()
     if world > 1:  # extrema over all slabs (NaN-propagating: a non-finite value on any rank shows)
