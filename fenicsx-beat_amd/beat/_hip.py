@@ -20,6 +20,13 @@ MODEL_FHN_README = 2
 MODEL_TP06_GRL1 = 3
 MODEL_TORORD_DYNCL_GRL1 = 4
 MODEL_TORORD_LAND_GRL1 = 5
+# beat_math_probe's helpers (BeatMathFn of csrc/beat_math_probe.h) and their input / output row counts
+(MATH_EXP, MATH_EXP_INT, MATH_LOG, MATH_LOG_INT, MATH_RCP, MATH_RSQRT, MATH_TP06_RCP2, MATH_TP06_RCP3, MATH_TP06_RCP4,
+ MATH_TORORD_RCP2, MATH_TORORD_RCP3, MATH_TORORD_RCP4, MATH_TP06_PHI_SMALL, MATH_TP06_PHI7, MATH_TORORD_PHI_SMALL,
+ MATH_TORORD_PHI7, MATH_TP06_GRL1, MATH_TP06_ADVANCE, MATH_TP06_GATE, MATH_TORORD_ADVANCE, MATH_TORORD_GATE,
+ MATH_TORORD_GATE_B) = range(22)
+MATH_IN = (1, 1, 1, 1, 1, 1, 2, 3, 4, 2, 3, 4, 1, 1, 1, 1, 4, 4, 4, 4, 4, 4)
+MATH_OUT = (1, 1, 1, 1, 1, 1, 2, 3, 4, 2, 3, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)
 MAX_STIM = 8
 MAX_CLASSES = 32
 
@@ -73,6 +80,7 @@ SIGNATURES = {
     "beat_copy": (_int, [_vp, _vp, _vp, _i64]),
     "beat_fill": (_int, [_vp, _vp, _dbl, _i64]),
     "beat_stream_probe": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _i64]),
+    "beat_math_probe": (_int, [_vp, _int, _vp, _i64, _vp, _i64]),
     "beat_gather": (_int, [_vp, _vp, _vp, _vp, _i64]),
     "beat_scatter": (_int, [_vp, _vp, _vp, _vp, _i64]),
     "beat_interp2": (_int, [_vp, _vp, _vp, _vp, _vp, _i64]),

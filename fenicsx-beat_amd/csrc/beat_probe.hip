@@ -15,6 +15,7 @@
 //   unroll 1, 2 or 4 independent 16-byte accesses in flight per lane and loop trip
 //   blocks workgroups of 256 threads in the launch (grid-stride loop); 0 = one workgroup per 256 * unroll * 16 bytes, no loop
 #include "beat_common.h"
+#include "beat_math_probe.h"
 
 namespace {
 
@@ -214,7 +215,40 @@ int launch_march(beat_ctx* ctx, double* dev, int64_t n, int nx, int ry, int segw
   return BEAT_OK;
 }
 
+// beat_math_probe: one helper of the ionic kernels' math layer per column (beat_math_probe.h), with FastMath set up as
+// ode_step_kernel sets it up (beat_ode_kernel.h): both exp tables and the log table staged in LDS, the rounding constant pinned
+__global__ __launch_bounds__(BEAT_BLOCK) void math_probe_kernel(int fn, const double* __restrict__ in, int64_t ld, double* __restrict__ out,
+                                                                int64_t n) {
+  __shared__ double etab[BEAT_EXP_TAB], etabi[BEAT_EXP_TAB];
+  __shared__ LogEntry ltab[128];
+  static_assert(BEAT_EXP_TAB == BEAT_BLOCK, "one table entry per thread");
+  etab[threadIdx.x] = beat_exp_tab_entry<false>(kExp2Tab[threadIdx.x], (int)threadIdx.x);
+  etabi[threadIdx.x] = beat_exp_tab_entry<true>(kExp2Tab[threadIdx.x], (int)threadIdx.x);
+  if (threadIdx.x < 128) ltab[threadIdx.x] = kLogTab[threadIdx.x];
+  __syncthreads();
+  FastMath fm{etab, ltab};
+  FastMathT<true> fmi{etabi, ltab};
+  beat_fm_pin(fm);
+  beat_fm_pin(fmi);
+  const int64_t i = (int64_t)blockIdx.x * BEAT_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  double a[4], o[4];
+  for (int r = 0; r < BEAT_MATH_IN[fn]; ++r) a[r] = in[r * ld + i];
+  beat_math_eval(fn, fm, fmi, a, o);
+  for (int r = 0; r < BEAT_MATH_OUT[fn]; ++r) out[r * ld + i] = o[r];
+}
+
 }  // namespace
+
+extern "C" int beat_math_probe(beat_ctx* ctx, int fn, const double* dev_in, int64_t ld, double* dev_out, int64_t n) {
+  BEAT_REQUIRE(ctx != nullptr && dev_in != nullptr && dev_out != nullptr, "bad argument");
+  BEAT_REQUIRE(fn >= 0 && fn < BEAT_MATH_COUNT, "fn must be 0..%d", BEAT_MATH_COUNT - 1);
+  BEAT_REQUIRE(n > 0 && ld >= n && n <= ((int64_t)1 << 31) * BEAT_BLOCK, "need 0 < n <= ld");
+  const unsigned grid = (unsigned)((n + BEAT_BLOCK - 1) / BEAT_BLOCK);
+  BEAT_KERNEL(math_probe_kernel, dim3(grid), dim3(BEAT_BLOCK), 0, ctx->stream, fn, dev_in, ld, dev_out, n);
+  BEAT_LAUNCH_CHECK();
+  return BEAT_OK;
+}
 
 extern "C" int beat_stream_probe(beat_ctx* ctx, double* dev, int64_t n, int mode, int policy, int unroll, int blocks,
                                  int rows, int64_t ld) {

@@ -23,11 +23,13 @@
 // exp() for the cell-model kernels.  x = k ln2/256 + r with |r| <= ln2/512, k = 256 m + j:
 //   exp(x) = 2^m * 2^(j/256) * (1 + r + r^2/2 + r^3/6 + r^4/24)
 // 2^(j/256) comes from a 256-entry table staged in LDS (2 KB), the truncation error of the degree-4 polynomial
-// is < 4e-17, so the result is within ~1 ulp.  k is rounded with the 1.5 * 2^52 trick: one fma gives the rounded
+// is < 4e-17; measured against the correctly rounded value (tests/test_device_math_host.py, _gpu.py) the result is within 1.31
+// ulp (1.33 for FastMathT<true>), 1.08 * 2^-1074 where it is subnormal.  k is rounded with the 1.5 * 2^52 trick: one fma gives the rounded
 // value in the mantissa and k as a signed integer in the low dword (no v_rndne / v_cvt).  No overflow / underflow / NaN
-// handling: arguments in these models are bounded (|x| < 700), and the result must be a normal number (BEAT_EXP_LO / _HI below:
-// round 6 scales by an integer add into the exponent field); arguments that are rate * dt products (gate updates, exp(J dt))
-// leave that range at unphysiological potentials and are clamped by their callers (beat_clamp_exp_arg).
+// handling of its own: with v_ldexp_f64 (FastMath) the scaling underflows through the subnormals to 0 and overflows to inf as libm
+// does, for |k| < 2^31; FastMathT<true> scales by an integer add into the exponent field and needs a normal result (BEAT_EXP_LO /
+// BEAT_EXP_HI_INT below).  Arguments that are rate * dt products (gate updates, exp(J dt)) leave the range at unphysiological
+// potentials and are clamped by their callers (beat_clamp_exp_arg).
 // 12 VALU instructions (13 with shift + v_ldexp_f64 until round 5, 16 with the 64-entry table and a degree-5 polynomial, ~27 for
 // the library routine) -- the ionic kernels are fp64-issue bound and the TP06 step evaluates 51 of them per node.
 // ------------------------------------------------------------------------------------------------
@@ -101,8 +103,10 @@ __device__ const double kExp2Tab[BEAT_EXP_TAB] = {
 
 // log(): x = 2^e * m, m in [1, 2); the top 7 mantissa bits pick c_j = 1 + (j + 0.5)/128 from a table of
 // (1/c_j, log c_j) pairs (2 KB in LDS, one ds_read_b128); r = m/c_j - 1, |r| <= 2^-8, and
-// log x = e ln2 + log c_j + (r - r^2/2 + ... - r^6/6), truncation < 2e-18.  Arguments here are
-// concentration ratios (positive, normal, far from 1), so no special cases.
+// log x = e ln2 + log c_j + (r - r^2/2 + ... - r^6/6), truncation < 2e-18; measured: absolute error <= 0.93 2^-53 max(|log x|, 1)
+// (the table does not centre on 1: relative error up to 4e-11 next to x = 1).  The arguments are concentrations and their
+// ratios; a diverged cell hands it zeros, negatives, NaN or inf, and the result is then libm's (-inf, NaN, NaN, +inf) -- the
+// reference evaluates the same expressions with NumPy, and a cell that has diverged must stay visibly diverged.
 struct LogEntry {
   double inv, logc;
 };
@@ -247,16 +251,21 @@ __device__ const LogEntry kLogTab[128] = {
 #define BEAT_ODE_WAVES_PER_NODE 2  // kernels whose parameters are per-node rows (TP06: 53 more doubles per lane)
 #endif
 
-// The range FastMath::exp takes (round 6): on the device the factor 2^m goes into the table value's exponent field by an INTEGER add
-// (one instruction in place of the shift + v_ldexp_f64 pair), which neither underflows to 0 nor overflows to inf -- the result must be a
-// normal number: exp(-708) = 3.3e-308 (m = -1022) ... exp(709) = 8.2e307.  Callers whose argument is a rate * dt product clamp it into
-// that range: below -708 the clamp changes no RESULT (1 - 3e-308 = 1, 3e-308 - 1 = -1 in fp64: what the gate updates and the GRL1
-// increments do with it), above 709.78 the callers put the overflow back (beat_exp_overflow: the scheme's literal expression gives
-// inf there, and so does the oracle).
-constexpr double BEAT_EXP_LO = -708.0, BEAT_EXP_HI = 709.0;
-__device__ __forceinline__ double beat_clamp_exp_arg(double x) { return fmin(fmax(x, BEAT_EXP_LO), BEAT_EXP_HI); }
-// exp(x) for any x >= BEAT_EXP_LO given e = FastMath::exp(min(x, BEAT_EXP_HI)): inf where exp overflows (x > 709.78...)
-__device__ __forceinline__ double beat_exp_overflow(double x, double e) { return x > 709.782712893384 ? HUGE_VAL : e; }
+// The range FastMath::exp takes.  FastMathT<true> (round 6, off: BEAT_TP06_EXP_INT) puts the factor 2^m into the table value's
+// exponent field by an INTEGER add (one instruction in place of the shift + v_ldexp_f64 pair), which neither underflows to 0 nor
+// overflows to inf -- its result must be a normal number: exp(-708) = 3.3e-308 (m = -1022) ... exp(709) = 8.2e307.  FastMath
+// (v_ldexp_f64) is right up to the overflow threshold ln(DBL_MAX) = 709.782712893384 and below -708 as well.  Callers whose argument
+// is a rate * dt product clamp it to the range of the flavour they use: below -708 the clamp changes no RESULT (1 - 3e-308 = 1,
+// 3e-308 - 1 = -1 in fp64: what the gate updates and the GRL1 increments do with it); above the upper end the callers put the
+// overflow back (beat_exp_overflow: the scheme's literal expression gives inf beyond 709.78, and so does the oracle).  Up to round 6
+// both flavours were clamped at 709, and TP06's exp(J dt) came out as exp(709) for J dt in (709, 709.78].
+constexpr double BEAT_EXP_LO = -708.0, BEAT_EXP_HI = 709.782712893384, BEAT_EXP_HI_INT = 709.0;
+template <bool INT_SCALE>
+__device__ __forceinline__ double beat_clamp_exp_arg(double x) {
+  return fmin(fmax(x, BEAT_EXP_LO), INT_SCALE ? BEAT_EXP_HI_INT : BEAT_EXP_HI);
+}
+// exp(x) for any x >= BEAT_EXP_LO given e = FastMath::exp(beat_clamp_exp_arg(x)): inf where exp overflows (x > 709.78...)
+__device__ __forceinline__ double beat_exp_overflow(double x, double e) { return x > BEAT_EXP_HI ? HUGE_VAL : e; }
 // The table entry as the device's exp() wants it: 2^(j/256) with j << 12 taken off its high word, so that adding the whole
 // k = 256 m + j, shifted by 12, leaves m in the exponent field (k << 12 = (m << 20) + (j << 12))
 template <bool INT_SCALE>
@@ -282,6 +291,37 @@ __device__ __forceinline__ double beat_rsqrt(double x) {
   return fma(r * fma(e, 0.375, 0.5), e, r);
 }
 
+// The pieces of FastMath::log that differ between the device and the host build of this header (tests/*_host_harness.cpp):
+// frexp's mantissa and exponent; x > 0 and finite (v_cmp_class_f64); log's value where x is not: -inf for +-0, +inf for +inf,
+// NaN for x < 0 and NaN, as y - 1/sqrt(y) with y = x + 0 (which is +0 for -0)
+__device__ __forceinline__ double beat_frexp_mant(double x) {
+#ifdef __AMDGCN__
+  return __builtin_amdgcn_frexp_mant(x);
+#else
+  int e;
+  return std::frexp(x, &e);
+#endif
+}
+__device__ __forceinline__ int beat_frexp_exp(double x) {
+#ifdef __AMDGCN__
+  return __builtin_amdgcn_frexp_exp(x);
+#else
+  int e = 0;
+  return std::isfinite(x) ? (std::frexp(x, &e), e) : 0;
+#endif
+}
+__device__ __forceinline__ bool beat_pos_finite(double x) {
+#ifdef __AMDGCN__
+  return __builtin_amdgcn_class(x, 0x180);  // +subnormal | +normal
+#else
+  return x > 0.0 && x < HUGE_VAL;
+#endif
+}
+__device__ __forceinline__ double beat_log_special(double x) {
+  const double y = x + 0.0;
+  return y - __builtin_amdgcn_rsq(y);
+}
+
 // a double constant through a scalar register pair (see torord_dyncl.h: phi_small)
 __device__ __forceinline__ double beat_sconst(double c) {
 #ifdef __AMDGCN__  // (tests/tp06_host_harness.cpp builds this header with g++)
@@ -294,7 +334,7 @@ __device__ __forceinline__ double beat_sconst(double c) {
 #define BEAT_FM_PIN 1
 #endif
 // INT_SCALE (round 6, the TP06 step): exp() puts 2^m into the table value's exponent field by an integer add -- see exp() and
-// BEAT_EXP_LO / _HI; the table then holds adjusted entries (beat_exp_tab_entry).  false: v_ldexp_f64, any argument down to -5.8e6
+// BEAT_EXP_LO / _HI_INT; the table then holds adjusted entries (beat_exp_tab_entry).  false: v_ldexp_f64, any argument down to -5.8e6
 // underflows to 0 (ToR-ORd, the generated models, the forward-Euler models).
 template <bool INT_SCALE_>
 struct FastMathT {
@@ -306,18 +346,23 @@ struct FastMathT {
   // register allocator re-materialised it (two v_mov_b32) at ten places of the TP06 step rather than keep two registers live
   double magic = 6755399441055744.0;
   __device__ __forceinline__ double log(double x) const {
-    const int hi = __double2hiint(x);
-    const int e = ((hi >> 20) & 0x7ff) - 1023;
+    // x = xm 2^(e + 1), xm in [0.5, 1): v_frexp_mant / v_frexp_exp normalise a subnormal x as well (the exponent field does not)
+    const double xm = beat_frexp_mant(x);
+    const int hi = __double2hiint(xm);
+    const int e = beat_frexp_exp(x) - 1;
     const LogEntry t = ltab[(hi >> 13) & 127];
-    const double m = __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(x));  // mantissa in [1, 2)
+    const double m = __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(xm));  // mantissa in [1, 2)
     const double r = fma(m, t.inv, -1.0);
     double p = fma(r, -1.0 / 6.0, 1.0 / 5.0);
     p = fma(r, p, -0.25);
     p = fma(r, p, 1.0 / 3.0);
     p = fma(r, p, -0.5);
     p = fma(r * r, p, r);
+    // x outside (0, inf): e ln2 becomes -inf (+-0), +inf (+inf) or NaN (x < 0, NaN), and the two fma below carry it into the
+    // result (p is finite: m is in [1, 2) whatever x is).  (double)e and all three have a zero low dword: one v_cndmask_b32
     const double ed = (double)e;
-    return fma(ed, 0.693147180559663, t.logc + fma(ed, 2.8235290563031577e-13, p));
+    const double es = __hiloint2double(beat_pos_finite(x) ? __double2hiint(ed) : __double2hiint(beat_log_special(x)), __double2loint(ed));
+    return fma(es, 0.693147180559663, t.logc + fma(es, 2.8235290563031577e-13, p));
   }
   __device__ __forceinline__ double exp(double x) const {
     const double kb = fma(x, 369.3299304675746, magic);    // 256 / ln 2; 1.5 * 2^52: k in the low dword
@@ -335,7 +380,7 @@ struct FastMathT {
 #ifdef __AMDGCN__
     if constexpr (INT_SCALE) {
       // 2^m 2^(j/256): k << 12 added to the (adjusted, beat_exp_tab_entry) table value's high word -- one v_lshl_add_u32; x in
-      // [BEAT_EXP_LO, BEAT_EXP_HI] (NaN stays NaN: r is NaN).  Bit for bit what ldexp gives there: scaling by 2^m commutes with the fma.
+      // [BEAT_EXP_LO, BEAT_EXP_HI_INT] (NaN stays NaN: r is NaN).  Bit for bit what ldexp gives there: scaling by 2^m commutes with the fma.
       const double ts = __hiloint2double(__double2hiint(t) + (int)((unsigned)ki << 12), __double2loint(t));
       return fma(ts, p, ts);
     }
@@ -597,8 +642,8 @@ struct FhnReadme {
 //    exp(+-(V+c)/k) for k in {5, 10, 20} come from E20 = exp(V/20) by squaring, k = 7 and k = 6
 //    likewise; exp(-V F/RT) = exp(-0.1 V F/RT)^10, exp((gamma-1) V F/RT) = exp(gamma V F/RT) exp(-V F/RT),
 //    the four K1 exponentials come from exp(0.02 u) and exp(0.0002 u), u = V - E_K.
-//  * a/b is computed as a * rcp(b) with two Newton steps on v_rcp_f64 (<= 1 ulp for the finite,
-//    normal denominators that occur here) instead of the ~12-instruction IEEE division sequence.
+//  * a/b is computed as a * rcp(b): v_rcp_f64 and one third-order correction step (beat_rcp; <= 1 ulp for the finite, normal
+//    denominators that occur here, tests/test_device_math_gpu.py) instead of the ~12-instruction IEEE division sequence.
 //  * parameter-only sub-expressions are evaluated once per launch on the host (Derived).
 // ------------------------------------------------------------------------------------------------
 #if defined(__clang__) && !defined(BEAT_TP06_NO_CONTRACT)
@@ -618,7 +663,7 @@ struct Tp06Grl1 {
   static constexpr int WAVES_PER_NODE = BEAT_ODE_WAVES_PER_NODE;  // per-node parameter rows: NP more values per lane
   static constexpr int STASH_SLOTS = BEAT_TP06_STASH;  // values parked in LDS while the gate blocks run (beat_stash)
   // exp() with the factor 2^m added into the exponent field (FastMathT<true>: one instruction less per exp(), 51 per node; results in
-  // the normal range only, i.e. |V| < ~370 mV -- beyond it the Gaussian time constants' arguments leave [BEAT_EXP_LO, BEAT_EXP_HI])
+  // the normal range only, i.e. |V| < ~370 mV -- beyond it the Gaussian time constants' arguments leave [BEAT_EXP_LO, BEAT_EXP_HI_INT])
   // Measured (profiles/r06_ode_addressing.md): 1778 -> 1729 static VALU instructions, 8.10 -> 8.00 ms in one process, 12.20 -> 12.165 ms per
   // 512^3 step -- 0.3 %, for a step that would return garbage instead of NaN beyond its range: OFF.
 #ifndef BEAT_TP06_EXP_INT
@@ -698,12 +743,12 @@ struct Tp06Grl1 {
     id = rcd * c;
   }
   __device__ static __forceinline__ double grl1(const FM& fm, double y, double fy, double J, double dt) {
-    return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg(J * dt))) - 1.0) * rcp(J) : fy * dt);
+    return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg<FM::INT_SCALE>(J * dt))) - 1.0) * rcp(J) : fy * dt);
   }
   // same with 1/J supplied by the caller (batched); rJ is only used where |J| > 1e-8
   __device__ static __forceinline__ double grl1r(const FM& fm, double y, double fy, double J, double rJ,
                                                  double dt) {
-    return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg(J * dt))) - 1.0) * rJ : fy * dt);
+    return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg<FM::INT_SCALE>(J * dt))) - 1.0) * rJ : fy * dt);
   }
   __device__ static __forceinline__ double guard(double J) { return (fabs(J) > 1e-8) ? J : 1.0; }
   // The GRL1 increment f (exp(J dt) - 1) / J of a non-gate state as f dt phi(J dt), phi(z) = (exp(z) - 1) / z by its Taylor polynomial
@@ -716,7 +761,7 @@ struct Tp06Grl1 {
 #define BEAT_TP06_PHI 1
 #endif
   __device__ static __forceinline__ double phi_small(double z) {
-    double ph = z * beat_sconst(1.0 / 362880.0) + beat_sconst(1.0 / 40320.0);
+    double ph = fma(z, beat_sconst(1.0 / 362880.0), beat_sconst(1.0 / 40320.0));
     ph = fma(z, ph, beat_sconst(1.0 / 5040.0));
     ph = fma(z, ph, beat_sconst(1.0 / 720.0));
     ph = fma(z, ph, beat_sconst(1.0 / 120.0));
@@ -735,7 +780,7 @@ struct Tp06Grl1 {
 #define BEAT_TP06_GATE_PHI 0  // 1: 1 - exp(z), z = -dt/tau, as -z phi7(z) when |z| <= 1/32 (per lane); measured, see profiles/r06_ode_addressing.md
 #endif
   __device__ static __forceinline__ double phi7(double z) {  // (exp(z) - 1) / z, |z| <= 1/32: first omitted term z^8 / 9! < 3e-18
-    double ph = z * beat_sconst(1.0 / 40320.0) + beat_sconst(1.0 / 5040.0);
+    double ph = fma(z, beat_sconst(1.0 / 40320.0), beat_sconst(1.0 / 5040.0));
     ph = fma(z, ph, beat_sconst(1.0 / 720.0));
     ph = fma(z, ph, beat_sconst(1.0 / 120.0));
     ph = fma(z, ph, beat_sconst(1.0 / 24.0));

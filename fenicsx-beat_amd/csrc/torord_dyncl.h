@@ -448,7 +448,7 @@ struct TorordGrl1T {
   // compiler materialises each one in a VGPR pair -- two v_mov_b32 ahead of every fma of the Horner scheme, three VALU
   // instructions per step instead of one.  Opaque in an SGPR pair it costs two s_mov on the scalar unit.)
   BEAT_DV static double phi_small(double z) {
-    double ph = z * BEAT_SCONST(1.0 / 362880.0) + BEAT_SCONST(1.0 / 40320.0);  // (two constants in one fma: one of them in VGPRs)
+    double ph = fma(z, BEAT_SCONST(1.0 / 362880.0), BEAT_SCONST(1.0 / 40320.0));  // (two constants in one fma: one of them in VGPRs)
     ph = fma(z, ph, BEAT_SCONST(1.0 / 5040.0));
     ph = fma(z, ph, BEAT_SCONST(1.0 / 720.0));
     ph = fma(z, ph, BEAT_SCONST(1.0 / 120.0));
@@ -469,7 +469,7 @@ struct TorordGrl1T {
   // is -z phi(z) by the Taylor polynomial of degree 7 (first omitted term z^8/9! < 3e-18): 7 fma in place of the exp().
   static constexpr double GATE_WINDOW = 1.0 / 32.0;
   BEAT_DV static double phi7(double z) {
-    double ph = z * BEAT_SCONST(1.0 / 40320.0) + BEAT_SCONST(1.0 / 5040.0);
+    double ph = fma(z, BEAT_SCONST(1.0 / 40320.0), BEAT_SCONST(1.0 / 5040.0));
     ph = fma(z, ph, BEAT_SCONST(1.0 / 720.0));
     ph = fma(z, ph, BEAT_SCONST(1.0 / 120.0));
     ph = fma(z, ph, BEAT_SCONST(1.0 / 24.0));

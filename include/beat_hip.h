@@ -185,6 +185,12 @@ int beat_fill(beat_ctx* ctx, double* dev_dst, double value, int64_t n);
  *  blocks: workgroups of 256 threads walking the array with a grid-stride loop; 0 = as many as the array has chunks */
 int beat_stream_probe(beat_ctx* ctx, double* dev, int64_t n, int mode, int policy, int unroll, int blocks, int rows,
                       int64_t ld);
+/* Math probe: the ionic kernels' arithmetic helpers one at a time (fenicsx-beat_amd/csrc/beat_math_probe.h: FastMath's exp and
+ * log in both flavours, beat_rcp / beat_rsqrt, the batched reciprocals of TP06 and ToR-ORd, the GRL1 polynomials and the
+ * composite gate / GRL1 updates), evaluated as the kernels evaluate them, for the accuracy tests (tests/test_device_math_gpu.py).
+ * dev_in is (k, ld), dev_out (m, ld), k and m the helper's input and output counts; column i < n is one evaluation.
+ * fn: BEAT_MATH_* of beat_math_probe.h (beat._hip.MATH_*). */
+int beat_math_probe(beat_ctx* ctx, int fn, const double* dev_in, int64_t ld, double* dev_out, int64_t n);
 /* dst[i] = src[idx[i]] (gather) / dst[idx[i]] = src[i] (scatter): marker-wise state transfer of
  * DolfinMultiODESolver (odesolver.py:280-292). */
 int beat_gather(beat_ctx* ctx, double* dev_dst, const double* dev_src, const int64_t* dev_idx, int64_t n);

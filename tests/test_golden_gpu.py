@@ -302,6 +302,61 @@ def test_torord_kernel_on_unphysiological_states_agrees_wherever_the_specificati
         assert cols.sum() > n // 3 and np.isfinite(out[:, cols]).all()
         err = np.abs(out[:, cols] - ref[:, cols]) / np.maximum(np.abs(ref[:, cols]), scale0)
         assert err.max() < 1e-7, (dt, float(err.max()), names[int(np.unravel_index(err.argmax(), err.shape)[0])])
+    # a concentration that enters a logarithm (reversal potentials) at or below 0 or NaN: the oracle's column is not finite, and
+    # neither is the kernel's -- a diverged cell stays visibly diverged (FastMath::log returned finite numbers there up to round 6)
+    _log_arguments_stay_diverged(lambda X, dt: torord.generalized_rush_larsen(states=X, t=0.3, parameters=P, dt=dt),
+                                 lambda X, dt: otor.torord_generalized_rush_larsen(X, 0.3, dt, P), base, names,
+                                 ("nai", "ki", "cli", "clss", "cai"), rng)
+
+
+def _log_arguments_stay_diverged(kernel, oracle, base, names, log_states, rng, n=600):
+    """Columns of `base` with one of `log_states` set to 0, -0, a negative value or NaN: wherever the oracle's column is
+    non-finite (most of them: a zero concentration can also end as a finite 1/(1 + inf) = 0) the kernel's is too."""
+    import warnings
+
+    S = base[:, rng.integers(0, base.shape[1], n)].copy()
+    rows = np.array([names.index(s) for s in log_states])
+    which = rng.integers(0, len(rows), n)
+    S[rows[which], np.arange(n)] = rng.choice([0.0, -0.0, -1e-6, -0.3, -50.0, np.nan], n)
+    for dt in (0.01, 0.05):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ref = oracle(S, dt)
+        out = kernel(S, dt)
+        ref_bad = ~np.isfinite(ref).all(axis=0)
+        assert ref_bad.sum() > n // 2
+        miss = ref_bad & np.isfinite(out).all(axis=0)
+        assert not miss.any(), [names[rows[which[i]]] + f"={S[rows[which[i]], i]}" for i in np.flatnonzero(miss)[:5]]
+
+
+def test_tp06_kernel_on_diverged_log_arguments_stays_non_finite():
+    """TP06's reversal potentials take the log of Na_i, K_i and Ca_i: where one of them is <= 0 or NaN the NumPy oracle's column
+    is not finite, and the kernel's must not be either (twin of the ToR-ORd check above)."""
+    from beat.models import tp06
+
+    from oracle import ionic
+
+    base = np.repeat(ionic.tp06_init_state_values()[:, None], 8, axis=1)
+    base[ionic.tp06_state_index("V")] = [-86.2, -60.0, -20.0, 0.0, 15.0, 30.0, 60.0, -100.0]
+    P = ionic.tp06_init_parameter_values(stim_amplitude=0.0)
+    _log_arguments_stay_diverged(lambda X, dt: tp06.generalized_rush_larsen(states=X, t=5.0, parameters=P, dt=dt),
+                                 lambda X, dt: ionic.tp06_generalized_rush_larsen(X, 5.0, dt, P), base, list(ionic.TP06_STATES),
+                                 ("Na_i", "K_i", "Ca_i"), np.random.default_rng(16))
+
+
+def test_torord_land_kernel_on_diverged_log_arguments_stays_non_finite():
+    """The Land instance's exp(n log(cai)) / exp(n/2 log(CaTrpn)) and the reversal potentials: a log argument <= 0 or NaN makes
+    the oracle's column non-finite, and the kernel's too."""
+    from beat.models import torord_land as tl
+
+    from oracle import torord as otor
+
+    g = np.load(GOLD / "torord_land_spec.npz")
+    names = list(g["state_names"])
+    P = g["parameter_sets"][0]
+    _log_arguments_stay_diverged(lambda X, dt: tl.generalized_rush_larsen(states=X, t=float(g["t"]), parameters=P, dt=dt),
+                                 lambda X, dt: otor.torord_land_generalized_rush_larsen(X, float(g["t"]), dt, P), g["states"], names,
+                                 ("nai", "ki", "cli", "clss", "cai", "CaTrpn"), np.random.default_rng(17))
 
 
 def test_torord_land_kernel_matches_the_ode_spec_golden_and_the_oracle():
