@@ -7,11 +7,13 @@ runs in ``libbeat_hip.so``.  There is no CPU fallback."""
 
 from . import (  # noqa: F401
     base_model,
+    butcher,
     conductivities,
     ecg,
     geometry,
     grid,
     io,
+    irksome_model,
     models,
     monodomain_model,
     monodomain_solver,
@@ -23,6 +25,7 @@ from . import (  # noqa: F401
     utils,
 )
 from .ecg import ECGRecovery
+from .irksome_model import IrksomeMonodomainModel
 from .monodomain_model import MonodomainModel
 from .monodomain_solver import MonodomainSplittingSolver
 from .stimulation import Stimulus
@@ -32,7 +35,7 @@ __version__ = "0.1.0"
 __program_name__ = "fenicsx-beat-amd"
 
 __all__ = [
-    "monodomain_model", "odesolver", "base_model", "MonodomainModel", "monodomain_solver",
+    "monodomain_model", "irksome_model", "IrksomeMonodomainModel", "butcher", "odesolver", "base_model", "MonodomainModel", "monodomain_solver",
     "MonodomainSplittingSolver", "utils", "single_cell", "conductivities", "stimulation", "geometry", "grid", "models",
     "Stimulus", "io", "ecg", "ECGRecovery", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
 ]

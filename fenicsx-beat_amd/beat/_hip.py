@@ -177,6 +177,13 @@ SIGNATURES.update({
         [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_dbl), _int, _vp, _vp, _dbl, _dbl, _int, _int, C.POINTER(KspInfo), C.POINTER(_int)],
     ),
     "beat_pde_solve_dist_begin": (_int, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_dbl), _int, _vp, _vp, _dbl, _dbl, _int]),
+    # implicit Runge-Kutta stages (beat.irksome_model)
+    "beat_pde_zwork_doubles": (_i64, [_vp]),
+    "beat_pde_zsolve": (_int, [_vp, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _int, C.POINTER(KspInfo)]),
+    "beat_pde_zapply": (_int, [_vp, _dbl, _dbl, _dbl, _vp, _vp, _vp, _vp]),
+    "beat_pde_rk_rhs": (_int, [_vp, C.POINTER(_vp), C.POINTER(_dbl), C.POINTER(_dbl), _int, C.POINTER(_vp), C.POINTER(_dbl),
+                               C.POINTER(_dbl), _int, _vp, _vp]),
+    "beat_pde_rk_update": (_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_dbl), C.POINTER(_dbl), _int]),
 })
 
 _lib = None

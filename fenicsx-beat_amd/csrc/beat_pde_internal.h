@@ -50,6 +50,7 @@ struct beat_pde {
   double* d_tabs = nullptr;
   double* d_st = nullptr;  // 16 doubles, PCG scalar state of beat_pde_solve
   int last_iters = -1;
+  int z_last_iters = -1;  // iterations of the last shifted solve (beat_pde_zsolve: its first chunk of enqueued iterations)
   unsigned vec_grid = 1;
   double* d_alphas = nullptr;  // PRING_MAX step lengths of the deferred-x PCG
   // A solve that has been ENQUEUED and not yet looked at by the host (beat_pde_solve_begin / _end, round 5): right-hand side, the

@@ -473,6 +473,38 @@ int beat_pde_solve(beat_pde* pde, const double* dev_v_prev, const double* const*
                    const double* host_stim_amp, int n_stim, double* dev_x, double* dev_work,
                    double rtol, double atol, int max_it, beat_ksp_info* info);
 
+/* ---- implicit Runge-Kutta stages: replace Irksome's StageDerivativeTimeStepper and its PETSc solve
+ *      (src/beat/irksome_model.py:57-69, advance() at :96) -----------------------------------------------------
+ * The stage system of a Butcher matrix A is diagonalised on the host (beat/butcher.py); every eigenvalue lambda
+ * leaves one shifted solve  S u = rhs,  S = a Mass + (b + i c) K  (a = C_m, b + i c = lambda dt).  Complex fields are
+ * split: a real and an imaginary field, each laid out as any field of the operator.  Constant-coefficient operators
+ * on an undivided grid only (EINVAL otherwise).
+ *
+ * beat_pde_zsolve: Jacobi-preconditioned COCG (CG with the unconjugated form p^T q; diag(S) is the preconditioner)
+ * from x = 0 to ||r||_2 <= max(rtol ||rhs||_2, atol) in the conjugated norm; scalars stay on the device behind a
+ * stop latch, the host looks at them once per chunk of enqueued iterations.  dev_x_im = NULL (then c = 0 and
+ * dev_rhs_im = NULL): the real instantiation of the same kernels, Jacobi-PCG.  dev_work: beat_pde_zwork_doubles(pde)
+ * doubles.  info as beat_pde_solve's; BEAT_ENOTCONV when max_it ran out (or the bilinear form broke down, reason -5).
+ * Synchronises. */
+int64_t beat_pde_zwork_doubles(const beat_pde* pde);
+int beat_pde_zsolve(beat_pde* pde, double a, double b, double c, const double* dev_rhs_re, const double* dev_rhs_im,
+                    double* dev_x_re, double* dev_x_im, double* dev_work, double rtol, double atol, int max_it,
+                    beat_ksp_info* info);
+/* y = S x for complex x (tests, src/beat/irksome_model.py:57: the form Irksome assembles per stage). */
+int beat_pde_zapply(beat_pde* pde, double a, double b, double c, const double* dev_x_re, const double* dev_x_im,
+                    double* dev_y_re, double* dev_y_im);
+/* Stage right-hand side  r = sum_m gamma_m w_m - K (sum_j s_j y_j)  (the load G(t_j) = sum_k amp_k(t_j) w_k of
+ * base_model.py:247-248 combined over the stage times, and the stiffness term of v_n and earlier stages);
+ * gamma_m, s_j complex (host_*_im may be NULL: 0), w_m and y_j real fields, at most BEAT_MAX_STIM of each.
+ * dev_r_im = NULL: a real right-hand side (every imaginary coefficient must be 0). */
+int beat_pde_rk_rhs(beat_pde* pde, const double* const* host_dev_w, const double* host_gamma_re,
+                    const double* host_gamma_im, int n_w, const double* const* host_dev_y, const double* host_s_re,
+                    const double* host_s_im, int n_y, double* dev_r_re, double* dev_r_im);
+/* Final update of the step  v += sum_i Re(d_i u_i)  over up to BEAT_MAX_STIM stage fields (host_dev_u_im or
+ * an entry of it NULL: a real stage); Irksome's v_{n+1} = v_n + dt sum_i b_i k_i in the transformed stages. */
+int beat_pde_rk_update(beat_pde* pde, double* dev_v, const double* const* host_dev_u_re, const double* const* host_dev_u_im,
+                       const double* host_d_re, const double* host_d_im, int n_u);
+
 /* ---- slab-decomposed diffusion solve: one C call per solve, communication inside the library -------------
  * Replaces, on a grid cut into z-slabs (one rank per GPU), what PETSc does inside KSP.solve on a partitioned
  * mesh: the neighbour exchange of ghost values (b.ghostUpdate / VecScatter, src/beat/base_model.py:203-206,242)
