@@ -9,7 +9,7 @@
 
 enum BeatMathFn {
   BEAT_MATH_EXP = 0,       // FastMath::exp (v_ldexp_f64 scaling: ToR-ORd, TP06, the generated models)
-  BEAT_MATH_EXP_INT,       // FastMathT<true>::exp (integer add into the exponent field; BEAT_TP06_EXP_INT)
+  BEAT_MATH_EXP_INT,       // FastMathT<true>::exp (integer add into the exponent field; no model uses it)
   BEAT_MATH_LOG,           // FastMath::log
   BEAT_MATH_LOG_INT,       // FastMathT<true>::log
   BEAT_MATH_RCP,           // beat_rcp

@@ -152,7 +152,7 @@ void init_locked(JitState& s) {
     if (::stat(cc.c_str(), &st) == 0) h = fnv(std::to_string((long long)st.st_size) + ":" + std::to_string((long long)st.st_mtime), h);
   }
 #ifdef BEAT_BUILD_EXTRA_FLAGS
-  // the EXTRA flags this library was built with (csrc/Makefile: variant libraries for A/B runs, -DBEAT_ODE_NT=3 ...): an instance
+  // the EXTRA flags this library was built with (csrc/Makefile: variant libraries for A/B runs, -DBEAT_TP06_WAVES=3 ...): an instance
   // compiled at run time is built with them too and cached under its own key
   s.extra = BEAT_BUILD_EXTRA_FLAGS;
   h = fnv(s.extra, h);

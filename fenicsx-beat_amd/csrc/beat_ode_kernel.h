@@ -12,10 +12,6 @@
 #include <type_traits>
 #include <vector>
 #include "ionic_models.h"
-
-#ifndef BEAT_ODE_PROBE
-#define BEAT_ODE_PROBE 0  // 1 / 2: probe builds of the plain step kernel (memory only / arithmetic only), tools/ode_probe.sh
-#endif
 #include "torord_dyncl.h"
 
 
@@ -51,39 +47,9 @@ struct PendingNow {
   int count;
   beat_pde_detail::GuessTerms gt;
 };
-// How a launch enqueued behind an open solve reads that solve's update count (BEAT_PENDING_READ, measured at 512^3 on one box,
-// profiles/r05_step_gap.md): 0 = per tile with a vector load through the generic pointer -- every pending load of the tile waits on
-// its round trip, and its s_waitcnt vmcnt(0) on the previous tile's stores as well: +0.10 ms on the ionic kernel of step() against the
-// library's loop, which knows the count on the host; 1 = once per launch, kept in an SGPR across the tile loop: the difference is
-// gone, but BOTH paths lose 0.1 - 0.4 ms to the changed register allocation; 2 = per tile with a SCALAR load (the state was written
-// by earlier kernels and is constant for this one; the constant cache is invalidated at kernel start): no vector-memory wait;
-// 3 = thread 0 of a block reads latch and count once, ahead of the barrier that follows the table set-up, into LDS; every tile
-// takes the count from there (a volatile LDS read: nothing lives across the tile loop, no global round trip per tile).  3 is the
-// build: against 2, alternating on two boxes (13 runs each, profiles/r05_step_gap.md), the ionic kernel of step() AND of the library's
-// loop sat at 9.68 - 9.72 ms in every run, where build 2 ranged from 9.63 to 10.03 (the two modes of this kernel that rounds 3 and 4
-// chased): mean step 13.55 - 13.57 against 13.62 - 13.76 ms.  (Not immune: 9.65 - 10.07 on a third box.)
-#ifndef BEAT_PENDING_READ
-#define BEAT_PENDING_READ 3
-#endif
-__device__ __forceinline__ int beat_pending_read(const PendingV& p) {
-#if BEAT_PENDING_READ == 1
-  return p.dev_st != nullptr ? __builtin_amdgcn_readfirstlane((int)p.dev_st[beat_pde_detail::NUPD]) : -1;
-#else
-  return -1;
-#endif
-}
+// (nupd: the open solve's update count, -1: the host's count and guess terms)
 __device__ __forceinline__ PendingNow beat_pending_now(const PendingV& p, int nupd) {
   PendingNow o{p.count, p.gt};
-#if BEAT_PENDING_READ == 0
-  if (p.dev_st != nullptr) nupd = (int)p.dev_st[beat_pde_detail::NUPD];
-#elif BEAT_PENDING_READ == 2
-  if (p.dev_st != nullptr) {
-    typedef const __attribute__((address_space(4))) double* ConstD;
-    ConstD stc = (ConstD)(uintptr_t)p.dev_st;
-    asm volatile("" : "+s"(stc));
-    nupd = (int)stc[beat_pde_detail::NUPD];
-  }
-#endif
   if (nupd >= 0) {
     o.count = nupd % p.ring_len;
     o.gt.accumulate = nupd >= p.ring_len ? 1 : 0;
@@ -177,14 +143,6 @@ __device__ __forceinline__ D mix_derived(const D& du, const D& dl) {
   return d;
 }
 
-// An IO type with somewhere to park values (ionic_models.h: beat_stash / beat_unstash): slot j of this lane at lds[j * BEAT_BLOCK]
-// (consecutive lanes 8 bytes apart: no bank conflicts), a region no other lane touches -- no barrier
-template <class Base>
-struct StashIO : Base {
-  double* lds;
-  __device__ __forceinline__ void stash(int slot, double v) const { lds[slot * BEAT_BLOCK] = v; }
-  __device__ __forceinline__ double unstash(int slot) const { return lds[slot * BEAT_BLOCK]; }
-};
 // the FastMath flavour a model's step takes (Model::FM; FastMath = v_ldexp_f64 scaling unless the model says otherwise)
 template <class Model, class = void>
 struct beat_fm_type { using type = FastMath; };
@@ -194,37 +152,6 @@ template <class Model, class = void>
 struct beat_fm_pin_wanted : std::false_type {};
 template <class Model>
 struct beat_fm_pin_wanted<Model, std::void_t<decltype(Model::FM_PIN)>> : std::integral_constant<bool, Model::FM_PIN> {};
-template <class Model, class = void>
-struct beat_stash_slots : std::integral_constant<int, 0> {};
-template <class Model>
-struct beat_stash_slots<Model, std::void_t<decltype(Model::STASH_SLOTS)>> : std::integral_constant<int, Model::STASH_SLOTS> {};
-
-// 1: the kernel's scalar arguments are re-read through the opaque kernel-argument pointer in every tile (see the tile loop)
-#ifndef BEAT_KARGS_PER_TILE
-#define BEAT_KARGS_PER_TILE 1
-#endif
-// 1: the thread's index within the block is recomputed per tile (see the tile loop)
-#ifndef BEAT_TID_PER_TILE
-#define BEAT_TID_PER_TILE 1
-#endif
-// cache policy of the class kernel's state rows (BEAT_ODE_CLS_NT: 1 = as the uniform kernels' rows, BEAT_ODE_NT; 0 = plain)
-#ifndef BEAT_ODE_CLS_NT
-#define BEAT_ODE_CLS_NT 1  // (round 6: ToR-ORd classes 2.547 -> 2.522 ms at 256^3 in one process, shell 401^3 9.87 - 10.05 -> 9.81 - 9.96: profiles/r06_inproc_cls_nt.txt)
-#endif
-__device__ __forceinline__ double beat_cls_load(const double* p) {
-#if BEAT_ODE_CLS_NT
-  return beat_row_load(p);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void beat_cls_store(double* p, double v) {
-#if BEAT_ODE_CLS_NT
-  beat_row_store(p, v);
-#else
-  *p = v;
-#endif
-}
 // a double nobody has computed: the register's content (see the pending values of the tile loop)
 __device__ __forceinline__ double beat_any_value() {
   double x;
@@ -235,11 +162,6 @@ __device__ __forceinline__ double beat_any_value() {
 #endif
   return x;
 }
-#if BEAT_PENDING_READ == 3
-#define BEAT_PENDING_TILE_COUNT __builtin_amdgcn_readfirstlane(*(volatile int*)&s_pend[1])
-#else
-#define BEAT_PENDING_TILE_COUNT nupd_dev
-#endif
 template <class Model, bool PER_NODE, bool PEND, bool MARKED = false, bool SPARSE = false, class CT = IdxPack<>,
           unsigned long long DM0 = 0, unsigned long long DM1 = 0>
 __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::WAVES_PER_NODE : Model::WAVES) void ode_step_kernel(
@@ -251,11 +173,9 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   static_assert(BEAT_EXP_TAB == BEAT_BLOCK, "one table entry per thread");
   etab[threadIdx.x] = beat_exp_tab_entry<beat_fm_type<Model>::type::INT_SCALE>(kExp2Tab[threadIdx.x], (int)threadIdx.x);
   if (threadIdx.x < 128) ltab[threadIdx.x] = kLogTab[threadIdx.x];
-  // values a step parks in LDS across the stretch that does not use them (StashIO): the uniform-parameter instances only
-  constexpr int NSTASH = (!PER_NODE && !MARKED) ? beat_stash_slots<Model>::value : 0;
-  __shared__ double stash_lds[NSTASH > 0 ? NSTASH * BEAT_BLOCK : 1];
   __shared__ int cls_jn[MARKED ? BEAT_BLOCK : 1];  // class kernel: the mapped node of each lane (see NodeIOWithV)
-#if BEAT_PENDING_READ == 3
+  // Behind an open solve (PendingV::dev_st) thread 0 reads its latch and update count once, into LDS, and every tile takes the
+  // count from there: no global round trip and nothing held in registers across the tile loop (profiles/r05_step_gap.md).
   __shared__ int s_pend[2];  // [0] the solve ahead has latched (or there is none), [1] its update count (-1: the host's count)
   if (PEND && threadIdx.x == 0) {
     s_pend[0] = pend.dev_st != nullptr ? (pend.dev_st[beat_pde_detail::STOP] != 0.0 ? 1 : 0) : 1;
@@ -265,14 +185,6 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   typename beat_fm_type<Model>::type fm{etab, ltab};
   if constexpr (beat_fm_pin_wanted<Model>::value) beat_fm_pin(fm);  // (two VGPRs for the whole step: a model's choice)
   if (PEND && s_pend[0] == 0) return;  // the solve ahead has not latched (see PendingV)
-#else
-  __syncthreads();
-  typename beat_fm_type<Model>::type fm{etab, ltab};
-  if constexpr (beat_fm_pin_wanted<Model>::value) beat_fm_pin(fm);  // (two VGPRs for the whole step: a model's choice)
-  if (PEND && pend.dev_st != nullptr && pend.dev_st[beat_pde_detail::STOP] == 0.0) return;  // the solve ahead has not latched (see PendingV)
-#endif
-  const int nupd_dev = PEND ? beat_pending_read(pend) : -1;
-  (void)nupd_dev;
   // (Round 3, measured and removed: starting the three blocks that share a CU a third of a tile apart -- s_sleep by
   // (blockIdx.x / 256) % 3 -- to de-phase their load bursts: 9.83 against 9.78 ms at 512^3, A B A B A B on one box.  The
   // 24 576 blocks of a launch replace each other on the CUs 32 times over; whatever phase they start in is gone after
@@ -283,7 +195,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   // of ~21 tiles each (at three waves per SIMD: 10.5-10.6 ms against 10.9-11.3 for one block per tile), which small models keep.
   // (the wave's number in the block lives in an SGPR; the lane number is taken from mbcnt per tile, opaque: whatever is derived from
   // threadIdx.x -- its 64-bit extension, its byte offset -- would otherwise be kept in VGPRs across the tile loop, three of the 128
-  // that four waves per SIMD have: see BEAT_TID_PER_TILE below)
+  // that four waves per SIMD have)
   const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   for (int64_t tile = blockIdx.x;; tile += gridDim.x) {
   // the kernel-argument segment through a pointer the optimiser cannot see through (see below, at the uniform parameters);
@@ -292,9 +204,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   KArgPtr ka = (KArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(ka));
   const PendingV& pendl = *(const PendingV*)(ka + offsetof(OdeStepKernArgHead<Model>, pend));
-#if BEAT_KARGS_PER_TILE
-  // (round 6) the scalar arguments as well, under their own names: as kernel parameters they are loaded once and stay in SGPRs
-  // across the tile loop -- with the class arguments the last spilled SGPRs of the class kernels, i.e. a VGPR of lanes to hold them
+  // the scalar arguments as well, under their own names: as kernel parameters they stay in SGPRs across the tile loop and spill
   const OdeStepKernArgHead<Model>& hd = *(const OdeStepKernArgHead<Model>*)ka;
   double* __restrict__ const states = hd.states;
   const int64_t n = hd.n, ld = hd.ld;
@@ -304,15 +214,10 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   const int v_index = hd.v_index;
   double* __restrict__ const v_copy = hd.v_copy;
   (void)ppn; (void)pld; (void)v_index; (void)v_copy;
-#endif
   if (tile * BEAT_BLOCK >= n) break;
-#if BEAT_TID_PER_TILE
   int lane_now = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   asm volatile("" : "+v"(lane_now));
   const int tid = (wave_in_block << 6) + lane_now;
-#else
-  const int tid = (int)threadIdx.x;
-#endif
   const int64_t tile0 = tile * BEAT_BLOCK;  // the tile's first node: uniform
   unsigned lane_off = (unsigned)tid * 8u;  // the lane's node within the tile, in BYTES (see NodeIO; not const: beat_at)
   const int64_t i = tile0 + tid;
@@ -346,9 +251,10 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
       double* vbase;  // mirror of the potential: the PDE's field (mapped: entry *jn_slot) or v_copy at the tile (entry = lane), or nullptr
       const int* jn_slot;  // LDS: the block's array (uniform; the lane's entry is found from `i`); nullptr: not mapped
       double v;
-      __device__ __forceinline__ double load(int k) const { return k == Model::V_INDEX ? v : beat_cls_load(beat_at(beat_row(base, k, ld), i)); }
+      // (rows non-temporal as in the uniform kernels: ToR-ORd classes 2.547 -> 2.522 ms at 256^3, profiles/r06_inproc_cls_nt.txt)
+      __device__ __forceinline__ double load(int k) const { return k == Model::V_INDEX ? v : beat_row_load(beat_at(beat_row(base, k, ld), i)); }
       __device__ __forceinline__ void store(int k, double x) const {
-        beat_cls_store(beat_at(beat_row(base, k, ld), i), x);
+        beat_row_store(beat_at(beat_row(base, k, ld), i), x);
         if (k == Model::V_INDEX && vbase != nullptr) {
           if (jn_slot != nullptr)
             vbase[*(const int*)((const char*)jn_slot + (i >> 1))] = x;  // entry tid = byte offset / 8
@@ -364,7 +270,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
       // the potential with the pending update applied (and the guess's bookkeeping done) once, ahead of the passes --
       // same expressions and order as NodeIOPending::load / x_flush_kernel: the pending values die here instead of
       // staying live through every pass (-30 VGPRs, no scratch)
-      const PendingNow now = beat_pending_now(pendl, BEAT_PENDING_TILE_COUNT);
+      const PendingNow now = beat_pending_now(pendl, __builtin_amdgcn_readfirstlane(*(volatile int*)&s_pend[1]));
       double pp[BEAT_MAX_PENDING_CLASS], pa[BEAT_MAX_PENDING_CLASS];
 #pragma unroll
       for (int j = 0; j < BEAT_MAX_PENDING_CLASS; ++j) {
@@ -425,7 +331,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
   if (PEND) {
     // all loads issued together (they overlap with the state loads that follow)
     // (every field addressed as its tile's first node -- uniform, SGPRs -- plus the lane's 32-bit offset: see NodeIO)
-    PendingNow now = beat_pending_now(pendl, BEAT_PENDING_TILE_COUNT);
+    PendingNow now = beat_pending_now(pendl, __builtin_amdgcn_readfirstlane(*(volatile int*)&s_pend[1]));
     // (round 6: the pending values are NOT zero-filled where nothing is pending -- every use is behind the same uniform condition as the
     // load; `j < count ? load : 0.0` cost 16 register pairs of zeros per tile, 46 of the step's ~1700 VALU instructions.  The
     // alternative value is "whatever the register holds": an asm statement without instructions that DEFINES the value.)
@@ -490,9 +396,6 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
       }
       const typename Model::Derived dl = Model::derive(pl);
       Model::step(io, pl, dl, fm, t, dt);
-    } else if constexpr (NSTASH > 0) {
-      const StashIO<NodeIOPending<Model::V_INDEX>> sio{io, stash_lds + tid};
-      Model::step(sio, p_uni, d_uni, fm, t, dt);
     } else {
       Model::step(io, p_uni, d_uni, fm, t, dt);
     }
@@ -544,44 +447,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (PER_NODE && CT::count == 0) ? Model::W
       const typename Model::Derived dl = Model::derive(pl);
       Model::step(io, pl, dl, fm, t, dt);
     } else {
-#if BEAT_ODE_PROBE == 1
-      // probe build (never shipped: -DBEAT_ODE_PROBE=1): the kernel's memory traffic alone -- every state read and
-      // written back, same grid and tile loop
-      double tmp[Model::NS];
-#pragma unroll
-      for (int k = 0; k < Model::NS; ++k) tmp[k] = io.load(k);
-#pragma unroll
-      for (int k = 0; k < Model::NS; ++k) io.store(k, tmp[k] * 1.0000000001);
-#elif BEAT_ODE_PROBE == 3
-      // probe build (-DBEAT_ODE_PROBE=3): the traffic of probe 1 with the array addressed tile-major -- the NS rows of a
-      // tile's 256 nodes next to each other (NS * 2 KB contiguous per tile) instead of NS streams ld apart
-      double tmp[Model::NS];
-      double* tb = states + tile * (int64_t)(Model::NS * BEAT_BLOCK) + threadIdx.x;
-#pragma unroll
-      for (int k = 0; k < Model::NS; ++k) tmp[k] = tb[k * BEAT_BLOCK];
-#pragma unroll
-      for (int k = 0; k < Model::NS; ++k) tb[k * BEAT_BLOCK] = tmp[k] * 1.0000000001;
-#elif BEAT_ODE_PROBE == 2
-      // probe build (-DBEAT_ODE_PROBE=2): the kernel's arithmetic alone -- states of the block's first tile (cache hits),
-      // stores behind a condition that never holds
-      struct ProbeIO {
-        double* __restrict__ base;
-        int64_t ld, i, j;
-        __device__ __forceinline__ double load(int k) const { return base[(int64_t)k * ld + j]; }
-        __device__ __forceinline__ void store(int k, double v) const {
-          if (v == 1.2345e300) base[(int64_t)k * ld + i] = v;
-        }
-      };
-      const ProbeIO pio{states, ldl, i, (int64_t)threadIdx.x};
-      Model::step(pio, p_uni, d_uni, fm, t, dt);
-#else
-      if constexpr (NSTASH > 0) {
-        const StashIO<NodeIO> sio{io, stash_lds + tid};
-        Model::step(sio, p_uni, d_uni, fm, t, dt);
-      } else {
-        Model::step(io, p_uni, d_uni, fm, t, dt);
-      }
-#endif
+      Model::step(io, p_uni, d_uni, fm, t, dt);
     }
     if (v_copy != nullptr) v_copy[i] = states[(int64_t)v_index * ldl + i];
   }

@@ -251,7 +251,7 @@ __device__ const LogEntry kLogTab[128] = {
 #define BEAT_ODE_WAVES_PER_NODE 2  // kernels whose parameters are per-node rows (TP06: 53 more doubles per lane)
 #endif
 
-// The range FastMath::exp takes.  FastMathT<true> (round 6, off: BEAT_TP06_EXP_INT) puts the factor 2^m into the table value's
+// The range FastMath::exp takes.  FastMathT<true> (no model uses it: see Tp06Grl1::FM) puts the factor 2^m into the table value's
 // exponent field by an INTEGER add (one instruction in place of the shift + v_ldexp_f64 pair), which neither underflows to 0 nor
 // overflows to inf -- its result must be a normal number: exp(-708) = 3.3e-308 (m = -1022) ... exp(709) = 8.2e307.  FastMath
 // (v_ldexp_f64) is right up to the overflow threshold ln(DBL_MAX) = 709.782712893384 and below -708 as well.  Callers whose argument
@@ -330,12 +330,9 @@ __device__ __forceinline__ double beat_sconst(double c) {
   return c;
 }
 
-#ifndef BEAT_FM_PIN
-#define BEAT_FM_PIN 1
-#endif
-// INT_SCALE (round 6, the TP06 step): exp() puts 2^m into the table value's exponent field by an integer add -- see exp() and
-// BEAT_EXP_LO / _HI_INT; the table then holds adjusted entries (beat_exp_tab_entry).  false: v_ldexp_f64, any argument down to -5.8e6
-// underflows to 0 (ToR-ORd, the generated models, the forward-Euler models).
+// INT_SCALE (no model uses it: see Tp06Grl1::FM): exp() puts 2^m into the table value's exponent field by an integer add -- see exp()
+// and BEAT_EXP_LO / _HI_INT; the table then holds adjusted entries (beat_exp_tab_entry).  false: v_ldexp_f64, any argument down to
+// -5.8e6 underflows to 0 (TP06, ToR-ORd, the generated models, the forward-Euler models).
 template <bool INT_SCALE_>
 struct FastMathT {
   static constexpr bool INT_SCALE = INT_SCALE_;
@@ -392,7 +389,7 @@ struct FastMathT {
 using FastMath = FastMathT<false>;
 template <bool I>
 __device__ __forceinline__ void beat_fm_pin(FastMathT<I>& fm) {
-#if defined(__AMDGCN__) && BEAT_FM_PIN
+#ifdef __AMDGCN__
   asm volatile("" : "+v"(fm.magic));
 #endif
 }
@@ -405,26 +402,17 @@ __device__ __forceinline__ void beat_fm_pin(FastMathT<I>& fm) {
 __device__ __forceinline__ double beat_guard(double v) { return fabs(v) < 1.0e-4 ? copysign(1.0e-4, v) : v; }
 
 // Access to the state-major array for one node (row k at base + k*ld).
-// Cache policy of the state rows' loads and stores (-DBEAT_ODE_NT: bit 0 non-temporal loads, bit 1 non-temporal stores; default
-// 0 = plain).  Round 5 measured it because the library's own streaming probe reaches its best in-place rate with both
-// (csrc/beat_probe.hip, profiles/r05_streaming.md: 6.5 against 6.0 TB/s for ONE stream per wave; 5.85 against 5.73 for 19 row
-// streams, the pattern of this kernel); the result for the kernels themselves is in profiles/r05_streaming.md.
-// Round 6: 3 is the default.  With one block per tile and four waves per SIMD (beat_ode.hip: ode_grid) the kernel behaves as the
-// probe does: TP06 512^3 in one process on the same memory 8.60 - 8.64 -> 8.41 ms (loads only: 8.55 - 8.57, stores only: no change),
-// the 512^3 step 12.68 / 13.12 -> 12.41 / 12.80 ms on the two levels consecutive processes alternate between
-// (profiles/r06_ode_addressing.md); ToR-ORd: 2.465 -> 2.44 ms at 256^3, its class kernel (plain accesses) unchanged.
-#ifndef BEAT_ODE_NT
-#define BEAT_ODE_NT 3
-#endif
+// The state rows are loaded and stored non-temporally: with one block per tile and four waves per SIMD, TP06 at 512^3 went from
+// 8.60 to 8.41 ms (profiles/r06_ode_addressing.md).  The host harnesses build this header with g++: plain accesses there.
 __device__ __forceinline__ double beat_row_load(const double* p) {
-#if (BEAT_ODE_NT & 1) && defined(__clang__)  // (the host harnesses build this header with g++: plain accesses there)
+#ifdef __clang__
   return __builtin_nontemporal_load(p);
 #else
   return *p;
 #endif
 }
 __device__ __forceinline__ void beat_row_store(double* p, double v) {
-#if (BEAT_ODE_NT & 2) && defined(__clang__)
+#ifdef __clang__
   __builtin_nontemporal_store(v, p);
 #else
   *p = v;
@@ -438,18 +426,12 @@ __device__ __forceinline__ void beat_row_store(double* p, double v) {
 // (v_lshl_add_u64 per row), kept from the row's load to its store: 38 of the TP06 step's 134 VGPRs, 90 of ToR-ORd's 227.
 // (the offset in BYTES, formed in 32-bit arithmetic: `base + zext(lane)` scales the 64-bit extension by 8, which the instruction
 // selector cannot prove to fit the 32-bit offset register)
-#ifndef BEAT_AT_OPAQUE
-#define BEAT_AT_OPAQUE 1
-#endif
-// base + k ld with the stride opaque per access (BEAT_ROW_OPAQUE): the row's base is then formed on the scalar unit where the access
+// base + k ld with the stride opaque per access: the row's base is then formed on the scalar unit where the access
 // is (s_mul + s_add, a handful of otherwise idle SALU cycles) instead of being kept in an SGPR pair from the row's load to its
 // store -- 19 (TP06) to 52 (ToR-ORd + Land) pairs of the ~100 SGPRs a wave has, spilled to VGPR lanes beyond that
-#ifndef BEAT_ROW_OPAQUE
-#define BEAT_ROW_OPAQUE 1
-#endif
 template <class T>
 __device__ __forceinline__ T* beat_row(T* base, int k, int64_t ld) {
-#if defined(__AMDGCN__) && BEAT_ROW_OPAQUE
+#ifdef __AMDGCN__
   asm volatile("" : "+s"(ld));
 #endif
   return base + (int64_t)k * ld;
@@ -457,7 +439,7 @@ __device__ __forceinline__ T* beat_row(T* base, int k, int64_t ld) {
 template <class T>
 __device__ __forceinline__ T* beat_at(T* uniform_base, unsigned& byte_off) {
   typedef typename std::conditional<std::is_const<T>::value, const char, char>::type Byte;
-#if defined(__AMDGCN__) && BEAT_AT_OPAQUE
+#ifdef __AMDGCN__
   // (the offset made opaque at every access, IN PLACE -- the caller's own variable, so that there is one value chain and no copy:
   // otherwise ONE 64-bit extension of the offset is formed at the top of the tile, outside the blocks of the accesses, and
   // instruction selection -- block by block -- no longer sees "uniform base + zext(32-bit offset)", the form that goes into the
@@ -527,27 +509,6 @@ struct RegIO {
   __device__ __forceinline__ double load(int k) const { return y[k]; }
   __device__ __forceinline__ void store(int k, double v) const { y[k] = v; }
 };
-
-// Parking a value in LDS across the part of a step that does not use it (an IO type that has somewhere to park it offers
-// stash / unstash: StashIO in beat_ode_kernel.h; every other IO type keeps the value where it is).  The TP06 step holds 19
-// loaded states, nine shared exponentials and five conductances while its twelve gate blocks run: at four waves per SIMD (128
-// VGPRs) the register allocator spilled 28 B per lane to scratch -- memory operations that also queue on the in-order vector-memory
-// counter behind the gate stores.  LDS reads and writes count on lgkmcnt and cost 64 B per node and value of LDS traffic.
-template <class IO, class = void>
-struct beat_has_stash : std::false_type {};
-template <class IO>
-struct beat_has_stash<IO, std::void_t<decltype(std::declval<const IO&>().stash(0, 0.0))>> : std::true_type {};
-template <class IO>
-__device__ __forceinline__ void beat_stash(const IO& io, int slot, double v) {
-  if constexpr (beat_has_stash<IO>::value) io.stash(slot, v);
-}
-template <class IO>
-__device__ __forceinline__ double beat_unstash(const IO& io, int slot, double kept) {
-  if constexpr (beat_has_stash<IO>::value)
-    return io.unstash(slot);
-  else
-    return kept;
-}
 
 // ------------------------------------------------------------------------------------------------
 // v' = -a s, s' = b v, forward Euler  (tests/test_odesolver.py:11-17)
@@ -646,7 +607,7 @@ struct FhnReadme {
 //    denominators that occur here, tests/test_device_math_gpu.py) instead of the ~12-instruction IEEE division sequence.
 //  * parameter-only sub-expressions are evaluated once per launch on the host (Derived).
 // ------------------------------------------------------------------------------------------------
-#if defined(__clang__) && !defined(BEAT_TP06_NO_CONTRACT)
+#ifdef __clang__
 #pragma clang fp contract(fast)  // a * b + c as one fma inside the step (the library as a whole is built with contraction off)
 #endif
 struct Tp06Grl1 {
@@ -656,20 +617,10 @@ struct Tp06Grl1 {
 #ifndef BEAT_TP06_WAVES
 #define BEAT_TP06_WAVES 4  // (round 6: 118 - 124 VGPRs in the uniform and the class kernels; the bound keeps it that way)
 #endif
-#ifndef BEAT_TP06_STASH
-#define BEAT_TP06_STASH 0
-#endif
   static constexpr int WAVES = BEAT_TP06_WAVES;
   static constexpr int WAVES_PER_NODE = BEAT_ODE_WAVES_PER_NODE;  // per-node parameter rows: NP more values per lane
-  static constexpr int STASH_SLOTS = BEAT_TP06_STASH;  // values parked in LDS while the gate blocks run (beat_stash)
-  // exp() with the factor 2^m added into the exponent field (FastMathT<true>: one instruction less per exp(), 51 per node; results in
-  // the normal range only, i.e. |V| < ~370 mV -- beyond it the Gaussian time constants' arguments leave [BEAT_EXP_LO, BEAT_EXP_HI_INT])
-  // Measured (profiles/r06_ode_addressing.md): 1778 -> 1729 static VALU instructions, 8.10 -> 8.00 ms in one process, 12.20 -> 12.165 ms per
-  // 512^3 step -- 0.3 %, for a step that would return garbage instead of NaN beyond its range: OFF.
-#ifndef BEAT_TP06_EXP_INT
-#define BEAT_TP06_EXP_INT 0
-#endif
-  using FM = FastMathT<BEAT_TP06_EXP_INT != 0>;
+  // (not FastMathT<true>: 0.3 % per 512^3 step for garbage instead of NaN beyond |V| ~ 370 mV, profiles/r06_ode_addressing.md)
+  using FM = FastMath;
   static constexpr bool FM_PIN = true;  // exp()'s rounding constant in a VGPR pair for the whole step (FastMath::magic): 118 -> 120 VGPRs, -18 VALU instructions
   enum S { Xr1, Xr2, Xs, m, h, j, d, f, f2, fCass, s, r, R_prime, Ca_i, Ca_SR, Ca_ss, Na_i, V, K_i };
   enum P {
@@ -745,21 +696,12 @@ struct Tp06Grl1 {
   __device__ static __forceinline__ double grl1(const FM& fm, double y, double fy, double J, double dt) {
     return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg<FM::INT_SCALE>(J * dt))) - 1.0) * rcp(J) : fy * dt);
   }
-  // same with 1/J supplied by the caller (batched); rJ is only used where |J| > 1e-8
-  __device__ static __forceinline__ double grl1r(const FM& fm, double y, double fy, double J, double rJ,
-                                                 double dt) {
-    return y + ((fabs(J) > 1e-8) ? fy * (beat_exp_overflow(J * dt, fm.exp(beat_clamp_exp_arg<FM::INT_SCALE>(J * dt))) - 1.0) * rJ : fy * dt);
-  }
-  __device__ static __forceinline__ double guard(double J) { return (fabs(J) > 1e-8) ? J : 1.0; }
   // The GRL1 increment f (exp(J dt) - 1) / J of a non-gate state as f dt phi(J dt), phi(z) = (exp(z) - 1) / z by its Taylor polynomial
   // of degree 8 when |J dt| <= 1/16 (first omitted term z^9 / 10! < 5e-18; phi(0) = 1 is the |J| <= 1e-8 limit of the scheme), the
   // scheme's literal expression otherwise -- the form the ToR-ORd kernel has had since round 3 (torord_dyncl.h: advance).  At dt = 0.01 -
   // 0.05 ms nearly every node is inside the window for its seven non-gate states (the potential during an upstroke is not): 13
   // instructions in place of exp() + reciprocal + selection (~26), and no cancellation in exp(z) - 1.  Round 6: the kernel is bound by
-  // fp64 issue once more (four waves per SIMD, 86 % VALU busy: profiles/r06_512.md).  BEAT_TP06_PHI=0: the literal expression always.
-#ifndef BEAT_TP06_PHI
-#define BEAT_TP06_PHI 1
-#endif
+  // fp64 issue once more (four waves per SIMD, 86 % VALU busy: profiles/r06_512.md).
   __device__ static __forceinline__ double phi_small(double z) {
     double ph = fma(z, beat_sconst(1.0 / 362880.0), beat_sconst(1.0 / 40320.0));
     ph = fma(z, ph, beat_sconst(1.0 / 5040.0));
@@ -772,13 +714,9 @@ struct Tp06Grl1 {
   }
   __device__ static __forceinline__ double advance(const FM& fm, double y, double fy, double J, double dt) {
     const double z = J * dt;
-    if (BEAT_TP06_PHI && fabs(z) <= 0.0625) return fma(fy * dt, phi_small(z), y);
+    if (fabs(z) <= 0.0625) return fma(fy * dt, phi_small(z), y);
     return grl1(fm, y, fy, J, dt);
   }
-  // gate with f = (inf - y)/tau, J = -1/tau
-#ifndef BEAT_TP06_GATE_PHI
-#define BEAT_TP06_GATE_PHI 0  // 1: 1 - exp(z), z = -dt/tau, as -z phi7(z) when |z| <= 1/32 (per lane); measured, see profiles/r06_ode_addressing.md
-#endif
   __device__ static __forceinline__ double phi7(double z) {  // (exp(z) - 1) / z, |z| <= 1/32: first omitted term z^8 / 9! < 3e-18
     double ph = fma(z, beat_sconst(1.0 / 40320.0), beat_sconst(1.0 / 5040.0));
     ph = fma(z, ph, beat_sconst(1.0 / 720.0));
@@ -788,11 +726,8 @@ struct Tp06Grl1 {
     ph = fma(z, ph, 0.5);
     return fma(z, ph, 1.0);
   }
+  // gate with f = (inf - y)/tau, J = -1/tau (exp() on every lane: -z phi7(z) for |z| <= 1/32 was slower, profiles/r06_ode_addressing.md)
   __device__ static __forceinline__ double gate(const FM& fm, double y, double inf, double rtau, double dt) {
-#if BEAT_TP06_GATE_PHI
-    const double z = -dt * rtau;
-    if (z >= -0.03125) return fma(inf - y, -z * phi7(z), y);
-#endif
     return y + (inf - y) * (1.0 - fm.exp(fmax(-dt * rtau, BEAT_EXP_LO)));  // (-dt / tau <= 0)
   }
 
@@ -800,14 +735,7 @@ struct Tp06Grl1 {
   // independent exp() chains; without fences everything is hoisted and one wave needs the whole
   // register file.  Each fenced block keeps a few chains in flight, which is all the latency hiding
   // 3-4 resident waves per SIMD need.
-#ifndef BEAT_TP06_FENCES
-#define BEAT_TP06_FENCES 1  // 0: none (experiments)
-#endif
-#if BEAT_TP06_FENCES
 #define BEAT_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define BEAT_FENCE()
-#endif
 
   template <class IO, class P>
   __device__ static __forceinline__ void step(const IO& io, const P& p, const Derived& q, const FM& fm,
@@ -848,15 +776,8 @@ struct Tp06Grl1 {
     // once per tile and wave) -- 12 more VGPRs through the gate section, which the three-wave budget has.  512^3, same
     // box, runs in pairs: 10.34-10.43 against 10.50-10.55 ms.  (Loading V after the gates, so that the two stores a
     // pending update makes at V's load precede no other load, added nothing to that: 10.34-10.39.)
-    const double vCai0 = io.load(Ca_i), vCaSR0 = io.load(Ca_SR), vCass0 = io.load(Ca_ss), vNai0 = io.load(Na_i),
-                 vKi0 = io.load(K_i), vR0 = io.load(R_prime);
-    // parked in LDS while the gate blocks run (see beat_stash): the ones needed last first
-    if (STASH_SLOTS >= 1) beat_stash(io, 0, vR0);
-    if (STASH_SLOTS >= 2) beat_stash(io, 1, vCaSR0);
-    if (STASH_SLOTS >= 3) beat_stash(io, 2, vKi0);
-    if (STASH_SLOTS >= 4) beat_stash(io, 3, vNai0);
-    if (STASH_SLOTS >= 5) beat_stash(io, 4, vCai0);
-    if (STASH_SLOTS >= 6) beat_stash(io, 5, vCass0);
+    const double vCai = io.load(Ca_i), vCaSR = io.load(Ca_SR), vCass = io.load(Ca_ss), vNai = io.load(Na_i),
+                 vKi = io.load(K_i), vR = io.load(R_prime);
 
     // ---- shared exponentials of V ----------------------------------------------------------------------
     const double E20 = fm.exp(0.05 * v), E7 = fm.exp(v * (1.0 / 7.0));
@@ -951,7 +872,6 @@ struct Tp06Grl1 {
     }
     BEAT_FENCE();
 
-    const double vCass = STASH_SLOTS >= 6 ? beat_unstash(io, 5, vCass0) : vCass0;
     {  // fCass (.ode:261-264): depends on Ca_ss only
       const double c2 = 1.0 + (vCass * 20.0) * (vCass * 20.0);                // 1 + (Ca_ss/0.05)^2
       double rc2, rt;
@@ -960,9 +880,6 @@ struct Tp06Grl1 {
     }
 
     // ---- reversal potentials ------------------------------------------------------------------------
-    const double vKi = STASH_SLOTS >= 3 ? beat_unstash(io, 2, vKi0) : vKi0;
-    const double vNai = STASH_SLOTS >= 4 ? beat_unstash(io, 3, vNai0) : vNai0;
-    const double vCai = STASH_SLOTS >= 5 ? beat_unstash(io, 4, vCai0) : vCai0;
     double rNai, rKi, rCai, rKs;
     rcp4(vNai, vKi, vCai, vKi + p[P_kna] * vNai, rNai, rKi, rCai, rKs);
     const double E_Na = q.RTF * fm.log(p[Na_o] * rNai);
@@ -1069,23 +986,13 @@ struct Tp06Grl1 {
       // dE_K/dK_i = -RTF/K_i, dE_Ks/dK_i = -RTF/(K_i + P_kna Na_i); currents depend on K_i only through them
       const double J_Ki = -(sum_du * q.RTF * rKi + gKs * q.RTF * rKs) * q.cVF;
       const double J_Nai = -((gNa + p[g_bna]) * q.RTF * rNai + 3.0 * di_NaK_dNai + 3.0 * di_NaCa_dNai) * q.cVF;
-#if BEAT_TP06_PHI
       io.store(V, advance(fm, v, -(I_tot + i_Stim), J_V, dt));
       io.store(K_i, advance(fm, vKi, -(I_K + i_Stim - 2.0 * i_NaK) * q.cVF, J_Ki, dt));
       io.store(Na_i, advance(fm, vNai, -(i_Na_tot + 3.0 * i_NaK + 3.0 * i_NaCa) * q.cVF, J_Nai, dt));
-#else
-      double rJV, rJK, rJN;
-      rcp3(guard(J_V), guard(J_Ki), guard(J_Nai), rJV, rJK, rJN);
-      io.store(V, grl1r(fm, v, -(I_tot + i_Stim), J_V, rJV, dt));
-      io.store(K_i, grl1r(fm, vKi, -(I_K + i_Stim - 2.0 * i_NaK) * q.cVF, J_Ki, rJK, dt));
-      io.store(Na_i, grl1r(fm, vNai, -(i_Na_tot + 3.0 * i_NaK + 3.0 * i_NaCa) * q.cVF, J_Nai, rJN, dt));
-#endif
     }
     BEAT_FENCE();
 
     // ---- calcium dynamics (.ode:298-316) -----------------------------------------------------------------------------
-    const double vR = STASH_SLOTS >= 1 ? beat_unstash(io, 0, vR0) : vR0;
-    const double vCaSR = STASH_SLOTS >= 2 ? beat_unstash(io, 1, vCaSR0) : vCaSR0;
     const double qup = q.Kup2 * rCai * rCai;
     double rup, rbc, rCaSR, rbsr, rbss;
     rcp3(1.0 + qup, vCai + p[K_buf_c], vCaSR, rup, rbc, rCaSR);
@@ -1133,6 +1040,6 @@ struct Tp06Grl1 {
   }
 #undef BEAT_FENCE
 };
-#if defined(__clang__) && !defined(BEAT_TP06_NO_CONTRACT)
+#ifdef __clang__
 #pragma clang fp contract(off)
 #endif

@@ -45,7 +45,7 @@
 #define BEAT_SCONST(c) beat_sconst(c)
 #endif
 
-#if defined(__clang__) && !defined(BEAT_TORORD_NO_CONTRACT)
+#ifdef __clang__
 #pragma clang fp contract(fast)
 #endif
 
@@ -440,9 +440,6 @@ struct TorordGrl1T {
   // the non-gate states, a reciprocal (7) and the |J| > 1e-8 selection (phi(0) = 1 is that limit).  It is also the more
   // accurate form: exp(z) - 1 loses log2(1/|z|) bits to cancellation.  The branch is per lane (a node's result does not
   // depend on which nodes share its wavefront); lanes outside the window take the general form below it.
-#ifndef BEAT_GRL1_PHI
-#define BEAT_GRL1_PHI 1  // 0: the general form for every lane (A/B builds)
-#endif
   static constexpr double PHI_WINDOW = 0.0625;
   // (BEAT_SCONST: the coefficient through a scalar register.  A 64-bit literal cannot be an operand; left alone the
   // compiler materialises each one in a VGPR pair -- two v_mov_b32 ahead of every fma of the Horner scheme, three VALU
@@ -457,11 +454,10 @@ struct TorordGrl1T {
     ph = fma(z, ph, 0.5);
     return fma(z, ph, 1.0);
   }
-  // gate with f = (inf - y) * rate, J = -rate  =>  y += (inf - y) (1 - exp(-dt rate))
+  // gate with f = (inf - y) * rate, J = -rate  =>  y += (inf - y) (1 - exp(-dt rate))  (phi_small here: measured, no gain)
   template <class FM>
   BEAT_DV static double gate(const FM& fm, double y, double inf, double rate, double dt) {
     const double z = -dt * rate;
-    if (BEAT_GRL1_PHI > 1 && fabs(z) <= PHI_WINDOW) return fma(inf - y, -z * phi_small(z), y);  // (measured: no gain for gates)
     return y + (inf - y) * (1.0 - fm.exp(fmax(z, -746.0)));  // rates reach 1e21/ms at +350 mV: see FastMath::exp
   }
   // The same update for a gate whose rate has an upper bound B known per parameter set (a time constant c + 1/s has the
@@ -488,7 +484,7 @@ struct TorordGrl1T {
   template <class FM>
   BEAT_DV static double advance(const FM& fm, double y, double f, double J, double dt) {
     const double z = J * dt;
-    if (BEAT_GRL1_PHI && fabs(z) <= PHI_WINDOW) return fma(f * dt, phi_small(z), y);
+    if (fabs(z) <= PHI_WINDOW) return fma(f * dt, phi_small(z), y);
     return grl1(y, f, J, fm.exp(fmin(fmax(z, -746.0), 710.0)) - 1.0, dt);
   }
 
@@ -514,7 +510,7 @@ struct TorordGrl1T {
     // Exponentials of the potential with slope 1/20, 1/10 and 1/5 mV (INa, Ito, ICaL, IKs: seven of them) are E20 = exp(v/20)
     // times or squared times a constant.
     const double E20 = fm.exp(0.05 * v), E10 = E20 * E20;
-    const bool small_g = BEAT_GRL1_PHI && dt * q.gate_bound <= GATE_WINDOW, small_i = BEAT_GRL1_PHI && dt * q.ito_bound <= GATE_WINDOW;
+    const bool small_g = dt * q.gate_bound <= GATE_WINDOW, small_i = dt * q.ito_bound <= GATE_WINDOW;
 
     // running sums: total current seen by the state and its derivative w.r.t. the state
     double Iv = 0.0, dIv = 0.0;
@@ -1252,7 +1248,7 @@ struct TorordGrl1T {
 using TorordDynClGrl1 = TorordGrl1T<false>;
 using TorordLandGrl1 = TorordGrl1T<true>;
 
-#if defined(__clang__) && !defined(BEAT_TORORD_NO_CONTRACT)
+#ifdef __clang__
 #pragma clang fp contract(off)
 #endif
 
