@@ -185,6 +185,39 @@ def test_state_array_keeps_the_best_of_three_placements(hip_ctx, monkeypatch):
     assert c.placement is not None and c.placement["rows_probed"] == 4 and len(c.placement["candidates"]) == 2
     d = StateArray(hip_ctx, 7, n + 1, 3)
     assert float(d.buf.abs().max()) == 0.0  # (placed or not: a usable array either way)
+    assert list(d.placement) == ["skipped"] and "16-byte" in d.placement["skipped"]
+
+
+def test_work_fields_keep_the_best_of_three_placements(hip_ctx, monkeypatch):
+    """The PCG's work fields (r, q, z, the ring) are placed by the state array's routine with the 4-row probe.  With the size
+    threshold lowered for the test: the record names three rates and the index of the largest, the buffer is zero-filled and of the
+    layout an unplaced one has, and a solve on it equals the solve on an unplaced buffer (BEAT_WORK_PLACE=1) bit for bit."""
+    from beat import _stencil
+    from beat._engine import DiffusionSolver, HipOps, Slab
+
+    nn = (64, 64, 64)
+    tabs = _stencil.stencil_tables(3, (0.1, 0.1, 0.1), 1e-3)
+    monkeypatch.setenv("BEAT_STATE_PLACE_MIN_BYTES", str(1 << 20))
+    placed = HipOps(hip_ctx, nn, True, True, *tabs)
+    rec = placed.work_placement
+    assert rec is not None and len(rec["candidates"]) == 3 and rec["rows_probed"] == 4
+    assert rec["chosen"] == int(np.argmax(rec["candidates"])) and min(rec["candidates"]) > 0.0
+    assert float(placed.work.abs().max()) == 0.0
+    monkeypatch.setenv("BEAT_WORK_PLACE", "1")
+    plain = HipOps(hip_ctx, nn, True, True, *tabs)
+    assert plain.work_placement is None and plain.work.numel() == placed.work.numel()
+    layout = lambda ops: [f.offset for f in (ops.r, ops.q, ops.z, *ops.ring)]  # noqa: E731
+    assert layout(plain) == layout(placed)
+    v = -85.0 + 30.0 * np.random.default_rng(5).random(placed.n)
+    outs = []
+    for ops in (placed, plain):
+        ops.set_timestep(0.01, 0.5, 0.05)
+        fv, fx = ops.new_field(), ops.new_field()
+        fv.set(v)
+        res = DiffusionSolver(ops, Slab(nn[2])).solve(fv, [], [], fx, rtol=1e-10, atol=1e-50, max_it=500)
+        assert res.converged_reason > 0
+        outs.append(fx.numpy())
+    np.testing.assert_array_equal(outs[0], outs[1])
 
 
 def test_tp06_many_steps_and_stimulus_window(hip_ctx):
