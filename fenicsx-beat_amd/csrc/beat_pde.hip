@@ -342,9 +342,38 @@ __device__ __forceinline__ void beat_pcg_begin(double* st, double rtol, double a
   st[STOP] = done ? 1.0 : 0.0;
   st[REASON] = done ? (rr <= tr ? 2.0 : 3.0) : 0.0;
 }
+// 3 = the predicted stop behind PDOT (beat_rr_pdot with a ring slot), with st[PQS..QQ] = p.q, r.q, q.q just summed (q = A p_i, r = r_i):
+//   r_{i+1} . r_{i+1} = RR - 2 alpha (r.q) + alpha^2 (q.q)   in exact arithmetic, alpha = RZ / PQ.
+// The prediction rho feeds no iterate: it only gates the stop.  E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds |rho - what the residual
+// update's reduction would compute| (c: beat_rr_predict_bound).  When rho + E settles the stopping test and its reason (and rho is
+// accurate enough for the recorded residual norm) the solve is latched exactly as the update, its count and the roll would have left
+// it -- same alpha bits in the ring slot, same ITERS, NUPD, STOP, REASON, RR = max(rho, 0) -- and the update's launches are the no-ops
+// latched launches are.  Otherwise nothing changes but PQ: the update and the roll run and decide, max_it included.
+__device__ __forceinline__ void beat_pcg_predict(double* st, double* alpha_slot, double c) {
+  st[PQ] = st[PQS];
+  const double alpha = st[RZ] / st[PQ];  // (the residual update's expression)
+  const double rr = st[RR], rq = st[RQ], qq = st[QQ];
+  const double rho = fma(alpha, fma(alpha, qq, -2.0 * rq), rr);
+  const double m = sqrt(rr) + fabs(alpha) * sqrt(qq);
+  const double e = c * m * m;
+  const double tr = st[RTOL] * st[RTOL] * st[BB];
+  // (a recorded norm within ~1e-6 of the explicit one: E <= 2^-20 rho; the comparisons are false for a NaN anywhere)
+  if (!(rho + e <= st[TOL2]) || !(e <= 0x1p-20 * rho)) return;
+  double reason;
+  if (rho + e <= tr) reason = 2.0;
+  else if (rho - e > tr) reason = 3.0;
+  else return;
+  *alpha_slot = alpha;
+  st[RR] = rho > 0.0 ? rho : 0.0;
+  st[ITERS] += 1.0;
+  st[NUPD] += 1.0;
+  st[REASON] = reason;
+  st[STOP] = 1.0;
+}
 __global__ __launch_bounds__(BEAT_BLOCK) void reduce_partials_kernel(const double* __restrict__ partials, int count, int nsum, double* out,
                                                                      const double* st, double* counter, int then, double* roll_st,
-                                                                     double rtol, double atol, double max_it) {
+                                                                     double rtol, double atol, double max_it, double* alpha_slot,
+                                                                     double bound_c) {
   __shared__ double red[4];
   if (st != nullptr && st[STOP] != 0.0) return;
   if (counter != nullptr && threadIdx.x == 0) counter[0] += 1.0;  // one more executed residual update
@@ -356,8 +385,14 @@ __global__ __launch_bounds__(BEAT_BLOCK) void reduce_partials_kernel(const doubl
   }
   if (then != 0 && threadIdx.x == 0) {  // (the thread that wrote the sums: its own stores are ahead of these loads)
     if (then == 1) beat_pcg_roll(roll_st);
+    else if (then == 3) beat_pcg_predict(roll_st, alpha_slot, bound_c);
     else beat_pcg_begin(roll_st, rtol, atol, max_it);
   }
+}
+
+__global__ void pcg_predict_kernel(double* st, double* alpha_slot, double c) {
+  if (st[STOP] != 0.0) return;
+  beat_pcg_predict(st, alpha_slot, c);
 }
 
 __global__ void pcg_begin_kernel(double* st, double rtol, double atol, double max_it) { beat_pcg_begin(st, rtol, atol, max_it); }
@@ -626,6 +661,7 @@ extern "C" int beat_pde_create(beat_ctx* ctx, const int64_t n[3], int z_lo_phys,
   p->n = n[0] * n[1] * n[2];
   const int64_t rows = (int64_t)g.ny * g.nz;
   p->vec_grid = (unsigned)std::min<int64_t>(2048, std::max<int64_t>(1, (rows + 3) / 4));
+  if (const char* e = std::getenv("BEAT_PCG_PREDICT_STOP")) p->predict_stop = e[0] != '0';  // (read per operator: A/B in one process)
   std::memcpy(p->h_mass, host_mass_tab, sizeof(p->h_mass));
   std::memcpy(p->h_stiff, host_stiff_tab, sizeof(p->h_stiff));
   BEAT_HIP_CHECK(hipSetDevice(ctx->device));
@@ -762,16 +798,17 @@ extern "C" int beat_pde_apply(beat_pde* pde, int which, const double* dev_x, dou
 }
 
 int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, double* counter, int then, double* roll_st,
-                           double rtol, double atol, int max_it) {
+                           double rtol, double atol, int max_it, double* alpha_slot, double bound_c) {
   static const bool fuse = [] {  // BEAT_PCG_FUSE=0: the scalar step in a launch of its own, as before round 5 (A/B runs)
     const char* e = std::getenv("BEAT_PCG_FUSE");
     return !(e && e[0] == '0');
   }();
   BEAT_KERNEL(reduce_partials_kernel, dim3(1), dim3(BEAT_BLOCK), 0, pde->ctx->stream, (const double*)pde->ctx->d_partials, count, nsum, out, st,
-              counter, fuse ? then : 0, roll_st, rtol, atol, (double)max_it);
+              counter, fuse ? then : 0, roll_st, rtol, atol, (double)max_it, alpha_slot, bound_c);
   BEAT_LAUNCH_CHECK();
   if (then != 0 && !fuse) {
     if (then == 1) BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st);
+    else if (then == 3) BEAT_KERNEL(pcg_predict_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st, alpha_slot, bound_c);
     else BEAT_KERNEL(pcg_begin_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st, rtol, atol, (double)max_it);
     BEAT_LAUNCH_CHECK();
   }
@@ -1284,9 +1321,11 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
     if (o.kind == 0) {
       // iteration i: p_i = D^-1 r + beta p_{i-1} and p_i . A p_i in one pass (ring slot i % PR), then r_new = r - alpha A p_i
       // with A p_i recomputed (written to the other of the two residual buffers: the kernel then needs no store-before-load
-      // ordering), then the scalar roll
+      // ordering), then the scalar roll.  The first pass may already settle the stop from a prediction of r_new . r_new: it then
+      // latches as the update, its count and the roll would have (iterations, update count, alpha of the slot), and the update's
+      // launches are latched no-ops -- the ring flush below and the host read the same counts either way
       double* rbuf[2] = {r, q};
-      if ((rc = beat_rr_pdot(pde, st, rbuf[i & 1], p_old, p_cur))) return rc;
+      if ((rc = beat_rr_pdot(pde, st, rbuf[i & 1], p_old, p_cur, slot))) return rc;
       if ((rc = beat_rr_rupd(pde, st, rbuf[i & 1], rbuf[(i + 1) & 1], p_cur, slot))) return rc;
       if (slot == PR - 1) {  // ring full: bring x up to date before slot 0 is overwritten
         if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR)))) return rc;

@@ -11,9 +11,10 @@
 namespace beat_pde_detail {
 
 // slots of the PCG scalar state `st` (device, caller-owned, >= 16 doubles)
-enum St { BB = 0, RZ, RR, PQ, RZN, RRN, TOL2, BETA, STOP, ITERS, REASON, RTOL, ATOL, MAXIT, NUPD, RR0, ALPHA };  // RR0: r.r of the initial guess
-// ALPHA: the step length of the single-reduction iteration (beat_rr_merged_next), device side only: the host reads the first
-// 16 entries.  The operator's own scalar state (beat_pde::d_st) has BEAT_ST_DOUBLES entries.
+enum St { BB = 0, RZ, RR, PQ, RZN, RRN, TOL2, BETA, STOP, ITERS, REASON, RTOL, ATOL, MAXIT, NUPD, RR0, ALPHA, PQS, RQ, QQ };  // RR0: r.r of the initial guess
+// ALPHA: the step length of the single-reduction iteration (beat_rr_merged_next); PQS, RQ, QQ: p.Ap, r.Ap and Ap.Ap of the pass that
+// predicts the stop (beat_rr_pdot with a ring slot; PQS is copied to PQ).  Device side only: the host reads the first 16 entries.
+// The operator's own scalar state (beat_pde::d_st) has BEAT_ST_DOUBLES entries.
 constexpr int BEAT_ST_DOUBLES = 32;
 constexpr int PRING = 6;  // search directions kept by the deferred-x PCG before x must be brought up to date (default ring)
 // Per-node-row operators on a single slab keep PRING_MAX directions (beat_pde::ring): their solves take 9 - 12 iterations at the
@@ -85,6 +86,10 @@ struct beat_pde {
   int last_rc = 0;
   int ring = beat_pde_detail::PRING;  // search directions kept before x is brought up to date (6; 12: per-node rows on a single slab)
   int last_base = 0;                  // first iteration of the ring cycle the last deferring solve left pending
+  // the register-row loop tests convergence from a prediction of r_{i+1} . r_{i+1} behind PDOT and skips the residual update when
+  // that settles it (beat_pcg_predict; BEAT_PCG_PREDICT_STOP=0 when the operator is created: the explicit test only)
+  bool predict_stop = true;
+  double predict_c = 0.0;  // its error-bound constant (beat_rr_predict_bound), computed on first use
   double* d_batch_st = nullptr;  // scalar states of the solves of a beat_split_steps batch (BEAT_MAX_BATCH x 16)
   // z node type of the ghost planes (the neighbouring slabs' boundary planes): 1 unless that plane is a face of the
   // whole grid (a neighbour that owns a single plane); set with beat_pde_set_ghost_types
@@ -157,8 +162,10 @@ inline int beat_pde_first_chunk(const beat_pde* pde) {
 
 // fixed-order sum of `count` block partials of `nsum` quantities into out[0..nsum) (beat_pde.hip)
 // then / roll_st / rtol / atol / max_it: the scalar step that follows the sums, in the same launch (1: the iteration's roll, 2: the start of a solve)
+// (3: the predicted stop behind PDOT, beat_pcg_predict: alpha_slot = the ring slot's step length, bound_c = beat_rr_predict_bound)
 int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, double* counter = nullptr, int then = 0,
-                           double* roll_st = nullptr, double rtol = 0.0, double atol = 0.0, int max_it = 0);
+                           double* roll_st = nullptr, double rtol = 0.0, double atol = 0.0, int max_it = 0, double* alpha_slot = nullptr,
+                           double bound_c = 0.0);
 
 // per-node-coefficient variants of the stage operations (beat_pde_var.hip); same contracts as the beat_pde_*
 // entry points that dispatch to them
@@ -239,9 +246,11 @@ int beat_small_solve(beat_pde* pde, const double* dev_v_prev, const double* cons
 bool beat_rr_available(const beat_pde* pde);
 int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
                 int n_stim, double* dev_x, double* dev_r, double* dev_st, int part = -1);  // part: as beat_var_rhs
-int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new);
+// slot >= 0: the single-slab loop's pass, which predicts the stop when the operator was created with it on (see beat_rr_pdot_part)
+int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, int slot = -1);
 int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,
-                      int part);
+                      int part, int slot = -1);
+double beat_rr_predict_bound(const beat_pde* pde);
 int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev_r_new, const double* dev_p, int slot,
                  bool roll = true);
 int beat_rr_next(beat_pde* pde, double* dev_st);

@@ -183,7 +183,11 @@ __device__ __forceinline__ int xcd_block(int b, int total) {
 // X / X2 / Y / Y2: the fields of RArgs::x, x2 (RHS with a guess: e), y, y2 as separate restrict-qualified kernel parameters -- the launch
 // passes distinct buffers (the residual update writes r out of place), and without the no-alias guarantee every
 // store would have to complete (s_waitcnt vmcnt(0)) before the next plane's loads may issue.
-template <int MODE, int RY, int PD, bool GUESS = false>
+// PRED (PDOT only, beat_rr_pdot with a ring slot): the pass also sums r . (A p) and (A p) . (A p), the two sums the prediction of the
+// next residual's r.r needs (beat_pcg_predict in beat_pde.hip); r of the owned rows is parked in LDS when its plane is staged and read
+// back row by row where it is used -- a wave-private slot per plane parity, no barrier, and its waits count on lgkmcnt, not on the
+// vmcnt of the plane in flight
+template <int MODE, int RY, int PD, bool GUESS = false, bool PRED = false>
 __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR_WAVES_RHS : ((MODE == RR_PDOT || MODE == RR_RUPD) && PD == 1 ? BEAT_RR_WAVES_IT : 1)) void rr_kernel(RGeom g, RArgs a, const double* __restrict__ X,
                                                         const double* __restrict__ X2, double* __restrict__ Y,
                                                         double* __restrict__ Y2) {
@@ -198,6 +202,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
   static_assert(!ALIGNED || BUF, "aligned segments come with the raw-buffer loads");
   constexpr int SEGW = ALIGNED ? 64 : SEG;
   static_assert(!GUESS || MODE == RR_RHS, "the initial guess enters the right-hand side only");
+  static_assert(!PRED || MODE == RR_PDOT, "the predicted-stop sums come with PDOT only");
   __shared__ double red[4];
   // boundary rows of the coefficient tables and 1/diag per node type, staged in LDS: the lanes on a face of the box
   // look them up every step, and a global load there would put a full vmcnt(0) drain -- outstanding stores and the
@@ -206,9 +211,12 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
   __shared__ double s_tab[27 * TABW];
   __shared__ double s_tab2[MODE == RR_RHS ? 27 * TABW : 1];
   __shared__ double s_taba[GUESS ? 27 * TABW : 1];
+  __shared__ double s_rc[PRED ? 4 * 2 * RY * 64 : 1];  // PRED: r of the owned rows, [wave][plane parity][row][lane]
+  __shared__ double s_acc[PRED ? 4 * 2 * 64 : 1];      // PRED: the lanes' two extra accumulators, [wave][sum][lane] (in registers: 173 VGPRs, 2 waves per SIMD)
   if (MODE != RR_RHS) {
     if (a.st[STOP] != 0.0) return;  // convergence latch (uniform over the grid)
   }
+  if (PRED) s_acc[(threadIdx.x >> 6) * 128 + (threadIdx.x & 63)] = s_acc[(threadIdx.x >> 6) * 128 + 64 + (threadIdx.x & 63)] = 0.0;
   for (int i = threadIdx.x; i < 27 * TABW; i += BEAT_BLOCK) {
     s_tab[i] = a.tab[i];
     if (MODE == RR_RHS) s_tab2[i] = a.tab2[i];
@@ -339,6 +347,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
           if (own_plane && r >= 1 && r <= RY && x_out && row_in[r])
             rr_store(&Y[(int64_t)k * g.plane + (int64_t)(y0 + r) * g.nx + gx], c);
         }
+        if (PRED && r >= 1 && r <= RY) s_rc[((((threadIdx.x >> 6) * 2 + (k & 1)) * RY) + r - 1) * 64 + lane] = ra[u][r];
       }
       if constexpr (ALIGNED) {  // the x-halo elements of plane k, formed like the rows (a lane that fetched nothing holds 0)
         double hc = rha[u];
@@ -528,6 +537,11 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
           }
           if (MODE == RR_PDOT) {
             acc0 = fma(v[0], s, acc0);  // p . (A p)
+            if (PRED) {                 // r . (A p), (A p) . (A p)
+              double* sa = &s_acc[(threadIdx.x >> 6) * 128 + lane];
+              sa[0] = fma(s_rc[((((threadIdx.x >> 6) * 2 + (z & 1)) * RY) + j) * 64 + lane], s, sa[0]);
+              sa[64] = fma(s, s, sa[64]);
+            }
           } else if (MODE == RR_UDOT) {  // u = D^-1 r:  u . (A u),  r . u,  r . r
             const double ri = Rw0[RAW ? j : 0];
             acc0 = fma(v[0], s, acc0);
@@ -573,7 +587,11 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
   }
   }
 
-  if (MODE == RR_PDOT) {
+  if (PRED) {
+    acc1 = s_acc[(threadIdx.x >> 6) * 128 + (threadIdx.x & 63)];
+    acc2 = s_acc[(threadIdx.x >> 6) * 128 + 64 + (threadIdx.x & 63)];
+  }
+  if (MODE == RR_PDOT && !PRED) {
     const double s0 = beat_block_sum(acc0, red);
     if (threadIdx.x == 0) a.partials[g.part_off + blockIdx.x] = s0;
   } else if (MODE == RR_RUPD) {
@@ -732,13 +750,13 @@ Coef interior_row(const double* tab) {
   return c;
 }
 
-template <int MODE, bool GUESS = false>
+template <int MODE, bool GUESS = false, bool PRED = false>
 void launch_rr(const beat_pde* pde, const RGeom& g, const RArgs& a) {
   if (g.total_blocks <= 0) return;
   const dim3 grid((unsigned)grid_blocks(g)), block(BEAT_BLOCK);  // xcd_block() deals whole runs to the 8 XCDs
   hipStream_t s = pde->ctx->stream;
 #define BEAT_RR_LAUNCH(RYV, PDV) \
-  BEAT_KERNEL((rr_kernel<MODE, RYV, PDV, GUESS>), grid, block, 0, s, g, a, a.x, GUESS ? a.e : a.x2, a.y, a.y2)
+  BEAT_KERNEL((rr_kernel<MODE, RYV, PDV, GUESS, PRED>), grid, block, 0, s, g, a, a.x, GUESS ? a.e : a.x2, a.y, a.y2)
   const int pd = rr_prefetch();
   if (g.ry == 2) {
     if (pd == 2) BEAT_RR_LAUNCH(2, 2); else if (pd == 3) BEAT_RR_LAUNCH(2, 3); else BEAT_RR_LAUNCH(2, 1);
@@ -835,13 +853,46 @@ int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* ho
   return beat_pde_launch_reduce(pde, off, 3, dev_st, nullptr);
 }
 
+// Bound constant of the predicted stop (beat_pcg_predict in beat_pde.hip): E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds
+// |rho - RR'|, rho = RR - 2 alpha RQ + alpha^2 QQ formed from the computed sums, RR' = what the residual update's reduction would
+// compute for r_{i+1}.  Every sum here is a chain of roundings: a lane's accumulator (acc = fma(x, y, acc): the product is exact, one
+// rounding per node it sums, zc planes x RY rows), the block tree (beat_block_sum: 6 shuffle levels + 2), the partials one thread of
+// the reduction adds in turn (ceil(count / 256)) and the block tree again -- depth D, error <= gamma_D sum |terms|, gamma_D = D u / (1 - D u),
+// u = 2^-53.  With sum r^2 <= RR, sum |r s| <= sqrt(RR QQ), sum s^2 <= QQ (Cauchy-Schwarz) and M = (sqrt(RR) + |alpha| sqrt(QQ))^2:
+//   RR, RQ, QQ as summed                                      gamma_D M    (RR: the right-hand side's or the last update's sum)
+//   rho's own two fma                                         2 u M
+//   r_{i+1} = fl(r - alpha s) per node, squared: (1 + d)^2    3 u M        (s = A p bit for bit as the update recomputes it)
+//   the update's own sum of r_{i+1}^2                         gamma_D (1 + u)^2 M
+// i.e. |rho - RR'| <= (2 D + 6) u M to first order; c = 4 (2 D + 8) u takes D over every geometry that sums a residual of this
+// operator (the right-hand side with and without a guess, PDOT, the update) and a factor 4 for the rest (gamma_D's denominator, the
+// square roots in M, RR and QQ being computed sums themselves).
+double beat_rr_predict_bound(const beat_pde* pde) {
+  const Geom& f = pde->g;
+  int depth = 0;
+  auto chain = [&](const RGeom& g) {
+    const int per_thread = (grid_blocks(g) + BEAT_BLOCK - 1) / BEAT_BLOCK;
+    depth = std::max(depth, g.zc * g.ry + 8 + per_thread + 8);
+  };
+  chain(make_geom(pde, 0, f.nz, 0, 0, RR_RHS));
+  chain(make_geom(pde, 0, f.nz, 0, 2, RR_RHS));
+  chain(make_geom(pde, 0, f.nz, 0, 4, RR_RHS));
+  chain(make_geom(pde, 0, f.nz, 0, 0, RR_PDOT));
+  chain(make_geom(pde, 0, f.nz, 0, 0, RR_RUPD));
+  return 4.0 * (2.0 * depth + 8.0) * std::ldexp(1.0, -53);
+}
+
 // p_new = D^-1 r + st[BETA] p_old (p_old unread while beta = 0), LOCAL p_new . A p_new -> dev_st[PQ].
 // In two parts on a decomposed grid (as beat_pde_spmv_dot_part): part 0 = the planes whose stencil needs no ghost
 // plane (enqueue it while the ghost planes of r travel), part 1 = the one or two slab-boundary planes -- which also
 // keep p_new on the ghost planes next to them -- and the reduction of all block partials.
+// slot >= 0 (the single-slab loop, operators created with the predicted stop on): the pass also sums r . A p and A p . A p
+// into dev_st[PQS..QQ], and the launch that reduces them predicts r_{i+1} . r_{i+1} -- when the prediction settles the stopping
+// test it latches the solve as the residual update of ring slot `slot` and the roll behind it would have (beat_pcg_predict)
 int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,
-                      int part) {
+                      int part, int slot) {
   const Geom& f = pde->g;
+  const bool pred = slot >= 0 && pde->predict_stop && f.z_lo_phys && f.z_hi_phys;
+  if (pred && pde->predict_c <= 0.0) pde->predict_c = beat_rr_predict_bound(pde);
   RArgs a{};
   a.x = dev_r;
   a.x2 = dev_p_old;
@@ -852,32 +903,43 @@ int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const 
   a.dinv_i = pde->h_dinv[13];
   a.partials = pde->ctx->d_partials;
   a.st = dev_st;
+  auto launch = [&](const RGeom& g) {
+    if (pred)
+      launch_rr<RR_PDOT, false, true>(pde, g, a);
+    else
+      launch_rr<RR_PDOT>(pde, g, a);
+  };
   const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
   const RGeom gi = make_geom(pde, lo, std::max(lo, hi), 0, 0, RR_PDOT);
   if (part == 0) {
-    launch_rr<RR_PDOT>(pde, gi, a);
+    launch(gi);
     BEAT_LAUNCH_CHECK();
     return BEAT_OK;
   }
   int off = gi.total_blocks > 0 ? grid_blocks(gi) : 0;
   if (!f.z_lo_phys) {
     const RGeom gb = make_geom(pde, 0, 1, off, 0, RR_PDOT);
-    launch_rr<RR_PDOT>(pde, gb, a);
+    launch(gb);
     off += grid_blocks(gb);
   }
   if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) {
     const RGeom gb = make_geom(pde, f.nz - 1, f.nz, off, 0, RR_PDOT);
-    launch_rr<RR_PDOT>(pde, gb, a);
+    launch(gb);
     off += grid_blocks(gb);
   }
   BEAT_LAUNCH_CHECK();
   BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
+  if (pred) {
+    static_assert(RQ == PQS + 1 && QQ == PQS + 2, "the three sums are reduced into one run of slots");
+    return beat_pde_launch_reduce(pde, off, 3, dev_st + PQS, dev_st, nullptr, 3, dev_st, 0.0, 0.0, 0, pde->d_alphas + slot,
+                                  pde->predict_c);
+  }
   return beat_pde_launch_reduce(pde, off, 1, dev_st + PQ, dev_st);
 }
 
-int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new) {
-  if (int rc = beat_rr_pdot_part(pde, dev_st, dev_r, dev_p_old, dev_p_new, 0)) return rc;
-  return beat_rr_pdot_part(pde, dev_st, dev_r, dev_p_old, dev_p_new, 1);
+int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, int slot) {
+  if (int rc = beat_rr_pdot_part(pde, dev_st, dev_r, dev_p_old, dev_p_new, 0, slot)) return rc;
+  return beat_rr_pdot_part(pde, dev_st, dev_r, dev_p_old, dev_p_new, 1, slot);
 }
 
 // alpha = st[RZ]/st[PQ] (kept for `slot`); r_new = r - alpha A p (out of place; ghost planes of p current); LOCAL
