@@ -176,7 +176,8 @@ class HipOps:
         # fields (profiles/r06_placement.md §4)
         self.work, self.work_placement = place_buffer(ctx, nfields * fld, offset=self.plane, n=self.n, rows=4, ld=fld,
                                                       tries=int(os.environ.get("BEAT_WORK_PLACE", "3")))
-        # same layout as beat_pde_solve: r, q, z, ring[...]; p is ring[0] for the in-place recurrences
+        # the work layout of the library's solves (beat_pcg_work in csrc/beat_pde_internal.h): r, q, z, ring[...], each field behind
+        # its lower ghost plane; p is ring[0] for the in-place recurrences
         self.fld = fld
         self.r = Field(ctx, self.n, self.plane, buf=self.work, offset=self.plane)
         self.q = Field(ctx, self.n, self.plane, buf=self.work, offset=self.plane + fld)
@@ -366,17 +367,9 @@ class HipOps:
         self.flush_pending()
         self.st_ptr_for_flush = None  # a pending update of this solve belongs to the handle's own scalar state
         ptrs, amps, k = self._stim_args(stim_w, stim_amp)
-        info = _hip.KspInfo()
-        pend = (C.c_int * 2)()
-        _hip.check(self.lib.beat_pde_solve_ex(self.handle, v_prev.ptr, ptrs, amps, k, x.ptr,
-                                              C.c_void_p(self.work.data_ptr()), rtol, atol, max_it, int(defer_flush),
-                                              C.byref(info), pend), allow_not_converged=True)
-        if pend[1] > 0 or self.lib.beat_pde_guess_pending(self.handle):  # (the guess increment alone may be due)
-            self.pending = (x, int(pend[0]), int(pend[1]))
-        res = KspResult(info.iterations, info.residual_norm, info.converged_reason, info.rhs_norm)
-        if self.ksp_log is not None:
-            self.ksp_log.append(res)
-        return res
+        return self._result(lambda info, pend: self.lib.beat_pde_solve_ex(
+            self.handle, v_prev.ptr, ptrs, amps, k, x.ptr, C.c_void_p(self.work.data_ptr()), rtol, atol, max_it, int(defer_flush),
+            info, pend), x)
 
     # -- the solve in two halves (beat_pde_solve_begin / _end): see include/beat_hip.h ------------------------------------
     def can_open(self) -> bool:
@@ -397,11 +390,19 @@ class HipOps:
                                                      rtol, atol, max_it))
         self.open_x = x
 
-    def _record(self, info) -> KspResult:
+    def _result(self, call, x, notify: bool = False) -> KspResult:
+        """One solve's record: ``call(info, pend)`` is the C call that fills it and the pair of what it leaves pending, which goes to
+        ``self.pending`` when ``x`` (the field solved for) is given.  A solve that did not converge is reported, not raised.
+        ``notify``: ``on_finish`` receives the record too."""
+        info = _hip.KspInfo()
+        pend = (C.c_int * 2)()
+        _hip.check(call(C.byref(info), pend), allow_not_converged=True)
+        if x is not None and (pend[1] > 0 or self.lib.beat_pde_guess_pending(self.handle)):  # (the guess increment alone may be due)
+            self.pending = (x, int(pend[0]), int(pend[1]))
         res = KspResult(info.iterations, info.residual_norm, info.converged_reason, info.rhs_norm)
         if self.ksp_log is not None:
             self.ksp_log.append(res)
-        if self.on_finish is not None:
+        if notify and self.on_finish is not None:
             self.on_finish(res)
         return res
 
@@ -411,22 +412,15 @@ class HipOps:
         if self.open_x is None:
             return None
         x, self.open_x = self.open_x, None
-        info = _hip.KspInfo()
-        pend = (C.c_int * 2)()
-        _hip.check(self.lib.beat_pde_solve_end(self.handle, C.byref(info), pend), allow_not_converged=True)
-        if pend[1] > 0 or self.lib.beat_pde_guess_pending(self.handle):
-            self.pending = (x, int(pend[0]), int(pend[1]))
-        return self._record(info)
+        return self._result(lambda info, pend: self.lib.beat_pde_solve_end(self.handle, info, pend), x, notify=True)
 
     def finished_behind(self):
         """The open solve was finished inside the ionic call that was enqueued behind it (beat_ode_step_* with pending = -1):
         collect its record; nothing is pending."""
         self.open_x = None
         self.pending = None
-        info = _hip.KspInfo()
-        pend = (C.c_int * 2)()
-        _hip.check(self.lib.beat_pde_solve_end(self.handle, C.byref(info), pend), allow_not_converged=True)  # (no solve open: the last record)
-        return self._record(info)
+        # (no solve open: the last record)
+        return self._result(lambda info, pend: self.lib.beat_pde_solve_end(self.handle, info, pend), None, notify=True)
 
     def solve_dist(self, comm: "LibComm", v_prev, stim_w, stim_amp, x, rtol, atol, max_it, defer_flush: bool = False) -> KspResult:
         """The slab-decomposed solve as ONE C call (beat_pde_solve_dist): halo exchange and all-reduces are issued
@@ -434,17 +428,9 @@ class HipOps:
         self.flush_pending()
         self.st_ptr_for_flush = None
         ptrs, amps, k = self._stim_args(stim_w, stim_amp)
-        info = _hip.KspInfo()
-        pend = (C.c_int * 2)()
-        _hip.check(self.lib.beat_pde_solve_dist(self.handle, comm.handle, v_prev.ptr, ptrs, amps, k, x.ptr,
-                                                C.c_void_p(self.work.data_ptr()), rtol, atol, max_it, int(defer_flush),
-                                                C.byref(info), pend), allow_not_converged=True)
-        if pend[1] > 0 or self.lib.beat_pde_guess_pending(self.handle):
-            self.pending = (x, int(pend[0]), int(pend[1]))
-        res = KspResult(info.iterations, info.residual_norm, info.converged_reason, info.rhs_norm)
-        if self.ksp_log is not None:
-            self.ksp_log.append(res)
-        return res
+        return self._result(lambda info, pend: self.lib.beat_pde_solve_dist(
+            self.handle, comm.handle, v_prev.ptr, ptrs, amps, k, x.ptr, C.c_void_p(self.work.data_ptr()), rtol, atol, max_it,
+            int(defer_flush), info, pend), x)
 
     def set_guess_order(self, order: int) -> None:
         """0: every solve starts from x0 = v_; m = 1..4: from v_ plus the degree-(m-1) extrapolation in time of the last

@@ -805,20 +805,20 @@ extern "C" int beat_comm_allreduce_sum(beat_comm* comm, double* dev_values, int 
   return allreduce_sum(comm, dev_values, count);
 }
 
-// ---- the decomposed solve in two halves (round 5: as beat_solve_begin / beat_solve_end of the single slab) ------------------------------
+// ---- the decomposed solve in two halves (round 5: its begin is here, its end is the single slab's beat_solve_end) ---------------------------
 // begin: ghost planes, right-hand side, the iterations the previous solve needed + 1 with their exchanges and all-reduces, and the
 // copy of the scalar state are in the streams when it returns; end: the host looks at the latch, enqueues more iterations if the
 // residual asks for them, and closes the solve.  Between the two a caller may enqueue the next ionic launch behind the solve
 // (beat_ode_step_pending with pending = -1): every rank sees the same all-reduced scalars, so every rank's launch does the same.
-namespace {
+
 // iterations [o.launched, o.launched + count) of the open decomposed solve
-int dist_enqueue_iterations(beat_pde* pde, int count) {
+int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
   beat_pde::OpenSolve& o = pde->open;
   beat_comm* comm = (beat_comm*)o.comm;
-  const int64_t n = pde->n, plane = pde->g.plane, fld = beat_pde_field_stride(pde);
-  double* r = o.work + plane;
-  double* q = r + fld;
-  double* ring = q + 2 * fld;  // [r, q, z, ring...]: z is unused by the Jacobi path
+  const int64_t n = pde->n, plane = pde->g.plane;
+  const PcgWork w = beat_pcg_work(pde, o.work);  // z is unused by the Jacobi path
+  const int64_t fld = w.fld;
+  double *r = w.r, *q = w.q, *ring = w.ring;
   const int PR = pde->ring;     // (6 on a decomposed grid; a one-rank communicator on a single slab of per-node rows: 12)
   double* st = pde->d_st;
   double* dev_x = o.x;
@@ -904,7 +904,14 @@ int dist_enqueue_iterations(beat_pde* pde, int count) {
   o.launched += count;
   return BEAT_OK;
 }
-}  // namespace
+
+int beat_dist_check(beat_pde* pde) { return ipc_check((beat_comm*)pde->open.comm); }
+
+int beat_dist_drain(beat_pde* pde) {
+  const beat_pde::OpenSolve& o = pde->open;
+  // the exchange started after the last residual update has no consumer: drain it before anything else touches those ghost planes
+  return o.rr || o.vpdot ? halo_wait((beat_comm*)o.comm) : BEAT_OK;
+}
 
 int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_prev, const double* const* host_dev_stim_w,
                           const double* host_stim_amp, int n_stim, double* dev_x, double* dev_work, double rtol, double atol, int max_it) {
@@ -917,14 +924,9 @@ int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_pr
   BEAT_REQUIRE(max_it >= 0, "max_it must be >= 0");
   BEAT_REQUIRE(!pde->open.on, "the previous solve has not been finished (beat_pde_solve_end)");
   beat_ctx* ctx = pde->ctx;
-  if (pde->h_st == nullptr) {
-    BEAT_HIP_CHECK(hipHostMalloc((void**)&pde->h_st, sizeof(double) * 16, hipHostMallocDefault));
-    BEAT_HIP_CHECK(hipEventCreateWithFlags(&pde->ev_st, hipEventDisableTiming));
-  }
-  const int64_t n = pde->n, plane = pde->g.plane, fld = beat_pde_field_stride(pde);
-  double* r = dev_work + plane;
-  double* q = r + fld;
-  double* ring = q + 2 * fld;  // [r, q, z, ring...]: z is unused by the Jacobi path
+  const int64_t n = pde->n, plane = pde->g.plane;
+  const PcgWork w = beat_pcg_work(pde, dev_work);
+  double *r = w.r, *q = w.q, *ring = w.ring;
   double* st = pde->d_st;
   double* h = ctx->h_pinned;
   int rc;
@@ -1004,88 +1006,16 @@ int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_pr
   if (vpdot) {
     if ((rc = halo_start(comm, r, n, plane))) return rc;  // ghost planes of r_0
   }
-  beat_pde::OpenSolve& o = pde->open;
-  o = beat_pde::OpenSolve{};
+  beat_pde::OpenSolve o{};
+  o.kind = SOLVE_DIST;
   o.comm = comm;
   o.rr = rr;
   o.merged = merged;
   o.vpdot = vpdot;
-  o.v_prev = dev_v_prev;
   o.x = dev_x;
   o.work = dev_work;
-  o.rtol = rtol;
-  o.atol = atol;
   o.max_it = max_it;
-  o.limit = max_it + (merged ? 1 : 0);
-  const int chunk = std::min(beat_pde_first_chunk(pde) + (merged ? 1 : 0), o.limit);
-  if ((rc = dist_enqueue_iterations(pde, chunk))) return rc;
-  BEAT_HIP_CHECK(hipMemcpyAsync(pde->h_st, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-  BEAT_HIP_CHECK(hipEventRecord(pde->ev_st, ctx->stream));
-  o.on = true;
-  return BEAT_OK;
-}
-
-int beat_dist_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* host_pending, bool* needed_more) {
-  beat_pde::OpenSolve& o = pde->open;
-  beat_comm* comm = (beat_comm*)o.comm;
-  beat_ctx* ctx = pde->ctx;
-  double* h = pde->h_st;
-  double* st = pde->d_st;
-  const int64_t fld = beat_pde_field_stride(pde);
-  double* ring = o.work + pde->g.plane + 3 * fld;
-  const int PR = pde->ring;
-  int rc;
-  BEAT_HIP_CHECK(hipEventSynchronize(pde->ev_st));
-  if ((rc = ipc_check(comm))) {
-    o.on = false;
-    return rc;
-  }
-  if (needed_more && h[STOP] == 0.0) *needed_more = true;  // unlatched at the first look: the launch behind the solve did nothing (beat_solve_end)
-  while (!(h[STOP] != 0.0 || o.launched >= o.limit)) {
-    if ((rc = dist_enqueue_iterations(pde, std::min(2, o.limit - o.launched)))) {
-      o.on = false;
-      return rc;
-    }
-    BEAT_HIP_CHECK(hipMemcpyAsync(h, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if ((rc = ipc_check(comm))) {
-      o.on = false;
-      return rc;
-    }
-  }
-  o.on = false;
-  pde->applied_behind = false;
-  if (o.rr || o.vpdot) {  // the exchange started after the last residual update has no consumer: drain it before anything else
-    if ((rc = halo_wait(comm))) return rc;  // touches those ghost planes
-  }
-  const int nupd = (int)h[NUPD], base = (nupd / PR) * PR;
-  const GuessTerms last = beat_guess_terms(pde, base);
-  beat_guess_observe(pde, (int)h[ITERS]);
-  if (beat_guess_end(pde, nupd, defer_flush != 0)) {  // the last partial ring cycle and / or the guess increment
-    if (defer_flush) {
-      host_pending[0] = base;
-      host_pending[1] = nupd % PR;
-      pde->last_base = base;
-    } else if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, base, 0, last))) {
-      return rc;
-    }
-  }
-  const int iters = (int)h[ITERS];
-  pde->last_iters = iters;
-  int reason = (int)h[REASON];
-  if (h[STOP] == 0.0) reason = -3;
-  pde->last_info.iterations = iters;
-  pde->last_info.converged_reason = reason;
-  pde->last_info.residual_norm = std::sqrt(h[RR]);
-  pde->last_info.rhs_norm = std::sqrt(h[BB]);
-  if (info) *info = pde->last_info;
-  pde->last_rc = BEAT_OK;
-  if (reason < 0) {
-    beat_set_error("PCG did not converge in %d iterations (||r|| = %.3e, ||b|| = %.3e)", iters, std::sqrt(h[RR]),
-                   std::sqrt(h[BB]));
-    pde->last_rc = BEAT_ENOTCONV;
-  }
-  return pde->last_rc;
+  return beat_solve_open(pde, o);
 }
 
 extern "C" int beat_pde_solve_dist_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_prev, const double* const* host_dev_stim_w,
@@ -1101,5 +1031,5 @@ extern "C" int beat_pde_solve_dist(beat_pde* pde, beat_comm* comm, const double*
   BEAT_REQUIRE(!defer_flush || host_pending != nullptr, "defer_flush needs host_pending[2]");
   if (host_pending) host_pending[0] = host_pending[1] = 0;
   if (int rc = beat_dist_solve_begin(pde, comm, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, dev_work, rtol, atol, max_it)) return rc;
-  return beat_dist_solve_end(pde, defer_flush, info, host_pending, nullptr);
+  return beat_solve_end(pde, defer_flush, info, host_pending, nullptr);
 }

@@ -474,9 +474,8 @@ extern "C" int beat_split_steps_big(beat_ctx* ctx, int model_id, double* dev_sta
   host_pending[1] = pending_in;
   host_pending[2] = 0;
   if (n_steps == 0) return BEAT_OK;
-  const int64_t fld = beat_pde_field_stride(pde);
   double* v_row = dev_states + (int64_t)v_index * ld;
-  const double* ring0 = dev_work + pde->g.plane + 3 * fld;  // [r, q, z, ring...], each field behind its lower ghost plane
+  const PcgWork w = beat_pcg_work(pde, dev_work);
   // (timing events of the ionic launches: destroyed on every way out of this function)
   struct Events {
     std::vector<hipEvent_t> ev;
@@ -498,7 +497,7 @@ extern "C" int beat_split_steps_big(beat_ctx* ctx, int model_id, double* dev_sta
   for (int s = 0; s < n_steps && rc == BEAT_OK; ++s) {
     if (host_ode_ms) BEAT_HIP_CHECK(hipEventRecord(ev[(size_t)2 * s], ctx->stream));
     rc = beat_ode_step_pending(ctx, model_id, dev_states, n, ld, host_params, num_params, nullptr, 0, host_t0[s], host_dt[s], v_index, nullptr,
-                               pde, ring0, fld, count);
+                               pde, w.ring, w.fld, count);
     if (host_ode_ms) BEAT_HIP_CHECK(hipEventRecord(ev[(size_t)2 * s + 1], ctx->stream));
     if (rc) break;
     beat_ksp_info info{};
@@ -563,19 +562,9 @@ extern "C" int beat_split_steps(beat_ctx* ctx, int model_id, double* dev_states,
   BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   int worst = BEAT_OK;
   for (int s = 0; s < n_steps; ++s) {
-    const double* hs = h.data() + 16 * s;
-    const int reason = (int)hs[beat_pde_detail::REASON];
-    if (host_info) {
-      host_info[s].iterations = (int)hs[beat_pde_detail::ITERS];
-      host_info[s].converged_reason = reason;
-      host_info[s].residual_norm = std::sqrt(hs[beat_pde_detail::RR]);
-      host_info[s].rhs_norm = std::sqrt(hs[beat_pde_detail::BB]);
-    }
-    if (reason < 0 && worst == BEAT_OK) {
-      beat_set_error("PCG did not converge in step %d of the batch (%d iterations, ||r|| = %.3e, ||b|| = %.3e)", s,
-                     (int)hs[beat_pde_detail::ITERS], std::sqrt(hs[beat_pde_detail::RR]), std::sqrt(hs[beat_pde_detail::BB]));
-      worst = BEAT_ENOTCONV;
-    }
+    const beat_ksp_info k = beat_pcg_info(h.data() + 16 * s);
+    if (host_info) host_info[s] = k;
+    if (worst == BEAT_OK) worst = beat_pcg_check(k, s);
   }
   pde->last_iters = (int)h[(size_t)16 * (n_steps - 1) + beat_pde_detail::ITERS];
   if (pde->guess_order < 0 && n_steps >= 4) {

@@ -1307,10 +1307,10 @@ bool beat_solve_lazy_available(const beat_pde* pde) {
 // `count` more iterations of the open solve, enqueued
 static int solve_enqueue_iterations(beat_pde* pde, int count) {
   beat_pde::OpenSolve& o = pde->open;
-  const int64_t fld = beat_pde_field_stride(pde);
-  double* r = o.work + pde->g.plane;
-  double* q = r + fld;
-  double* ring = q + 2 * fld;
+  if (o.kind == SOLVE_DIST) return beat_dist_enqueue_iterations(pde, count);
+  const PcgWork w = beat_pcg_work(pde, o.work);
+  const int64_t fld = w.fld;
+  double *r = w.r, *q = w.q, *ring = w.ring;
   double* st = pde->d_st;
   const int PR = pde->ring;
   int rc;
@@ -1318,7 +1318,14 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
     const int i = o.launched + it, slot = i % PR;
     double* p_cur = ring + (int64_t)slot * fld;
     const double* p_old = ring + (int64_t)((i + PR - 1) % PR) * fld;
-    if (o.kind == 0) {
+    if (o.kind == SOLVE_POLY) {
+      // polynomial preconditioner: classic in-place recurrences with p = ring[0]
+      if ((rc = beat_pde_spmv_dot(pde, ring, q, st))) return rc;
+      if ((rc = beat_pde_cg_update(pde, st, o.x, r, ring, q))) return rc;
+      for (int j = 0; j < pde->pc_ncoef - 1; ++j)
+        if ((rc = beat_pde_pc_pass(pde, j, r, w.z, q, st, st + RZN))) return rc;
+      if ((rc = beat_pde_cg_next_z(pde, st, w.z, ring))) return rc;
+    } else if (o.kind == SOLVE_RR) {
       // iteration i: p_i = D^-1 r + beta p_{i-1} and p_i . A p_i in one pass (ring slot i % PR), then r_new = r - alpha A p_i
       // with A p_i recomputed (written to the other of the two residual buffers: the kernel then needs no store-before-load
       // ordering), then the scalar roll.  The first pass may already settle the stop from a prediction of r_new . r_new: it then
@@ -1331,8 +1338,9 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
         if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR)))) return rc;
       }
     } else {
-      // per-node rows (round 4): the tile kernel forms p_i = D^-1 r + beta p_{i-1} while loading, stores it and q = A p_i in the
-      // same pass (beat_vtl_pdot); same expressions, same bits as the three-kernel iteration (BEAT_VTL_PDOT=0)
+      // per-node rows (round 4) or the LDS-tiled constant-coefficient kernels, deferred x: iteration i uses p_i = ring[i % PR].  With
+      // o.pdot (per-node rows) the tile kernel forms p_i = D^-1 r + beta p_{i-1} while loading, stores it and q = A p_i in the same
+      // pass (beat_vtl_pdot); same expressions, same bits as the three-kernel iteration (BEAT_VTL_PDOT=0)
       double* p_next = ring + (int64_t)((i + 1) % PR) * fld;
       if (o.pdot) {
         if ((rc = beat_vtl_pdot(pde, st, r, p_old, p_cur, q, i == 0))) return rc;
@@ -1342,7 +1350,7 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
       // (with the fused pass the scalar roll -- beta for the next pass, the latch, the iteration count -- runs in the launch that sums
       // the residual update's partials; the x update, when the ring is full, reads the update count only and may follow it)
       if ((rc = o.pdot ? beat_var_update_r(pde, st, r, q, slot, true) : beat_pde_cg_update_r(pde, st, r, q, slot))) return rc;
-      if (slot == PR - 1) {
+      if (slot == PR - 1) {  // ring full: bring x up to date before slot 0 is overwritten
         if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR)))) return rc;
       }
       if (!o.pdot && (rc = beat_pde_cg_next_oop(pde, st, r, p_cur, p_next))) return rc;
@@ -1352,54 +1360,122 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
   return BEAT_OK;
 }
 
-int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp, int n_stim,
-                     double* dev_x, double* dev_work, double rtol, double atol, int max_it) {
-  BEAT_REQUIRE(pde != nullptr && dev_work != nullptr && dev_v_prev && dev_x, "null argument");
-  BEAT_REQUIRE(beat_solve_lazy_available(pde), "this operator's solves are not of the kind that can be left open");
-  BEAT_REQUIRE(!pde->open.on, "the previous solve has not been finished (beat_pde_solve_end)");
-  BEAT_REQUIRE(max_it >= 0, "max_it must be >= 0");
-  BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
-  BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
-  BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
+int beat_solve_open(beat_pde* pde, beat_pde::OpenSolve o) {
   beat_ctx* ctx = pde->ctx;
   if (pde->h_st == nullptr) {
     BEAT_HIP_CHECK(hipHostMalloc((void**)&pde->h_st, sizeof(double) * 16, hipHostMallocDefault));
     BEAT_HIP_CHECK(hipEventCreateWithFlags(&pde->ev_st, hipEventDisableTiming));
   }
-  beat_pde::OpenSolve& o = pde->open;
-  o = beat_pde::OpenSolve{};
-  o.kind = beat_rr_available(pde) ? 0 : 1;
-  o.pdot = o.kind == 1 && beat_vtl_pdot_available(pde);
-  o.v_prev = dev_v_prev;
+  o.limit = o.max_it + (o.merged ? 1 : 0);
+  pde->open = o;
+  if (int rc = solve_enqueue_iterations(pde, std::min(beat_pde_first_chunk(pde) + (o.merged ? 1 : 0), o.limit))) return rc;
+  BEAT_HIP_CHECK(hipMemcpyAsync(pde->h_st, pde->d_st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
+  BEAT_HIP_CHECK(hipEventRecord(pde->ev_st, ctx->stream));
+  pde->open.on = true;
+  return BEAT_OK;
+}
+
+// A single-slab solve of any multi-launch kind, enqueued up to the host's first look
+static int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
+                            int n_stim, double* dev_x, double* dev_work, double rtol, double atol, int max_it) {
+  BEAT_REQUIRE(pde != nullptr && dev_work != nullptr && dev_v_prev && dev_x, "null argument");
+  BEAT_REQUIRE(!pde->open.on, "the previous solve has not been finished (beat_pde_solve_end)");
+  BEAT_REQUIRE(max_it >= 0, "max_it must be >= 0");
+  BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
+  BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
+  BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
+  beat_pde::OpenSolve o{};
+  o.kind = pde->pc_ncoef > 1 ? SOLVE_POLY : beat_rr_available(pde) ? SOLVE_RR : pde->var ? SOLVE_ROWS : SOLVE_TILED;
+  o.pdot = o.kind == SOLVE_ROWS && beat_vtl_pdot_available(pde);
   o.x = dev_x;
   o.work = dev_work;
-  o.rtol = rtol;
-  o.atol = atol;
   o.max_it = max_it;
-  const int64_t fld = beat_pde_field_stride(pde);
-  double* r = dev_work + pde->g.plane;
-  double* q = r + fld;
-  double* ring = q + 2 * fld;
+  const PcgWork w = beat_pcg_work(pde, dev_work);
   double* st = pde->d_st;
   int rc;
+  if (o.kind == SOLVE_TILED || o.kind == SOLVE_POLY) {
+    // the stage kernels' right-hand side, which starts from x0 = v_ (beat_guess_skip), and the start of the solve
+    if ((rc = beat_pde_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, st))) return rc;
+    if ((rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;
+    if (o.kind == SOLVE_POLY) {  // z = M^-1 r, p = z
+      for (int j = 0; j < pde->pc_ncoef - 1; ++j)
+        if ((rc = beat_pde_pc_pass(pde, j, w.r, w.z, w.q, st, st + RZ))) return rc;
+      if ((rc = beat_pde_cg_first_z(pde, st, w.z, w.ring))) return rc;
+    }
+    return beat_solve_open(pde, o);
+  }
   beat_guess_begin(pde);
   pde->fuse_begin = beat_pde::FuseBegin{true, false, rtol, atol, max_it};
-  if (o.kind == 0) {
-    rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st);
+  if (o.kind == SOLVE_RR) {
+    rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, st);
   } else if (beat_vtl_rhs_available(pde)) {  // two tile passes (b = B v_ + dt stim, r = b - A (v_ + e)); q is free until iteration 0
-    rc = beat_vtl_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, q, st, pde->guess.use_e ? pde->guess.e : nullptr);
+    rc = beat_vtl_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, w.q, st,
+                      pde->guess.use_e ? pde->guess.e : nullptr);
   } else {  // the gather kernel: the guess increment e next to v_
-    rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, pde->guess.use_e ? pde->guess.e : nullptr);
+    rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, st, pde->guess.use_e ? pde->guess.e : nullptr);
   }
   const bool begun = pde->fuse_begin.done;  // (the right-hand side's reduction has run the start of the solve in its own launch)
   pde->fuse_begin.on = false;
   if (rc) return rc;
   if (!begun && (rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;
-  if ((rc = solve_enqueue_iterations(pde, std::min(beat_pde_first_chunk(pde), max_it)))) return rc;
-  BEAT_HIP_CHECK(hipMemcpyAsync(pde->h_st, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-  BEAT_HIP_CHECK(hipEventRecord(pde->ev_st, ctx->stream));
-  o.on = true;
+  return beat_solve_open(pde, o);
+}
+
+// The host's first look at the open solve, then two more iterations at a time until the latch or the limit
+static int poll_until_latched(beat_pde* pde, bool* needed_more) {
+  beat_pde::OpenSolve& o = pde->open;
+  const double* h = pde->h_st;
+  const bool dist = o.kind == SOLVE_DIST;
+  int rc;
+  BEAT_HIP_CHECK(hipEventSynchronize(pde->ev_st));
+  if (dist && (rc = beat_dist_check(pde))) return rc;
+  // (a launch enqueued behind this solve saw the state the host sees at this first look: unlatched, it did nothing -- also when no
+  // further iteration may be enqueued (max_it = 0: pcg_begin does not latch and the loop below is skipped))
+  if (needed_more && h[STOP] == 0.0) *needed_more = true;
+  while (!(h[STOP] != 0.0 || o.launched >= o.limit)) {
+    if ((rc = solve_enqueue_iterations(pde, std::min(2, o.limit - o.launched)))) return rc;
+    BEAT_HIP_CHECK(hipMemcpyAsync(pde->h_st, pde->d_st, sizeof(double) * 16, hipMemcpyDeviceToHost, pde->ctx->stream));
+    BEAT_HIP_CHECK(hipStreamSynchronize(pde->ctx->stream));
+    if (dist && (rc = beat_dist_check(pde))) return rc;
+  }
   return BEAT_OK;
+}
+
+// The end of a deferred-x solve with scalar state h: the directions of its last, partially filled ring cycle and / or the guess
+// increment, added to x (stream-ordered before anything that reads x) or, with defer_flush, left to the caller in host_pending
+// (beat_ode_step_pending / beat_pde_x_flush)
+static int finish_ring_cycle(beat_pde* pde, const double* h, int defer_flush, int* host_pending) {
+  const int PR = pde->ring;
+  const int nupd = (int)h[NUPD], base = (nupd / PR) * PR;
+  const GuessTerms last = beat_guess_terms(pde, base);
+  beat_guess_observe(pde, (int)h[ITERS]);
+  if (!beat_guess_end(pde, nupd, defer_flush != 0)) return BEAT_OK;
+  if (defer_flush) {
+    host_pending[0] = pde->last_base = base;
+    host_pending[1] = nupd % PR;
+    return BEAT_OK;
+  }
+  const PcgWork w = beat_pcg_work(pde, pde->open.work);
+  return beat_pde_x_flush_terms(pde, pde->d_st, pde->open.x, w.ring, w.fld, base, 0, last);
+}
+
+beat_ksp_info beat_pcg_info(const double* h) {
+  beat_ksp_info k{};
+  k.iterations = (int)h[ITERS];
+  k.converged_reason = (int)h[REASON];
+  k.residual_norm = std::sqrt(h[RR]);
+  k.rhs_norm = std::sqrt(h[BB]);
+  return k;
+}
+
+int beat_pcg_check(const beat_ksp_info& k, int batch_step) {
+  if (k.converged_reason >= 0) return BEAT_OK;
+  if (batch_step >= 0)
+    beat_set_error("PCG did not converge in step %d of the batch (%d iterations, ||r|| = %.3e, ||b|| = %.3e)", batch_step, k.iterations,
+                   k.residual_norm, k.rhs_norm);
+  else
+    beat_set_error("PCG did not converge in %d iterations (||r|| = %.3e, ||b|| = %.3e)", k.iterations, k.residual_norm, k.rhs_norm);
+  return BEAT_ENOTCONV;
 }
 
 int beat_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* host_pending, bool* needed_more) {
@@ -1411,61 +1487,27 @@ int beat_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* hos
     return pde->last_rc;
   }
   BEAT_REQUIRE(!defer_flush || host_pending != nullptr, "defer_flush needs host_pending[2]");
-  if (pde->open.comm != nullptr) return beat_dist_solve_end(pde, defer_flush, info, host_pending, needed_more);  // a decomposed solve
   beat_pde::OpenSolve& o = pde->open;
-  beat_ctx* ctx = pde->ctx;
-  double* h = pde->h_st;
-  double* st = pde->d_st;
-  const int64_t fld = beat_pde_field_stride(pde);
-  double* ring = o.work + pde->g.plane + 3 * fld;
-  const int PR = pde->ring;
-  int rc;
-  BEAT_HIP_CHECK(hipEventSynchronize(pde->ev_st));
-  // (a launch enqueued behind this solve saw the state the host sees at this first look: unlatched, it did nothing -- also when no
-  // further iteration may be enqueued (max_it = 0: pcg_begin does not latch and the loop below is skipped))
-  if (needed_more && h[STOP] == 0.0) *needed_more = true;
-  while (!(h[STOP] != 0.0 || o.launched >= o.max_it)) {
-    if ((rc = solve_enqueue_iterations(pde, std::min(2, o.max_it - o.launched)))) {
-      o.on = false;
-      return rc;
-    }
-    BEAT_HIP_CHECK(hipMemcpyAsync(h, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  }
+  int rc = poll_until_latched(pde, needed_more);
   o.on = false;
+  if (rc) return rc;
   pde->applied_behind = false;  // (step_behind_open_solve sets it again when its launch has applied this solve's update)
-  // directions of the last, partially filled ring cycle (stream-ordered before anything that reads x) and / or the guess increment
-  const int nupd = (int)h[NUPD], base = (nupd / PR) * PR;
-  const GuessTerms last = beat_guess_terms(pde, base);
-  beat_guess_observe(pde, (int)h[ITERS]);
-  if (beat_guess_end(pde, nupd, defer_flush != 0)) {
-    if (defer_flush) {  // the caller adds these directions itself (beat_ode_step_pending / beat_pde_x_flush)
-      host_pending[0] = pde->last_base = base;
-      host_pending[1] = nupd % PR;
-    } else if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, base, 0, last))) {
-      return rc;
-    }
-  }
-  const int iters = (int)h[ITERS];
-  pde->last_iters = iters;
-  int reason = (int)h[REASON];
-  if (h[STOP] == 0.0) reason = -3;  // max_it == launched without the latch (max_it = 0)
-  pde->last_info.iterations = iters;
-  pde->last_info.converged_reason = reason;
-  pde->last_info.residual_norm = std::sqrt(h[RR]);
-  pde->last_info.rhs_norm = std::sqrt(h[BB]);
-  if (info) *info = pde->last_info;
-  pde->last_rc = BEAT_OK;
-  if (reason < 0) {
-    beat_set_error("PCG did not converge in %d iterations (||r|| = %.3e, ||b|| = %.3e)", iters, std::sqrt(h[RR]), std::sqrt(h[BB]));
-    pde->last_rc = BEAT_ENOTCONV;
-  }
-  return pde->last_rc;
+  if (o.kind == SOLVE_DIST && (rc = beat_dist_drain(pde))) return rc;
+  const double* h = pde->h_st;
+  if (o.kind != SOLVE_POLY && (rc = finish_ring_cycle(pde, h, defer_flush, host_pending))) return rc;  // (POLY: x is up to date)
+  beat_ksp_info k = beat_pcg_info(h);
+  if (h[STOP] == 0.0) k.converged_reason = -3;  // the limit reached without the latch (max_it = 0)
+  pde->last_iters = k.iterations;
+  pde->last_info = k;
+  if (info) *info = k;
+  return pde->last_rc = beat_pcg_check(k);
 }
 
 extern "C" int beat_pde_solve_begin(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w,
                                     const double* host_stim_amp, int n_stim, double* dev_x, double* dev_work, double rtol, double atol,
                                     int max_it) {
+  BEAT_REQUIRE(pde != nullptr && dev_work != nullptr && dev_v_prev && dev_x, "null argument");
+  BEAT_REQUIRE(beat_solve_lazy_available(pde), "this operator's solves are not of the kind that can be left open");
   return beat_solve_begin(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, dev_work, rtol, atol, max_it);
 }
 extern "C" int beat_pde_solve_end(beat_pde* pde, beat_ksp_info* info, int* host_pending) {
@@ -1489,97 +1531,7 @@ extern "C" int beat_pde_solve_ex(beat_pde* pde, const double* dev_v_prev,
     BEAT_REQUIRE(dev_v_prev && dev_x, "null argument");
     return beat_small_solve(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, rtol, atol, max_it, info);
   }
-  if (beat_solve_lazy_available(pde)) {
-    // Jacobi with the register-row kernels (constant coefficients: the loop that never stores q = A p) or on per-node rows:
-    // enqueue, then wait -- the two halves a caller may also drive apart (beat_pde_solve_begin / _end)
-    if (int rc = beat_solve_begin(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, dev_work, rtol, atol, max_it)) return rc;
-    return beat_solve_end(pde, defer_flush, info, host_pending, nullptr);
-  }
-  const int64_t fld = beat_pde_field_stride(pde);
-  double* r = dev_work + pde->g.plane;
-  double* q = r + fld;
-  double* z = q + fld;     // only touched by the polynomial preconditioner
-  double* ring = z + fld;  // pde->ring search directions, ring[j] = ring + j*fld
-  const int PR = pde->ring;
-  double* st = pde->d_st;
-  beat_ctx* ctx = pde->ctx;
-  double* h = ctx->h_pinned;
-  const int npass = pde->pc_ncoef - 1;
-  int rc;
-  if ((rc = beat_pde_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st))) return rc;
-  if ((rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;
-  int launched = 0;
-  int chunk = beat_pde_first_chunk(pde);
-  if (npass > 0) {
-    // polynomial preconditioner: classic in-place recurrences with p = ring[0]
-    double* p = ring;
-    for (int j = 0; j < npass; ++j)
-      if ((rc = beat_pde_pc_pass(pde, j, r, z, q, st, st + RZ))) return rc;
-    if ((rc = beat_pde_cg_first_z(pde, st, z, p))) return rc;
-    while (true) {
-      chunk = std::min(chunk, max_it - launched);
-      for (int it = 0; it < chunk; ++it) {
-        if ((rc = beat_pde_spmv_dot(pde, p, q, st))) return rc;
-        if ((rc = beat_pde_cg_update(pde, st, dev_x, r, p, q))) return rc;
-        for (int j = 0; j < npass; ++j)
-          if ((rc = beat_pde_pc_pass(pde, j, r, z, q, st, st + RZN))) return rc;
-        if ((rc = beat_pde_cg_next_z(pde, st, z, p))) return rc;
-      }
-      launched += chunk;
-      BEAT_HIP_CHECK(hipMemcpyAsync(h, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-      BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (h[STOP] != 0.0 || launched >= max_it) break;
-      chunk = 2;
-    }
-  } else {
-    // Jacobi on the LDS-tiled constant-coefficient kernels (BEAT_RR=0), deferred x: iteration i uses p_i = ring[i % PR]
-    while (true) {
-      chunk = std::min(chunk, max_it - launched);
-      for (int it = 0; it < chunk; ++it) {
-        const int i = launched + it, slot = i % PR;
-        double* p_cur = ring + (int64_t)slot * fld;
-        double* p_next = ring + (int64_t)((i + 1) % PR) * fld;
-        if ((rc = beat_pde_spmv_dot(pde, p_cur, q, st))) return rc;
-        if ((rc = beat_pde_cg_update_r(pde, st, r, q, slot))) return rc;
-        if (slot == PR - 1) {  // ring full: bring x up to date before slot 0 is overwritten
-          if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR))))
-            return rc;
-        }
-        if ((rc = beat_pde_cg_next_oop(pde, st, r, p_cur, p_next))) return rc;
-      }
-      launched += chunk;
-      BEAT_HIP_CHECK(hipMemcpyAsync(h, st, sizeof(double) * 16, hipMemcpyDeviceToHost, ctx->stream));
-      BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-      if (h[STOP] != 0.0 || launched >= max_it) break;
-      chunk = 2;
-    }
-    // directions of the last, partially filled ring cycle (stream-ordered before anything that reads x)
-    const int nupd = (int)h[NUPD], base = (nupd / PR) * PR;
-    const GuessTerms last = beat_guess_terms(pde, base);
-    beat_guess_observe(pde, (int)h[ITERS]);
-    if (beat_guess_end(pde, nupd, defer_flush != 0)) {
-      if (defer_flush) {  // the caller adds these directions itself (beat_ode_step_pending / beat_pde_x_flush)
-        host_pending[0] = pde->last_base = base;
-        host_pending[1] = nupd % PR;
-      } else if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, base, 0, last))) {
-        return rc;
-      }
-    }
-  }
-  const int iters = (int)h[ITERS];
-  pde->last_iters = iters;
-  int reason = (int)h[REASON];
-  if (h[STOP] == 0.0) reason = -3;  // max_it == launched without the latch (max_it = 0)
-  pde->last_info.iterations = iters;
-  pde->last_info.converged_reason = reason;
-  pde->last_info.residual_norm = std::sqrt(h[RR]);
-  pde->last_info.rhs_norm = std::sqrt(h[BB]);
-  if (info) *info = pde->last_info;
-  pde->last_rc = BEAT_OK;
-  if (reason < 0) {
-    beat_set_error("PCG did not converge in %d iterations (||r|| = %.3e, ||b|| = %.3e)", iters,
-                   std::sqrt(h[RR]), std::sqrt(h[BB]));
-    pde->last_rc = BEAT_ENOTCONV;
-  }
-  return pde->last_rc;
+  // enqueue, then wait -- the two halves a caller may also drive apart (beat_pde_solve_begin / _end) on the loops that can be left open
+  if (int rc = beat_solve_begin(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, dev_work, rtol, atol, max_it)) return rc;
+  return beat_solve_end(pde, defer_flush, info, host_pending, nullptr);
 }

@@ -37,6 +37,15 @@ struct Geom {
 
 enum { MODE_APPLY = 0, MODE_SPMV_DOT = 1, MODE_RHS = 2, MODE_PC = 3 };
 
+// The loops of a multi-launch solve (beat_pde::OpenSolve::kind): each is one body of the iterations beat_pde.hip enqueues
+enum SolveKind {
+  SOLVE_RR = 0,  // register-row kernels, constant coefficients: the loop that never stores q = A p
+  SOLVE_ROWS,    // per-node rows (OpenSolve::pdot: the fused tile pass)
+  SOLVE_TILED,   // the LDS-tiled constant-coefficient kernels (more blocks than BEAT_MAX_PARTIALS, or BEAT_RR=0)
+  SOLVE_POLY,    // the polynomial preconditioner: classic in-place recurrences, x updated as it goes, no ring
+  SOLVE_DIST     // a decomposed solve (beat_dist.hip; OpenSolve::rr / merged / vpdot say which of its loops runs)
+};
+
 }  // namespace beat_pde_detail
 
 struct beat_pde {
@@ -54,22 +63,21 @@ struct beat_pde {
   int z_last_iters = -1;  // iterations of the last shifted solve (beat_pde_zsolve: its first chunk of enqueued iterations)
   unsigned vec_grid = 1;
   double* d_alphas = nullptr;  // PRING_MAX step lengths of the deferred-x PCG
-  // A solve that has been ENQUEUED and not yet looked at by the host (beat_pde_solve_begin / _end, round 5): right-hand side, the
+  // A solve that has been ENQUEUED and not yet looked at by the host (beat_solve_open / beat_solve_end, round 5): right-hand side, the
   // iterations the previous solve needed + 1 and the copy of the scalar state are in the stream, `ev_st` marks the copy.  The next
   // ionic launch may be enqueued behind it before the host waits (PendingV::dev_st): the device does not idle while the host wakes up.
+  // Every multi-launch solve goes through this state; only the register-row and per-node-row ones may be left open by a caller.
   struct OpenSolve {
     bool on = false;
-    int kind = 0;  // 0: register-row kernels (constant coefficients), 1: per-node rows
+    int kind = beat_pde_detail::SOLVE_RR;
     bool pdot = false;
-    const double* v_prev = nullptr;
     double* x = nullptr;
     double* work = nullptr;
-    double rtol = 0.0, atol = 0.0;
     int max_it = 0, launched = 0;
-    // a decomposed solve (beat_dist.hip: beat_dist_solve_begin / _end): its communicator and which of its loops runs
+    int limit = 0;  // iterations that may be enqueued: max_it (+ 1 merged: the pass that finds r_k converged is one more than the k updates)
+    // a decomposed solve (beat_dist.hip: beat_dist_solve_begin): its communicator and which of its loops runs
     void* comm = nullptr;
     bool rr = false, merged = false, vpdot = false;
-    int limit = 0;
   } open;
   // set by beat_solve_begin around its right-hand side: the start of the solve (pcg_begin_kernel's step) is to run in the launch that
   // sums the right-hand side's partials; `done` says a right-hand side took it up
@@ -149,6 +157,20 @@ struct beat_pde {
   const double* dinv_arg() const { return var ? v_dinv : d_dinv(); }
 };
 
+// The PCG's work area (beat_pde_work_fields fields, beat_pde_field_stride doubles apart): [ghost plane | r | q | z | ring[0..]].
+// Each field sits behind its lower ghost plane, which the stencil kernels read (a decomposed grid: the neighbour's boundary plane)
+// like the upper one behind it; z is only touched by the polynomial preconditioner; ring[j] = ring + j * fld.  (HipOps in
+// beat/_engine.py mirrors this layout.)
+struct PcgWork {
+  double *r, *q, *z, *ring;
+  int64_t fld;
+};
+inline PcgWork beat_pcg_work(const beat_pde* pde, double* work) {
+  const int64_t fld = beat_pde_field_stride(pde);
+  double* r = work + pde->g.plane;
+  return {r, r + fld, r + 2 * fld, r + 3 * fld, fld};
+}
+
 // Iterations enqueued before the host first looks at the convergence latch: the previous solve's count plus one.  A
 // latched iteration costs four empty launches (~20 us); one short costs a host round trip with the GPU idle plus a
 // second one after the catch-up iterations, and consecutive time steps differ by one iteration all the time.
@@ -221,17 +243,26 @@ int beat_vtl_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* h
                  double* dev_x, double* dev_r, double* dev_p, double* dev_t, double* dev_red, const double* dev_e);
 int beat_vtl_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, double* dev_q, int first);
 
-// the two halves of beat_pde_solve_ex for the Jacobi paths (beat_pde.hip): enqueue without waiting / wait, iterate on if needed, do
-// the host's bookkeeping.  beat_solve_end: *needed_more = the first look found the solve unlatched (a launch enqueued behind it
-// with PendingV::dev_st has done nothing); a solve that was never opened: the last finished solve's record
+// The multi-launch solves in two halves.  beat_solve_open (beat_pde.hip), called by a begin once its right-hand side and start are
+// enqueued: pde->open = `o` (limit set from o.max_it), the first chunk of iterations and the copy of the scalar state for the first
+// look.  beat_solve_end: wait for that look, enqueue more iterations if the residual asks for them, do the host's bookkeeping;
+// *needed_more = the first look found the solve unlatched (a launch enqueued behind it with PendingV::dev_st has done nothing); a
+// solve that was never opened: the last finished solve's record
 bool beat_solve_lazy_available(const beat_pde* pde);
+int beat_solve_open(beat_pde* pde, beat_pde::OpenSolve o);
+int beat_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* host_pending, bool* needed_more);
+// the record of a solve from its scalar state h (16 doubles); BEAT_ENOTCONV with the error set when it did not converge (batch_step
+// >= 0: the solve of that step of a beat_split_steps batch)
+beat_ksp_info beat_pcg_info(const double* h);
+int beat_pcg_check(const beat_ksp_info& info, int batch_step = -1);
+// the decomposed solve's part of the above (beat_dist.hip): its begin, iterations [open.launched, + count) with their exchanges and
+// all-reduces, the error of a peer after each look (ipc transport), the exchange left in flight by the last residual update
 struct beat_comm;
 int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_prev, const double* const* host_dev_stim_w,
                           const double* host_stim_amp, int n_stim, double* dev_x, double* dev_work, double rtol, double atol, int max_it);
-int beat_dist_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* host_pending, bool* needed_more);
-int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp, int n_stim,
-                     double* dev_x, double* dev_work, double rtol, double atol, int max_it);
-int beat_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* host_pending, bool* needed_more);
+int beat_dist_enqueue_iterations(beat_pde* pde, int count);
+int beat_dist_check(beat_pde* pde);
+int beat_dist_drain(beat_pde* pde);
 
 // one-workgroup solve of small constant-coefficient grids (beat_pde_small.hip)
 bool beat_small_available(const beat_pde* pde);

@@ -356,18 +356,8 @@ int beat_small_solve(beat_pde* pde, const double* dev_v_prev, const double* cons
     beat_guess_observe(pde, (int)h[ITERS]);
     beat_guess_advance(pde);
   }
-  const int iters = (int)h[ITERS], reason = (int)h[REASON];
-  pde->last_iters = iters;
-  if (info) {
-    info->iterations = iters;
-    info->converged_reason = reason;
-    info->residual_norm = std::sqrt(h[RR]);
-    info->rhs_norm = std::sqrt(h[BB]);
-  }
-  if (reason < 0) {
-    beat_set_error("PCG did not converge in %d iterations (||r|| = %.3e, ||b|| = %.3e)", iters, std::sqrt(h[RR]),
-                   std::sqrt(h[BB]));
-    return BEAT_ENOTCONV;
-  }
-  return BEAT_OK;
+  const beat_ksp_info k = beat_pcg_info(h);
+  pde->last_iters = k.iterations;
+  if (info) *info = k;
+  return beat_pcg_check(k);
 }

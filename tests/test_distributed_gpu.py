@@ -94,6 +94,60 @@ def test_collective_path_on_one_rank_matches_single_slab_solve(hip_ctx, per_node
             dist.destroy_process_group()
 
 
+def test_lds_tiled_jacobi_loop_matches_stage_loop(hip_ctx, monkeypatch):
+    """BEAT_RR=0 on a constant-coefficient single slab: beat_pde_solve_ex runs the LDS-tiled Jacobi loop (the loop of grids with
+    more blocks than BEAT_MAX_PARTIALS) -- against the stage-driven loop on one rank, which launches the same stage kernels one by
+    one; then the same solve with its last partial ring cycle deferred and flushed."""
+    import torch.distributed as dist
+
+    from beat import _stencil
+    from beat._engine import DiffusionSolver, HipOps, Slab
+
+    monkeypatch.setenv("BEAT_RR", "0")
+    ctx = hip_ctx
+    created = False
+    if not dist.is_initialized():
+        dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{_free_port()}", rank=0, world_size=1,
+                                device_id=ctx.device)
+        created = True
+    try:
+        nx, ny, nz = 40, 33, 17
+        f0 = np.array([np.cos(np.pi / 6), np.sin(np.pi / 6), 0.0])
+        M = 9.5e-4 * np.outer(f0, f0) + 1.25e-4 * (np.eye(3) - np.outer(f0, f0))
+        mt, kt = _stencil.stencil_tables(3, (0.1, 0.1, 0.1), M)
+        v = -85.0 + 30.0 * np.random.default_rng(5).random(nx * ny * nz)
+        results = []
+        for mode in ("fused", "stage"):
+            ops = HipOps(ctx, (nx, ny, nz), True, True, mt, kt)
+            ops.set_small(False)
+            ops.set_timestep(0.01, 0.5, 0.05)
+            assert not ops.can_open()  # neither the register-row nor the per-node-row loop: the tiled one
+            solver = DiffusionSolver(ops, Slab(nz), force_distributed=mode == "stage", stage_driven=mode == "stage")
+            fv, fx = ops.new_field(), ops.new_field()
+            fv.set(v)
+            res = solver.solve(fv, [], [], fx, rtol=1e-11, atol=1e-50, max_it=200)
+            results.append((fx.numpy(), res))
+        (x1, r1), (xs, rs) = results
+        assert r1.converged_reason > 0 and r1.iterations % 6  # (a partial last ring cycle: the deferral below has work)
+        assert rs.iterations == r1.iterations and rs.converged_reason == r1.converged_reason
+        np.testing.assert_array_equal(xs, x1)
+        # the fused solve again, its last partial ring cycle left pending until flushed: the same bits
+        ops = HipOps(ctx, (nx, ny, nz), True, True, mt, kt)
+        ops.set_small(False)
+        ops.set_timestep(0.01, 0.5, 0.05)
+        fv, fx = ops.new_field(), ops.new_field()
+        fv.set(v)
+        res = ops.solve_single(fv, [], [], fx, 1e-11, 1e-50, 200, defer_flush=True)
+        assert res.iterations == r1.iterations and ops.pending is not None
+        assert not np.array_equal(fx.numpy(), x1)
+        ops.flush_pending()
+        assert ops.pending is None
+        np.testing.assert_array_equal(fx.numpy(), x1)
+    finally:
+        if created:
+            dist.destroy_process_group()
+
+
 class _ThreadWorld:
     """A torch.distributed look-alike for several threads of one process, each playing one rank: the pieces
     DiffusionSolver uses (all_reduce on device tensors, P2POp / batch_isend_irecv of ghost planes).  A one-GPU box
