@@ -251,8 +251,8 @@ class _DeviceODE:
             hp, npar, ppn, pld = self._per_node_args
         pend = None
         behind = False  # enqueue this launch BEHIND a solve that is still open (pending = -1: beat_ode_step_pending)
+        model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
         if pending_ops is not None and getattr(pending_ops, "open_x", None) is not None:
-            model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
             long_ring = len(pending_ops.ring) > 6  # (only the class kernel takes more than six pending directions)
             if (v_row is not None and int(v_index) == model_v and pending_ops.open_x.ptr.value == v_row.ptr.value
                     and (self.node_map is None or self.node_map[1].ptr.value == v_row.ptr.value)
@@ -262,7 +262,6 @@ class _DeviceODE:
             else:
                 pending_ops.solve_finish()
         if not behind and pending_ops is not None and pending_ops.pending is not None:
-            model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
             if (v_row is not None and int(v_index) == model_v
                     and pending_ops.pending[0].ptr.value == v_row.ptr.value
                     and (self.node_map is None or self.node_map[1].ptr.value == v_row.ptr.value)):
@@ -270,33 +269,30 @@ class _DeviceODE:
                 pending_ops.pending = None
             else:
                 pending_ops.flush_pending()
+        # (operator, ring, field stride, count) of what the launch applies, as the pending-update entry points take them
+        pend_args = (None, None, 0, 0) if pend is None else (pending_ops.handle, pending_ops.ring[0].ptr, pending_ops.fld, int(pend[2]))
         with self.monitor.track_time("ode_total_step"):
             with self.monitor.track_time("ode_function_call"):
                 if use_classes:
                     mk, table, ncls = self.classes
-                    if int(v_index) != self.model.state_index(self.model.v_name) and pend is not None:
+                    if int(v_index) != model_v and pend is not None:
                         raise ValueError("a pending update needs the model's own potential row")
                     nmap, vfield = (None, None) if self.node_map is None else (C.c_void_p(self.node_map[0].data_ptr()), self.node_map[1].ptr)
                     _hip.check(self.ctx.lib.beat_ode_step_classes(
                         self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, C.c_void_p(table.data_ptr()),
                         ncls, C.c_void_p(mk.data_ptr()), float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr,
-                        nmap, vfield,
-                        pending_ops.handle if pend is not None else None, pending_ops.ring[0].ptr if pend is not None else None,
-                        pending_ops.fld if pend is not None else 0, int(pend[2]) if pend is not None else 0))
+                        nmap, vfield, *pend_args))
                 elif self._sparse is not None and ppn is not None and not self.explicit_classes:
                     uni, idx, rows = self._sparse
                     _hip.check(self.ctx.lib.beat_ode_step_rows(
                         self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, uni.ctypes.data_as(C.c_void_p),
                         len(uni), idx.ctypes.data_as(C.c_void_p), len(idx), C.c_void_p(rows.data_ptr()), self.n, float(t0), float(dt),
-                        int(v_index), None if v_copy is None else v_copy.ptr,
-                        pending_ops.handle if pend is not None else None, pending_ops.ring[0].ptr if pend is not None else None,
-                        pending_ops.fld if pend is not None else 0, int(pend[2]) if pend is not None else 0))
+                        int(v_index), None if v_copy is None else v_copy.ptr, *pend_args))
                 elif pend is not None:
                     _hip.check(
                         self.ctx.lib.beat_ode_step_pending(
                             self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, hp, npar, ppn,
-                            pld, float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr,
-                            pending_ops.handle, pending_ops.ring[0].ptr, pending_ops.fld, int(pend[2]))
+                            pld, float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr, *pend_args)
                     )
                 else:
                     _hip.check(

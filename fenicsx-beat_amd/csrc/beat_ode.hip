@@ -40,6 +40,29 @@ static int launch_ode_run(beat_ctx* ctx, double* states, int64_t n, int64_t ld, 
   return BEAT_OK;
 }
 
+// The built-in cell models: f(ModelTag<M>{}) for the model of `model_id` (a generic lambda takes its type as
+// typename decltype(tag)::type); BEAT_NOT_BUILTIN for any other id -- each caller handles models registered as source itself.
+template <class M> struct ModelTag { using type = M; };
+constexpr int BEAT_NOT_BUILTIN = 1001;
+
+template <class F>
+static int with_builtin_model(int model_id, F&& f) {
+  switch (model_id) {
+    case BEAT_MODEL_SIMPLE_ODE: return f(ModelTag<SimpleOde>{});
+    case BEAT_MODEL_FHN_DEMO: return f(ModelTag<FhnDemo>{});
+    case BEAT_MODEL_FHN_README: return f(ModelTag<FhnReadme>{});
+    case BEAT_MODEL_TP06_GRL1: return f(ModelTag<Tp06Grl1>{});
+    case BEAT_MODEL_TORORD_DYNCL_GRL1: return f(ModelTag<TorordDynClGrl1>{});
+    case BEAT_MODEL_TORORD_LAND_GRL1: return f(ModelTag<TorordLandGrl1>{});
+    default: return BEAT_NOT_BUILTIN;
+  }
+}
+
+static int unknown_model(int model_id) {
+  beat_set_error("unknown model id %d", model_id);
+  return BEAT_EINVAL;
+}
+
 extern "C" int beat_ode_run(beat_ctx* ctx, int model_id, double* dev_states, int64_t n, int64_t ld,
                             const double* host_params, int num_params, const double* dev_params_per_node,
                             int64_t params_ld, double t0, double dt, int64_t nsteps, int nbeats, int save_freq,
@@ -50,19 +73,11 @@ extern "C" int beat_ode_run(beat_ctx* ctx, int model_id, double* dev_states, int
   if (model_id >= BEAT_MODEL_CUSTOM_BASE)  // a model registered as source (beat_ode_model_register)
     return beat_custom_run(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t0, dt, nsteps, nbeats,
                            save_freq, host_track_idx, ntrack, dev_trace);
-#define BEAT_RUN(M)                                                                                          \
-  return launch_ode_run<M>(ctx, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, \
-                           t0, dt, nsteps, nbeats, save_freq, host_track_idx, ntrack, dev_trace)
-  switch (model_id) {
-    case BEAT_MODEL_SIMPLE_ODE: BEAT_RUN(SimpleOde);
-    case BEAT_MODEL_FHN_DEMO: BEAT_RUN(FhnDemo);
-    case BEAT_MODEL_FHN_README: BEAT_RUN(FhnReadme);
-    case BEAT_MODEL_TP06_GRL1: BEAT_RUN(Tp06Grl1);
-    case BEAT_MODEL_TORORD_DYNCL_GRL1: BEAT_RUN(TorordDynClGrl1);
-    case BEAT_MODEL_TORORD_LAND_GRL1: BEAT_RUN(TorordLandGrl1);
-    default: beat_set_error("unknown model id %d", model_id); return BEAT_EINVAL;
-  }
-#undef BEAT_RUN
+  const int rc = with_builtin_model(model_id, [&](auto tag) {
+    return launch_ode_run<typename decltype(tag)::type>(ctx, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t0, dt,
+                                                        nsteps, nbeats, save_freq, host_track_idx, ntrack, dev_trace);
+  });
+  return rc == BEAT_NOT_BUILTIN ? unknown_model(model_id) : rc;
 }
 
 // blocks of an ionic launch over n nodes
@@ -102,6 +117,20 @@ static unsigned ode_grid(int64_t n, int num_states) {
   return grid;
 }
 
+// One parameter route's kernel: the instance that applies a pending update, or the one without.  (`auto`: instantiated where
+// launch_ode uses it, so that the code object lays the kernels out in the order the routes are written.)
+template <class Model, bool PER_NODE, bool MARKED = false, bool SPARSE = false>
+static auto launch_instance(bool have_pend, hipStream_t stream, unsigned grid, double* states, int64_t n, int64_t ld,
+                            const ParamPack<Model::NP>& prm, const typename Model::Derived& drv, const double* ppn, int64_t pld, double t,
+                            double dt, int v_index, double* v_copy, const PendingV& pend, const MarkedArgs& mk, const SparseRows& sp) {
+  if (have_pend)
+    BEAT_KERNEL((ode_step_kernel<Model, PER_NODE, true, MARKED, SPARSE>), dim3(grid), dim3(BEAT_BLOCK), 0, stream, states, n, ld, prm, drv,
+                ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
+  else
+    BEAT_KERNEL((ode_step_kernel<Model, PER_NODE, false, MARKED, SPARSE>), dim3(grid), dim3(BEAT_BLOCK), 0, stream, states, n, ld, prm, drv,
+                ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
+}
+
 template <class Model>
 static int launch_ode(beat_ctx* ctx, double* states, int64_t n, int64_t ld, const double* host_params,
                       int num_params, const double* ppn, int64_t pld, double t, double dt,
@@ -113,77 +142,49 @@ static int launch_ode(beat_ctx* ctx, double* states, int64_t n, int64_t ld, cons
   // two-parameter test ODE is called with on purpose and nothing else is)
   BEAT_REQUIRE(host_params != nullptr || ppn != nullptr || mk.markers != nullptr || Model::NP == 2,
                "no parameters given: a host vector, per-node rows or parameter classes");
-  BEAT_REQUIRE(v_copy == nullptr || (v_index >= 0 && v_index < Model::NS), "v_index %d out of range", v_index);
-  BEAT_REQUIRE(mk.markers == nullptr || v_copy == nullptr || v_index == Model::V_INDEX,
-               "the class kernel mirrors the model's potential (row %d), not row %d", Model::V_INDEX, v_index);
-  const bool have_pend = pend.count > 0 || pend.gt.d != nullptr || pend.dev_st != nullptr;
-  BEAT_REQUIRE(!have_pend || v_index == Model::V_INDEX,
-               "a pending update needs v_index = %d (the model's membrane potential), got %d", Model::V_INDEX, v_index);
+  if (int rc = beat_check_step_rows(Model::NS, Model::V_INDEX, v_index, v_copy, mk.markers != nullptr, pend)) return rc;
+  const bool have_pend = beat_pending_has_work(pend);
   ParamPack<Model::NP> prm;
   for (int k = 0; k < Model::NP; ++k) prm.p[k] = host_params ? host_params[k] : 1.0;
   typename Model::Derived drv = Model::derive(prm.p);
   const unsigned grid = ode_grid(n, Model::NS);
-  const dim3 g3(grid), b3(BEAT_BLOCK);
-#define BEAT_LAUNCH_ODE(PN, PD)                                                                                 \
-  BEAT_KERNEL((ode_step_kernel<Model, PN, PD>), g3, b3, 0, ctx->stream, states, n, ld, prm, drv, ppn, pld, t, \
-                     dt, v_index, v_copy, pend, mk, sp)
   if (mk.markers != nullptr) {
     BEAT_REQUIRE(ppn == nullptr && mk.table != nullptr, "parameter classes come with a table, not with per-node rows");
-    if (have_pend)
-      BEAT_KERNEL((ode_step_kernel<Model, false, true, true>), g3, b3, 0, ctx->stream, states, n, ld, prm, drv, ppn, pld, t, dt,
-                  v_index, v_copy, pend, mk, sp);
-    else
-      BEAT_KERNEL((ode_step_kernel<Model, false, false, true>), g3, b3, 0, ctx->stream, states, n, ld, prm, drv, ppn, pld, t, dt,
-                  v_index, v_copy, pend, mk, sp);
+    launch_instance<Model, false, true>(have_pend, ctx->stream, grid, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
   } else if (ppn != nullptr && sp.count > 0) {
     BEAT_REQUIRE(pld >= n, "params_ld %lld < n %lld", (long long)pld, (long long)n);
     BEAT_REQUIRE(host_params != nullptr, "sparse rows come with the uniform parameter vector");
     // the instance with these indices as compile-time constants, written and compiled at first use (beat_ode_jit.hip); where
     // that is not to be had (no hipcc, BEAT_JIT=0, a model without accessor-style parameters) the run-time-index kernel below
     {
-      const int rc = beat_ode_jit_launch<Model>(ctx, g3, have_pend, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
+      const int rc = beat_ode_jit_launch<Model>(ctx, dim3(grid), have_pend, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
       if (rc != BEAT_JIT_UNAVAILABLE) return rc;
     }
     // (the shipped kernel finds a row's entry by comparison at run time: four rows; more need the compiled instance)
     BEAT_REQUIRE(sp.count <= BEAT_MAX_SPARSE_ROWS_RT, "%d varying rows need run-time compilation, which is not available here "
                  "(beat_ode_jit_stats; at most %d rows otherwise): pass all rows (beat_ode_step)", sp.count, BEAT_MAX_SPARSE_ROWS_RT);
-    if (have_pend)
-      BEAT_KERNEL((ode_step_kernel<Model, true, true, false, true>), g3, b3, 0, ctx->stream, states, n, ld, prm, drv, ppn, pld, t, dt,
-                  v_index, v_copy, pend, mk, sp);
-    else
-      BEAT_KERNEL((ode_step_kernel<Model, true, false, false, true>), g3, b3, 0, ctx->stream, states, n, ld, prm, drv, ppn, pld, t, dt,
-                  v_index, v_copy, pend, mk, sp);
+    launch_instance<Model, true, false, true>(have_pend, ctx->stream, grid, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk,
+                                              sp);
   } else if (ppn != nullptr) {
     BEAT_REQUIRE(pld >= n, "params_ld %lld < n %lld", (long long)pld, (long long)n);
-    if (have_pend)
-      BEAT_LAUNCH_ODE(true, true);
-    else
-      BEAT_LAUNCH_ODE(true, false);
+    launch_instance<Model, true>(have_pend, ctx->stream, grid, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
   } else {
-    if (have_pend)
-      BEAT_LAUNCH_ODE(false, true);
-    else
-      BEAT_LAUNCH_ODE(false, false);
+    launch_instance<Model, false>(have_pend, ctx->stream, grid, states, n, ld, prm, drv, ppn, pld, t, dt, v_index, v_copy, pend, mk, sp);
   }
-#undef BEAT_LAUNCH_ODE
   BEAT_LAUNCH_CHECK();
   return BEAT_OK;
 }
 
 extern "C" int beat_ode_model_info(int model_id, int* num_states, int* num_params) {
-  int ns, np;
-  switch (model_id) {
-    case BEAT_MODEL_SIMPLE_ODE: ns = SimpleOde::NS; np = SimpleOde::NP; break;
-    case BEAT_MODEL_FHN_DEMO: ns = FhnDemo::NS; np = FhnDemo::NP; break;
-    case BEAT_MODEL_FHN_README: ns = FhnReadme::NS; np = FhnReadme::NP; break;
-    case BEAT_MODEL_TP06_GRL1: ns = Tp06Grl1::NS; np = Tp06Grl1::NP; break;
-    case BEAT_MODEL_TORORD_DYNCL_GRL1: ns = TorordDynClGrl1::NS; np = TorordDynClGrl1::NP; break;
-    case BEAT_MODEL_TORORD_LAND_GRL1: ns = TorordLandGrl1::NS; np = TorordLandGrl1::NP; break;
-    default:
-      if (beat_custom_model_info(model_id, &ns, &np, nullptr) == BEAT_OK) break;  // a model registered as source
-      beat_set_error("unknown model id %d", model_id);
-      return BEAT_EINVAL;
-  }
+  int ns = 0, np = 0;
+  const int rc = with_builtin_model(model_id, [&](auto tag) {
+    using M = typename decltype(tag)::type;
+    ns = M::NS;
+    np = M::NP;
+    return BEAT_OK;
+  });
+  if (rc == BEAT_NOT_BUILTIN && beat_custom_model_info(model_id, &ns, &np, nullptr) != BEAT_OK)  // a model registered as source?
+    return unknown_model(model_id);
   if (num_states) *num_states = ns;
   if (num_params) *num_params = np;
   return BEAT_OK;
@@ -206,19 +207,11 @@ static int ode_step_dispatch(beat_ctx* ctx, int model_id, double* dev_states, in
     return beat_custom_step(ctx, model_id, ode_grid(n, cns), dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t, dt,
                             v_index, dev_v_copy, pend, mk);
   }
-#define BEAT_STEP(M)                                                                                             \
-  return launch_ode<M>(ctx, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t, dt, \
-                       v_index, dev_v_copy, pend, mk, sp)
-  switch (model_id) {
-    case BEAT_MODEL_SIMPLE_ODE: BEAT_STEP(SimpleOde);
-    case BEAT_MODEL_FHN_DEMO: BEAT_STEP(FhnDemo);
-    case BEAT_MODEL_FHN_README: BEAT_STEP(FhnReadme);
-    case BEAT_MODEL_TP06_GRL1: BEAT_STEP(Tp06Grl1);
-    case BEAT_MODEL_TORORD_DYNCL_GRL1: BEAT_STEP(TorordDynClGrl1);
-    case BEAT_MODEL_TORORD_LAND_GRL1: BEAT_STEP(TorordLandGrl1);
-    default: beat_set_error("unknown model id %d", model_id); return BEAT_EINVAL;
-  }
-#undef BEAT_STEP
+  const int rc = with_builtin_model(model_id, [&](auto tag) {
+    return launch_ode<typename decltype(tag)::type>(ctx, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t, dt,
+                                                    v_index, dev_v_copy, pend, mk, sp);
+  });
+  return rc == BEAT_NOT_BUILTIN ? unknown_model(model_id) : rc;
 }
 
 extern "C" int beat_ode_step(beat_ctx* ctx, int model_id, double* dev_states, int64_t n, int64_t ld,
@@ -256,8 +249,6 @@ static int step_behind_open_solve(beat_ctx* ctx, beat_pde* pde, const double* de
   BEAT_REQUIRE(dev_ring0 != nullptr && field_stride >= n, "bad pending update");
   BEAT_REQUIRE(pde->open.x == v_row, "the open solve does not work on this row");
   PendingV behind{dev_ring0, field_stride, pde->d_alphas, 0, pde->guess, pde->d_st, pde->ring};
-  const bool plain_kernel_fits = pde->ring <= BEAT_MAX_PENDING;  // (a longer ring: only the class kernel takes it all)
-  (void)plain_kernel_fits;
   if (int rc = launch(behind)) return rc;
   beat_ksp_info info{};
   int pend2[2] = {0, 0};
@@ -282,30 +273,43 @@ static int step_behind_open_solve(beat_ctx* ctx, beat_pde* pde, const double* de
   return launch(pend);
 }
 
-extern "C" int beat_ode_step_pending(beat_ctx* ctx, int model_id, double* dev_states, int64_t n, int64_t ld,
-                                     const double* host_params, int num_params,
-                                     const double* dev_params_per_node, int64_t params_ld, double t, double dt,
-                                     int v_index, double* dev_v_copy, beat_pde* pde, const double* dev_ring0,
-                                     int64_t field_stride, int pending) {
+// The pending-update protocol of the step entry points (beat_ode_step_pending / _rows / _classes): what a deferred solve left to
+// this launch -- search directions in dev_ring0's ring, `pending` of them, and the guess increment -- handed to `launch`, or with
+// pending = -1 the launch enqueued behind the operator's open solve.  long_ring: the class kernel, which takes all
+// BEAT_MAX_PENDING_CLASS directions; the others take BEAT_MAX_PENDING and leave a longer ring to the flush pass.  node_map: the
+// potential is a field of the PDE's grid (v_row), whose stride is not measured in the state array's n nodes.
+static int step_with_pending(beat_ctx* ctx, beat_pde* pde, double* v_row, int64_t n, const double* dev_ring0, int64_t field_stride,
+                             int pending, bool long_ring, bool node_map, const std::function<int(const PendingV&)>& launch) {
   static_assert(BEAT_MAX_PENDING == beat_pde_detail::PRING && BEAT_MAX_PENDING_CLASS == beat_pde_detail::PRING_MAX, "pending directions = ring size");
   if (pending == -1) {
-    BEAT_REQUIRE(pde != nullptr && pde->ring <= BEAT_MAX_PENDING, "this kernel's pending path takes %d directions: finish the solve first", BEAT_MAX_PENDING);
-    return step_behind_open_solve(ctx, pde, dev_ring0, field_stride, n, dev_states + (int64_t)v_index * ld, [&](const PendingV& pv) {
-      return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t, dt, v_index,
-                               dev_v_copy, pv);
-    });
+    BEAT_REQUIRE(long_ring || (pde != nullptr && pde->ring <= BEAT_MAX_PENDING),
+                 "this kernel's pending path takes %d directions: finish the solve first", BEAT_MAX_PENDING);
+    return step_behind_open_solve(ctx, pde, dev_ring0, field_stride, node_map ? 0 : n, v_row, launch);
   }
   BEAT_REQUIRE(pending >= 0 && pending <= BEAT_MAX_PENDING_CLASS, "pending count %d out of range", pending);
-  BEAT_REQUIRE(pending == 0 || (pde != nullptr && dev_ring0 != nullptr && field_stride >= n), "bad pending update");
+  BEAT_REQUIRE(pending == 0 || (pde != nullptr && dev_ring0 != nullptr && (field_stride >= n || node_map)), "bad pending update");
   BEAT_REQUIRE(pde == nullptr || !pde->open.on, "the operator has an open solve: finish it (beat_pde_solve_end) or pass pending = -1");
-  if (int rc = flush_long_ring(pde, dev_states + (int64_t)v_index * ld, dev_ring0, field_stride, pending)) return rc;
+  if (!long_ring)
+    if (int rc = flush_long_ring(pde, v_row, dev_ring0, field_stride, pending)) return rc;
   PendingV pend{dev_ring0, field_stride, pending ? pde->d_alphas : nullptr, pending, {}};
   if (pde != nullptr && pde->guess_pending) {  // this launch is the application the deferring solve left open
     pend.gt = pde->guess_final;
     pde->guess_pending = false;
   }
-  return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld,
-                           t, dt, v_index, dev_v_copy, pend);
+  return launch(pend);
+}
+
+extern "C" int beat_ode_step_pending(beat_ctx* ctx, int model_id, double* dev_states, int64_t n, int64_t ld,
+                                     const double* host_params, int num_params,
+                                     const double* dev_params_per_node, int64_t params_ld, double t, double dt,
+                                     int v_index, double* dev_v_copy, beat_pde* pde, const double* dev_ring0,
+                                     int64_t field_stride, int pending) {
+  double* v_row = dev_states + (int64_t)v_index * ld;
+  return step_with_pending(ctx, pde, v_row, n, dev_ring0, field_stride, pending, /*long_ring=*/false, /*node_map=*/false,
+                           [&](const PendingV& pv) {
+    return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_params_per_node, params_ld, t, dt, v_index,
+                             dev_v_copy, pv);
+  });
 }
 
 
@@ -326,24 +330,12 @@ extern "C" int beat_ode_step_rows(beat_ctx* ctx, int model_id, double* dev_state
     BEAT_REQUIRE(host_row_params[j] >= 0 && host_row_params[j] < num_params, "row %d names parameter %d of %d", j, host_row_params[j], num_params);
     sp.idx[j] = host_row_params[j];
   }
-  if (pending == -1) {  // behind an open solve (see beat_ode_step_pending)
-    BEAT_REQUIRE(pde != nullptr && pde->ring <= BEAT_MAX_PENDING, "this kernel's pending path takes %d directions: finish the solve first", BEAT_MAX_PENDING);
-    return step_behind_open_solve(ctx, pde, dev_ring0, field_stride, n, dev_states + (int64_t)v_index * ld, [&](const PendingV& pv) {
-      return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_rows, rows_ld, t, dt, v_index, dev_v_copy, pv,
-                               MarkedArgs{nullptr, nullptr, 0, nullptr, nullptr}, sp);
-    });
-  }
-  BEAT_REQUIRE(pending >= 0 && pending <= BEAT_MAX_PENDING_CLASS, "pending count %d out of range", pending);
-  BEAT_REQUIRE(pending == 0 || (pde != nullptr && dev_ring0 != nullptr && field_stride >= n), "bad pending update");
-  BEAT_REQUIRE(pde == nullptr || !pde->open.on, "the operator has an open solve: finish it (beat_pde_solve_end) or pass pending = -1");
-  if (int rc = flush_long_ring(pde, dev_states + (int64_t)v_index * ld, dev_ring0, field_stride, pending)) return rc;
-  PendingV pend{dev_ring0, field_stride, pending ? pde->d_alphas : nullptr, pending, {}};
-  if (pde != nullptr && pde->guess_pending) {
-    pend.gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
-  return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_rows, rows_ld, t, dt, v_index, dev_v_copy,
-                           pend, MarkedArgs{nullptr, nullptr, 0, nullptr, nullptr}, sp);
+  double* v_row = dev_states + (int64_t)v_index * ld;
+  return step_with_pending(ctx, pde, v_row, n, dev_ring0, field_stride, pending, /*long_ring=*/false, /*node_map=*/false,
+                           [&](const PendingV& pv) {
+    return ode_step_dispatch(ctx, model_id, dev_states, n, ld, host_params, num_params, dev_rows, rows_ld, t, dt, v_index, dev_v_copy, pv,
+                             MarkedArgs{nullptr, nullptr, 0, nullptr, nullptr}, sp);
+  });
 }
 
 template <class Model>
@@ -360,28 +352,16 @@ static int fill_table(const double* host_params, int num_params, int classes, st
   return BEAT_OK;
 }
 
-template <class Model>
-static int table_doubles() { return (int)(sizeof(OdeTableEntry<Model>) / sizeof(double)); }
-
 extern "C" int beat_ode_class_table_doubles(int model_id, int* doubles_per_class) {
   BEAT_REQUIRE(doubles_per_class != nullptr, "null argument");
-  switch (model_id) {
-    case BEAT_MODEL_SIMPLE_ODE: *doubles_per_class = table_doubles<SimpleOde>(); break;
-    case BEAT_MODEL_FHN_DEMO: *doubles_per_class = table_doubles<FhnDemo>(); break;
-    case BEAT_MODEL_FHN_README: *doubles_per_class = table_doubles<FhnReadme>(); break;
-    case BEAT_MODEL_TP06_GRL1: *doubles_per_class = table_doubles<Tp06Grl1>(); break;
-    case BEAT_MODEL_TORORD_DYNCL_GRL1: *doubles_per_class = table_doubles<TorordDynClGrl1>(); break;
-    case BEAT_MODEL_TORORD_LAND_GRL1: *doubles_per_class = table_doubles<TorordLandGrl1>(); break;
-    default: {
-      int np = 0;  // a model registered as source: its parameters + the one double of its (empty) Derived
-      if (beat_custom_model_info(model_id, nullptr, &np, nullptr) == BEAT_OK) {
-        *doubles_per_class = np + 1;
-        break;
-      }
-      beat_set_error("unknown model id %d", model_id);
-      return BEAT_EINVAL;
-    }
-  }
+  const int rc = with_builtin_model(model_id, [&](auto tag) {
+    *doubles_per_class = (int)(sizeof(OdeTableEntry<typename decltype(tag)::type>) / sizeof(double));
+    return BEAT_OK;
+  });
+  if (rc != BEAT_NOT_BUILTIN) return rc;
+  int np = 0;  // a model registered as source: its parameters + the one double of its (empty) Derived
+  if (beat_custom_model_info(model_id, nullptr, &np, nullptr) != BEAT_OK) return unknown_model(model_id);
+  *doubles_per_class = np + 1;
   return BEAT_OK;
 }
 
@@ -390,26 +370,17 @@ extern "C" int beat_ode_class_table_fill(beat_ctx* ctx, int model_id, const doub
   BEAT_REQUIRE(ctx != nullptr && host_params != nullptr && dev_table != nullptr, "null argument");
   BEAT_REQUIRE(classes >= 1 && classes <= BEAT_MAX_CLASSES, "1..%d parameter classes, got %d", BEAT_MAX_CLASSES, classes);
   std::vector<double> tab;
-  int rc;
-  switch (model_id) {
-    case BEAT_MODEL_SIMPLE_ODE: rc = fill_table<SimpleOde>(host_params, num_params, classes, tab); break;
-    case BEAT_MODEL_FHN_DEMO: rc = fill_table<FhnDemo>(host_params, num_params, classes, tab); break;
-    case BEAT_MODEL_FHN_README: rc = fill_table<FhnReadme>(host_params, num_params, classes, tab); break;
-    case BEAT_MODEL_TP06_GRL1: rc = fill_table<Tp06Grl1>(host_params, num_params, classes, tab); break;
-    case BEAT_MODEL_TORORD_DYNCL_GRL1: rc = fill_table<TorordDynClGrl1>(host_params, num_params, classes, tab); break;
-    case BEAT_MODEL_TORORD_LAND_GRL1: rc = fill_table<TorordLandGrl1>(host_params, num_params, classes, tab); break;
-    default: {
-      int np = 0;
-      if (beat_custom_model_info(model_id, nullptr, &np, nullptr) != BEAT_OK) {
-        beat_set_error("unknown model id %d", model_id);
-        return BEAT_EINVAL;
-      }
-      BEAT_REQUIRE(num_params == np, "model expects %d parameters, got %d", np, num_params);
-      tab.assign((size_t)(np + 1) * classes, 0.0);
-      for (int c = 0; c < classes; ++c)
-        for (int k = 0; k < np; ++k) tab[(size_t)c * (np + 1) + k] = host_params[(size_t)c * np + k];
-      rc = BEAT_OK;
-    }
+  int rc = with_builtin_model(model_id, [&](auto tag) {
+    return fill_table<typename decltype(tag)::type>(host_params, num_params, classes, tab);
+  });
+  if (rc == BEAT_NOT_BUILTIN) {
+    int np = 0;
+    if (beat_custom_model_info(model_id, nullptr, &np, nullptr) != BEAT_OK) return unknown_model(model_id);
+    BEAT_REQUIRE(num_params == np, "model expects %d parameters, got %d", np, num_params);
+    tab.assign((size_t)(np + 1) * classes, 0.0);
+    for (int c = 0; c < classes; ++c)
+      for (int k = 0; k < np; ++k) tab[(size_t)c * (np + 1) + k] = host_params[(size_t)c * np + k];
+    rc = BEAT_OK;
   }
   if (rc) return rc;
   BEAT_HIP_CHECK(hipMemcpyAsync(dev_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -427,24 +398,12 @@ extern "C" int beat_ode_step_classes(beat_ctx* ctx, int model_id, double* dev_st
   BEAT_REQUIRE(classes >= 1 && classes <= BEAT_MAX_CLASSES, "1..%d parameter classes, got %d", BEAT_MAX_CLASSES, classes);
   int stride = 0;
   if (int rc = beat_ode_class_table_doubles(model_id, &stride)) return rc;
-  if (pending == -1) {  // behind an open solve (see beat_ode_step_pending): the class kernel takes the long ring as well
-    double* v_row = dev_v_field != nullptr ? dev_v_field : dev_states + (int64_t)v_index * ld;
-    return step_behind_open_solve(ctx, pde, dev_ring0, field_stride, dev_node_map != nullptr ? 0 : n, v_row, [&](const PendingV& pv) {
-      return ode_step_dispatch(ctx, model_id, dev_states, n, ld, nullptr, 0, nullptr, 0, t, dt, v_index, dev_v_copy, pv,
-                               MarkedArgs{dev_markers, dev_table, stride, dev_node_map, dev_v_field});
-    });
-  }
-  BEAT_REQUIRE(pending >= 0 && pending <= BEAT_MAX_PENDING_CLASS, "pending count %d out of range", pending);
-  BEAT_REQUIRE(pending == 0 || (pde != nullptr && dev_ring0 != nullptr && (field_stride >= n || dev_node_map != nullptr)),
-               "bad pending update");
-  BEAT_REQUIRE(pde == nullptr || !pde->open.on, "the operator has an open solve: finish it (beat_pde_solve_end) or pass pending = -1");
-  PendingV pend{dev_ring0, field_stride, pending ? pde->d_alphas : nullptr, pending, {}};
-  if (pde != nullptr && pde->guess_pending) {
-    pend.gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
-  return ode_step_dispatch(ctx, model_id, dev_states, n, ld, nullptr, 0, nullptr, 0, t, dt, v_index, dev_v_copy, pend,
-                           MarkedArgs{dev_markers, dev_table, stride, dev_node_map, dev_v_field});
+  double* v_row = dev_v_field != nullptr ? dev_v_field : dev_states + (int64_t)v_index * ld;
+  return step_with_pending(ctx, pde, v_row, n, dev_ring0, field_stride, pending, /*long_ring=*/true, /*node_map=*/dev_node_map != nullptr,
+                           [&](const PendingV& pv) {
+    return ode_step_dispatch(ctx, model_id, dev_states, n, ld, nullptr, 0, nullptr, 0, t, dt, v_index, dev_v_copy, pv,
+                             MarkedArgs{dev_markers, dev_table, stride, dev_node_map, dev_v_field});
+  });
 }
 
 

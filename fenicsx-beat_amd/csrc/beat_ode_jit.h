@@ -24,7 +24,20 @@
 constexpr int BEAT_JIT_UNAVAILABLE = 1000;
 constexpr int BEAT_MODEL_CUSTOM_BASE = 100;  // model ids of cell models registered as source (beat_ode_model_register)
 int beat_custom_model_info(int model_id, int* ns, int* np, int* v_index);
-struct PendingV;
+
+// the launch has an update of the potential to apply: search directions, a guess increment, or an open solve to read them from
+inline bool beat_pending_has_work(const PendingV& pend) { return pend.count > 0 || pend.gt.d != nullptr || pend.dev_st != nullptr; }
+
+// What every ionic step checks of its rows, built-in or registered model alike (ns states, the potential in row v): the row
+// mirrored into v_copy, the class kernel's mirror (the model's potential only) and the row a pending update is added to.
+inline int beat_check_step_rows(int ns, int v, int v_index, const double* v_copy, bool marked, const PendingV& pend) {
+  BEAT_REQUIRE(v_copy == nullptr || (v_index >= 0 && v_index < ns), "v_index %d out of range", v_index);
+  BEAT_REQUIRE(!marked || v_copy == nullptr || v_index == v, "the class kernel mirrors the model's potential (row %d), not row %d", v, v_index);
+  BEAT_REQUIRE(!beat_pending_has_work(pend) || v_index == v,
+               "a pending update needs v_index = %d (the model's membrane potential), got %d", v, v_index);
+  return BEAT_OK;
+}
+
 int beat_custom_step(beat_ctx* ctx, int model_id, unsigned grid, double* states, int64_t n, int64_t ld, const double* host_params,
                      int num_params, const double* ppn, int64_t pld, double t, double dt, int v_index, double* v_copy, const PendingV& pend,
                      const MarkedArgs& mk);

@@ -559,11 +559,8 @@ int beat_custom_step(beat_ctx* ctx, int model_id, unsigned grid, double* states,
   BEAT_REQUIRE(marked || ((host_params != nullptr || per_node) && num_params == m.np),
                "model %s expects %d parameters (a host vector, per-node rows or classes), got %d", m.name.c_str(), m.np, num_params);
   BEAT_REQUIRE(!per_node || pld >= n, "params_ld %lld < n %lld", (long long)pld, (long long)n);
-  const bool have_pend = pend_in.count > 0 || pend_in.gt.d != nullptr || pend_in.dev_st != nullptr;
-  BEAT_REQUIRE(!have_pend || v_index == m.v_index, "a pending update needs v_index = %d (the model's membrane potential), got %d", m.v_index, v_index);
-  BEAT_REQUIRE(v_copy == nullptr || (v_index >= 0 && v_index < m.ns), "v_index %d out of range", v_index);
-  BEAT_REQUIRE(!marked || v_copy == nullptr || v_index == m.v_index, "the class kernel mirrors the model's potential (row %d), not row %d",
-               m.v_index, v_index);
+  if (int rc = beat_check_step_rows(m.ns, m.v_index, v_index, v_copy, marked, pend_in)) return rc;
+  const bool have_pend = beat_pending_has_work(pend_in);
   const char* tf[2] = {"false", "true"};
   const std::string what = std::string("step_n") + (per_node ? "1" : "0") + "p" + (have_pend ? "1" : "0") + "m" + (marked ? "1" : "0");
   hipFunction_t f = custom_instance(ctx, m, what,
