@@ -273,10 +273,18 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zdirection_kernel(Geom g, ZOp op, 
   }
 }
 
+// (ar + i ai) / (br + i bi) by Smith's scaling: |b|^2 is never formed, so the quotient of two dot products stays finite
+// wherever both are (|b| below 1e-154 or above 1e154 under- / overflows |b|^2); for bi = 0 it is the plain real division.
 __device__ __forceinline__ void zdiv(double ar, double ai, double br, double bi, double& cr, double& ci) {
-  const double den = br * br + bi * bi;
-  cr = (ar * br + ai * bi) / den;
-  ci = (ai * br - ar * bi) / den;
+  if (fabs(bi) <= fabs(br)) {
+    const double t = bi / br, den = br + bi * t;
+    cr = (ar + ai * t) / den;
+    ci = (ai - ar * t) / den;
+  } else {
+    const double t = br / bi, den = br * t + bi;
+    cr = (ar * t + ai) / den;
+    ci = (ai * t - ar) / den;
+  }
 }
 
 // Fixed-order sum of `nsum` block partials, then the scalar step of the stage that produced them:

@@ -34,3 +34,55 @@ def semidiscrete_exact(Mm, K, C_m, v0, f_spatial, T):
     Q = gc * (1.0 + lam * w) / den
     y = (y0 - P) * np.exp(-lam * T) + P * np.cos(T) + Q * np.sin(T)
     return X @ y
+
+
+def jacobi_cocg(S, b, rtol, atol, max_it, dtype=np.clongdouble):
+    """Host restatement of the stage solve of csrc/beat_pde_rk.hip: Jacobi-preconditioned COCG from x0 = 0 on the sparse S
+    (complex symmetric; real for a real dtype: plain Jacobi-PCG), in the precision of `dtype`.
+
+    r^T z and p^T q are unconjugated, rr = ||r||^2 is conjugated; tol^2 = max(rtol^2 ||b||^2, atol^2).  Reasons: 2 (rtol
+    met), 3 (atol met), -3 (max_it), -5 (p^T q = 0, or r^T z = 0 with r unconverged), checked in zscalar_kernel's order.
+    Returns (x, iterations, reason, sqrt(rr), sqrt(bb), history) with history[k] = rr / tol^2 after iteration k + 1."""
+    S = S.tocsr().astype(dtype)
+    b = np.asarray(b).astype(dtype)
+    d = S.diagonal()
+    dinv = np.zeros_like(d)
+    nz = d != 0
+    dinv[nz] = 1 / d[nz]
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = dinv * r
+    p = z.copy()
+    rz = r @ z
+    rr = np.real(np.vdot(r, r))
+    bb = rr
+    tr = rtol * rtol * bb
+    tol2 = max(tr, atol * atol)
+    its, reason, hist = 0, 0, []
+    if rr <= tol2:
+        reason = 2 if rr <= tr else 3
+    while reason == 0:
+        q = S @ p
+        pq = p @ q
+        if pq == 0:
+            reason = -5
+            break
+        alpha = rz / pq
+        x += alpha * p
+        r -= alpha * q
+        z = dinv * r
+        rzn = r @ z
+        rr = np.real(np.vdot(r, r))
+        beta = rzn / rz
+        rz = rzn
+        its += 1
+        hist.append(float(rr / tol2) if tol2 > 0 else np.inf)
+        if rr <= tol2:
+            reason = 2 if rr <= tr else 3
+        elif its >= max_it:
+            reason = -3
+        elif rzn == 0:
+            reason = -5
+        else:
+            p = z + beta * p
+    return x, its, reason, float(np.sqrt(rr)), float(np.sqrt(bb)), hist

@@ -55,22 +55,55 @@ def _setup(dim):
 @pytest.mark.parametrize("dim", [2, 3])
 @pytest.mark.parametrize("expr", TABLEAUX)
 def test_one_step_parity_with_coupled_stage_solve(expr, dim):
+    _one_step_parity(expr, *_setup(dim))
+
+
+def _setup_more(case):
+    """Meshes beyond _setup's: a 1-D interval (all y / z rows collapsed), a 2-D box with nx > 64 and an off-diagonal
+    tensor, a 3-D box with nx > 64, an off-diagonal tensor and C_m != 1."""
+    from beat import grid as g
+
+    if case == "interval300":
+        return g.create_interval(g.COMM_WORLD, 300, [0.0, 3.0]), 1.0, 1.0, 0.05
+    if case == "rect130x33":
+        mesh = g.create_rectangle(g.COMM_WORLD, [np.zeros(2), np.array([2.6, 0.66])], [130, 33])
+        return mesh, np.array([[2.0, 0.3], [0.3, 1.0]]), 1.0, 0.01
+    f0 = np.array([np.cos(np.pi / 6), np.sin(np.pi / 6), 0.0])
+    aniso3 = 9.5e-4 * np.outer(f0, f0) + 1.25e-4 * (np.eye(3) - np.outer(f0, f0))
+    mesh = g.create_box(g.COMM_WORLD, [np.zeros(3), np.array([1.4, 0.18, 0.1])], [70, 9, 5])
+    return mesh, aniso3, 0.01, 0.05
+
+
+@pytest.mark.parametrize("case", ["interval300", "rect130x33", "box70x9x5"])
+@pytest.mark.parametrize("expr", TABLEAUX)
+def test_one_step_parity_on_more_meshes(expr, case):
+    _one_step_parity(expr, *_setup_more(case))
+
+
+def _one_step_parity(expr, mesh, Mten, C_m, dt):
+    """Two steps of the model against the sparse coupled stage solve: <= 1e-9 relative."""
     import beat
     from beat import grid as g
     from oracle import fem
 
-    mesh, Mten, C_m, dt = _setup(dim)
+    dim = mesh.dim
     time = g.Constant(mesh, 0.0)
     x = g.SpatialCoordinate(mesh)
-    I_s = (1.0 + x[0] + 0.5 * x[1]) * (g.cos(3 * time) + 2.0)
+    if dim == 1:
+        I_s = (1.0 + x[0]) * (g.cos(3 * time) + 2.0)
+        spatial = lambda p: 1.0 + p[0]  # noqa: E731
+        v0 = lambda p: np.cos(np.pi * p[0])  # noqa: E731
+    else:
+        I_s = (1.0 + x[0] + 0.5 * x[1]) * (g.cos(3 * time) + 2.0)
+        spatial = lambda p: 1.0 + p[0] + 0.5 * p[1]  # noqa: E731
+        v0 = lambda p: np.cos(np.pi * p[0]) * (1.0 + p[1])  # noqa: E731
     t = _tableau(expr)
     model = beat.IrksomeMonodomainModel(time=time, mesh=mesh, M=Mten, butcher_tableau=t, I_s=I_s, params=TIGHT, C_m=C_m)
-    v0 = lambda p: np.cos(np.pi * p[0]) * (1.0 + p[1])  # noqa: E731
     model.state.interpolate(v0)
     om = _oracle_mesh(mesh)
     Mm = fem.assemble_mass(om)
     K = fem.assemble_stiffness(om, Mten if np.ndim(Mten) else Mten * np.eye(dim))
-    w = fem.load_vector(om, lambda p: 1.0 + p[0] + 0.5 * p[1])
+    w = fem.load_vector(om, spatial)
     G = lambda tt: (np.cos(3 * tt) + 2.0) * w  # noqa: E731
     v = v0(om.x.T)
     t0 = 0.2
@@ -82,6 +115,84 @@ def test_one_step_parity_with_coupled_stage_solve(expr, dim):
     got = np.asarray(model.state.x.array)
     assert np.abs(got - v).max() / np.abs(v).max() < 1e-9
     assert model.ksp.converged_reason > 0 and model.ksp.iterations > 0
+
+
+def _moving_pulse(g, x, time, shift):
+    """A stimulus that mixes x and t (no separable form): re-integrated at every stage time."""
+    return g.exp(-((x[0] - shift - 0.5 * time) ** 2) / 0.05)
+
+
+@pytest.mark.parametrize("mixed", [False, True], ids=["alone", "with_separable"])
+@pytest.mark.parametrize("expr", ["Alexander()", "LobattoIIIA(2)", "RadauIIA(3)", "GaussLegendre(2)"])
+def test_non_separable_stimulus_against_coupled_stage_solve(expr, mixed):
+    """A stimulus that is not a product f(x) g(t) goes through _CompiledStimulus.general: its weights are integrated again
+    at every stage time into per-stage load fields.  Alone and next to a separable stimulus (both kinds in one _merge),
+    on the lower-triangular and the diagonalised paths, against the coupled stage solve with G(t) = int f(x, t) phi_i
+    by the same quadrature (5 Gauss points per collapsed axis, stimulation.assemble_weights)."""
+    import beat
+    from beat import grid as g
+    from beat.stimulation import Stimulus
+    from oracle import fem
+
+    mesh = g.create_rectangle(g.COMM_WORLD, [np.zeros(2), np.array([1.2, 0.6])], [48, 24])
+    Mten, C_m, dt = np.array([[2.0, 0.3], [0.3, 1.0]]) * 0.1, 1.0, 0.05
+    time = g.Constant(mesh, 0.0)
+    x = g.SpatialCoordinate(mesh)
+    dx = g.dx(domain=mesh)
+    I_s = [Stimulus(expr=_moving_pulse(g, x, time, 0.3), dZ=dx)]
+    if mixed:
+        I_s.append(Stimulus(expr=(1.0 + x[0]) * (g.cos(3 * time) + 2.0), dZ=dx))
+    t = _tableau(expr)
+    model = beat.IrksomeMonodomainModel(time=time, mesh=mesh, M=Mten, butcher_tableau=t, I_s=I_s, params=TIGHT, C_m=C_m)
+    assert model._stimuli[0].general is not None
+    assert not mixed or model._stimuli[1].general is None
+    v0 = lambda p: np.cos(np.pi * p[0]) * (1.0 + p[1])  # noqa: E731
+    model.state.interpolate(v0)
+    om = _oracle_mesh(mesh)
+    Mm = fem.assemble_mass(om)
+    K = fem.assemble_stiffness(om, Mten)
+    w_sep = fem.load_vector(om, lambda p: 1.0 + p[0], m=5)
+
+    def G(tt):
+        out = fem.load_vector(om, lambda p: np.exp(-((p[0] - 0.3 - 0.5 * tt) ** 2) / 0.05), m=5)
+        return out + (np.cos(3 * tt) + 2.0) * w_sep if mixed else out
+
+    v = v0(om.x.T)
+    t0 = 0.1
+    for _ in range(2):
+        model.step((t0, t0 + dt))
+        v = _sparse_coupled_step(Mm, K, C_m, t.A, t.b, t.c, dt, v, G, t0)
+        t0 += dt
+    got = np.asarray(model.state.x.array)
+    assert np.abs(got - v).max() / np.abs(v).max() < 1e-9
+    assert model.ksp.converged_reason > 0
+
+
+def test_too_many_load_fields_are_refused():
+    """RadauIIA(3) with three non-separable stimuli needs 3 x 3 = 9 load fields in a stage right-hand side, one more than
+    the kernel takes: NotImplementedError, and the state is left as it was."""
+    import beat
+    from beat import grid as g
+    from beat.stimulation import Stimulus
+
+    mesh = g.create_unit_square(g.COMM_WORLD, 12, 12)
+    time = g.Constant(mesh, 0.0)
+    x = g.SpatialCoordinate(mesh)
+    dx = g.dx(domain=mesh)
+    I_s = [Stimulus(expr=_moving_pulse(g, x, time, s), dZ=dx) for s in (0.2, 0.4, 0.6)]
+    model = beat.IrksomeMonodomainModel(time=time, mesh=mesh, M=1.0, butcher_tableau=_tableau("RadauIIA(3)"), I_s=I_s,
+                                        params=TIGHT)
+    model.state.interpolate(lambda p: np.cos(np.pi * p[0]))
+    before = np.asarray(model.state.x.array).copy()
+    with pytest.raises(NotImplementedError):
+        model.step((0.0, 0.05))
+    assert np.array_equal(np.asarray(model.state.x.array), before)
+    # two of them fit (6 fields)
+    time.value = 0.0
+    model2 = beat.IrksomeMonodomainModel(time=time, mesh=mesh, M=1.0, butcher_tableau=_tableau("RadauIIA(3)"),
+                                         I_s=I_s[:2], params=TIGHT)
+    model2.step((0.0, 0.05))
+    assert model2.ksp.converged_reason > 0
 
 
 def test_complex_solve_against_scipy():
