@@ -24,6 +24,7 @@ whole, or runs as classes when its columns are few).  SymPy is needed (it is wha
 from __future__ import annotations
 
 import ast
+import copy
 import hashlib
 from pathlib import Path
 
@@ -52,9 +53,16 @@ def _walk(text: str, where: str):
             raise ValueError(f"{where}:{node.lineno}: statement not understood in an .ode file")
 
 
-_EXPR_NODES = (ast.Expression, ast.BinOp, ast.UnaryOp, ast.Call, ast.Name, ast.Constant, ast.Load, ast.Add, ast.Sub, ast.Mult, ast.Div,
-               ast.Pow, ast.USub, ast.UAdd, ast.Compare, ast.Lt, ast.LtE, ast.Gt, ast.GtE, ast.Eq, ast.NotEq, ast.BoolOp, ast.And, ast.Or,
-               ast.Not, ast.IfExp, ast.Mod)
+_EXPR_NODES = (ast.BinOp, ast.UnaryOp, ast.Call, ast.Name, ast.Constant, ast.Load, ast.Add, ast.Sub, ast.Mult, ast.Div, ast.Pow,
+               ast.USub, ast.UAdd, ast.Compare, ast.Lt, ast.LtE, ast.Gt, ast.GtE, ast.Eq, ast.NotEq, ast.BoolOp, ast.And, ast.Or, ast.Not,
+               ast.Mod)
+# What an expression of an .ode file may call (SymPy's function of the same name, but for the two renamed below and Conditional),
+# and the constants it may name besides its states, parameters and intermediates (tests/data/language_cell.ode uses each of them)
+_FUNCTIONS = ("exp", "log", "sqrt", "floor", "abs", "Abs", "pow", "sin", "cos", "tan", "tanh", "sinh", "cosh", "atan", "asin", "acos",
+              "Conditional", "Lt", "Le", "Gt", "Ge", "Eq", "And", "Or", "Not")
+_SYMPY_NAMES = {"abs": "Abs", "pow": "Pow"}
+_CONSTANTS = ("time", "t", "pi")
+_RELATIONS = ("Lt", "Le", "Gt", "Ge", "Eq", "And", "Or", "Not")
 
 
 def _check_expression(node, where: str, known) -> None:
@@ -76,14 +84,48 @@ class _ComparisonsAsNumbers(ast.NodeTransformer):
     """gotran lets a comparison stand in arithmetic as 0 or 1 -- ``gammas*((zetas > 0)*zetas + (zetas < -1)*(-zetas - 1))`` in the
     Land model, ``Gt(Zetas, 0)*Zetas`` in the reference's own file: a comparison (infix or Lt / Le / Gt / Ge / Eq / And / Or / Not)
     that is an operand of an arithmetic operator becomes ``_indicator(comparison)``
-    (Piecewise((1, c), (0, True))); as an argument of Conditional / And / Or / Not it stays a condition."""
+    (Piecewise((1, c), (0, True))); as an argument of Conditional / And / Or / Not it stays a condition.
+
+    Infix forms become the calls first, since Python's own meaning of them on SymPy objects is not gotran's: ``a == b`` and
+    ``a != b`` on a Symbol are a structural test that gives a bool (``Eq`` / ``Not(Eq)`` here), a chained ``a < b <= c`` and
+    ``and`` / ``or`` / ``not`` ask a relation for its truth value (``And`` of the pairs, ``And`` / ``Or`` / ``Not`` here).  The
+    operands of ``and`` / ``or`` / ``not`` must be comparisons: anything else is refused with its line."""
+
+    _OPS = {ast.Lt: "Lt", ast.LtE: "Le", ast.Gt: "Gt", ast.GtE: "Ge", ast.Eq: "Eq", ast.NotEq: "Eq"}
+
+    def __init__(self, where: str):
+        self.where = where
 
     @staticmethod
-    def _wrap(node):
-        relation = isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in ("Lt", "Le", "Gt", "Ge", "Eq", "And", "Or", "Not")
-        if relation or isinstance(node, (ast.Compare, ast.BoolOp)):
-            return ast.copy_location(ast.Call(func=ast.Name(id="_indicator", ctx=ast.Load()), args=[node], keywords=[]), node)
-        return node
+    def _call(name, args, like):
+        return ast.copy_location(ast.Call(func=ast.Name(id=name, ctx=ast.Load()), args=args, keywords=[]), like)
+
+    @staticmethod
+    def _is_relation(node):
+        return isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in _RELATIONS
+
+    def _wrap(self, node):
+        return self._call("_indicator", [node], node) if self._is_relation(node) else node
+
+    def _relations(self, nodes, what, like):
+        for n in nodes:
+            if not self._is_relation(n):
+                raise ValueError(f"{self.where}:{like.lineno}: the operands of `{what}` in an .ode file must be comparisons")
+        return nodes
+
+    def visit_Compare(self, node):
+        self.generic_visit(node)
+        pairs, left = [], node.left
+        for op, right in zip(node.ops, node.comparators):
+            rel = self._call(self._OPS[type(op)], [copy.deepcopy(left), copy.deepcopy(right)], node)
+            pairs.append(self._call("Not", [rel], node) if isinstance(op, ast.NotEq) else rel)
+            left = right
+        return pairs[0] if len(pairs) == 1 else self._call("And", pairs, node)
+
+    def visit_BoolOp(self, node):
+        self.generic_visit(node)
+        what = "and" if isinstance(node.op, ast.And) else "or"
+        return self._call("And" if what == "and" else "Or", self._relations(node.values, what, node), node)
 
     def visit_BinOp(self, node):
         self.generic_visit(node)
@@ -92,8 +134,9 @@ class _ComparisonsAsNumbers(ast.NodeTransformer):
 
     def visit_UnaryOp(self, node):
         self.generic_visit(node)
-        if not isinstance(node.op, ast.Not):
-            node.operand = self._wrap(node.operand)
+        if isinstance(node.op, ast.Not):
+            return self._call("Not", self._relations([node.operand], "not", node), node)
+        node.operand = self._wrap(node.operand)
         return node
 
 
@@ -157,38 +200,32 @@ class OdeFileModel(DeviceModel):
         psym = {p: sympy.Symbol(p, real=True) for p in params}
         tsym, dtsym = sympy.Symbol("time", real=True), sympy.Symbol("dt", real=True)
 
-        def cond(c):
-            return c
-
         def piecewise(c, a, b):
             return sympy.Piecewise((a, c), (b, True))
 
-        ns = {"exp": sympy.exp, "log": sympy.log, "sqrt": sympy.sqrt, "floor": sympy.floor, "abs": sympy.Abs, "Abs": sympy.Abs,
-              "pow": sympy.Pow, "sin": sympy.sin, "cos": sympy.cos, "tan": sympy.tan, "tanh": sympy.tanh, "sinh": sympy.sinh,
-              "cosh": sympy.cosh, "atan": sympy.atan, "asin": sympy.asin, "acos": sympy.acos,
-              "Conditional": piecewise, "Lt": sympy.Lt, "Le": sympy.Le, "Gt": sympy.Gt, "Ge": sympy.Ge, "Eq": sympy.Eq,
-              "And": sympy.And, "Or": sympy.Or, "Not": sympy.Not, "time": tsym, "t": tsym, "pi": sympy.pi,
-              "_indicator": lambda c: sympy.Piecewise((sympy.Integer(1), c), (sympy.Integer(0), True))}
+        ns = {nm: getattr(sympy, _SYMPY_NAMES.get(nm, nm)) for nm in _FUNCTIONS if nm != "Conditional"}
+        ns.update({"Conditional": piecewise, "time": tsym, "t": tsym, "pi": sympy.pi,
+                   "_indicator": lambda c: sympy.Piecewise((sympy.Integer(1), c), (sympy.Integer(0), True))})
         ns.update(psym)
         ns.update(ysym)
-        rhs = {}
-        callables = {k for k, v in ns.items() if callable(v) and not isinstance(v, sympy.Basic)}
+        rhs, line = {}, {}
         for nm, node in assigns:
-            _check_expression(node, str(self.path), callables - {"_indicator"})
-            node = ast.fix_missing_locations(_ComparisonsAsNumbers().visit(node))
+            _check_expression(node, str(self.path), set(_FUNCTIONS))
+            node = ast.fix_missing_locations(_ComparisonsAsNumbers(str(self.path)).visit(node))
             try:
                 expr = sympy.sympify(eval(compile(ast.Expression(node), str(self.path), "eval"), {"__builtins__": {}}, ns))
             except Exception as exc:  # noqa: BLE001
                 raise ValueError(f"{self.path}: cannot turn `{nm} = ...` into an expression: {exc}") from exc
             ns[nm] = expr
             if nm.startswith("d") and nm.endswith("_dt") and nm[1:-3] in states:
-                rhs[nm[1:-3]] = expr
+                rhs[nm[1:-3]], line[nm[1:-3]] = expr, node.lineno
         missing = [s for s in states if s not in rhs]
         if missing:
             raise ValueError(f"{self.path}: no d<state>_dt for {missing}")
         names = list(states)
         f = [rhs[s] for s in names]
-        J = [sympy.diff(rhs[s], ysym[s]) if scheme == "generalized_rush_larsen" else sympy.Integer(0) for s in names]
+        J = [self._self_derivative(rhs[s], ysym[s], f"{self.path}:{line[s]}: d{s}_dt") if scheme == "generalized_rush_larsen"
+             else sympy.Integer(0) for s in names]
         self._grl = [bool(j != 0) for j in J]
         repl, red = sympy.cse(f + J, symbols=sympy.numbered_symbols("x_"), optimizations="basic")
         self._sym = dict(y=[ysym[s] for s in names], p=[psym[p] for p in params], t=tsym, dt=dtsym, repl=repl,
@@ -198,6 +235,21 @@ class OdeFileModel(DeviceModel):
         self._library_id = None   # the id beat_ode_model_register gave (the source is handed over once per process)
         self.source = self._cxx(stem)
         self.key = f"{self.cxx_name}"
+
+    @staticmethod
+    def _self_derivative(expr, y, where: str):
+        """d expr / d y, or a ValueError naming the equation: floor and % have no derivative the generator can print (SymPy
+        leaves ``Derivative(floor(y), y)`` in the result or refuses outright), and none is made up for them here."""
+        import sympy
+
+        try:
+            j = sympy.diff(expr, y)
+        except Exception as exc:  # noqa: BLE001
+            raise ValueError(f"{where}: cannot differentiate with respect to the state {y}: {exc}") from exc
+        if j.has(sympy.Derivative, sympy.Subs):
+            raise ValueError(f"{where}: the derivative with respect to the state {y} is not one the generator can print "
+                             f"({next(iter(j.atoms(sympy.Derivative, sympy.Subs)))}): floor and % of a state have none")
+        return j
 
     # ------------------------------------------------------------------------------------------------ C++
     def _cxx(self, stem: str) -> str:
@@ -216,6 +268,11 @@ class OdeFileModel(DeviceModel):
                     pb = self.parenthesize(b, 1000)
                     return "(1.0/(" + "*".join([pb] * (-int(e))) + "))"
                 return super()._print_Pow(expr)
+
+            def _print_Mod(self, expr):  # Python's %, as NumPy evaluates it (np.mod): the result takes the divisor's sign
+                uses_mod.append(True)
+                a, b = expr.args
+                return f"beat_mod({self._print(a)}, {self._print(b)})"
 
             def _print_Piecewise(self, expr):
                 # BRANCH-FREE: both arms evaluated, the result selected (v_cndmask).  As `c ? a : b` with the arms inline the
@@ -237,6 +294,7 @@ class OdeFileModel(DeviceModel):
         # exp(): the library's table-driven evaluation (FastMath::exp of csrc/ionic_models.h, what the shipped models use: 13 VALU
         # instructions, <= 1 ulp, the 256-entry table in LDS) with the argument kept inside double range -- or libm's
         exp_name = "fexp" if self.fast_exp else "exp"
+        uses_mod = []
         pr = Printer({"contract": False, "user_functions": {"exp": exp_name}})
         y, p = self._sym["y"], self._sym["p"]
         sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
@@ -310,6 +368,11 @@ class OdeFileModel(DeviceModel):
                    "    // overflows to inf as libm does; the clamp turns a NaN argument into a number, hence the select)\n"
                    "    const auto fexp = [&fm](double x) { const double e = fm.exp(fmin(fmax(x, -1.0e6), 1.0e3)); return x != x ? x : e; };\n" if self.fast_exp else "")
                 + "    const auto beat_sel = [](bool c, double a, double b) { return c ? a : b; };\n"
+                + ("    // (a % b with Python's and NumPy's meaning: fmod's result moved by b where it has the other sign; a zero takes b's sign)\n"
+                   "    const auto beat_mod = [](double a, double b) {\n"
+                   "      const double m = fmod(a, b);\n"
+                   "      return m != 0.0 ? ((m < 0.0) != (b < 0.0) ? m + b : m) : copysign(0.0, b);\n"
+                   "    };\n" if uses_mod else "")
                 + "\n".join(loads + pl + lines + body) + "\n  }\n};\n")
 
     # ------------------------------------------------------------------------------------------------ NumPy

@@ -141,3 +141,16 @@ def test_ode_expressions_are_data_not_code(tmp_path):
     f.write_text(text.replace("dn_dt =", "gate_on = (V > -60)*1.0 + Lt(V, -100)*2.0\ndn_dt = 0*gate_on +"))
     m = from_ode(f)
     assert m.num_states == 5 and np.isfinite(m.numpy_step(m.init_state_values(), 0.0, m.init_parameter_values(), 0.01)).all()
+    # ... and its value is 0 or 1 by the comparison, for every infix operator (== and != on a SymPy symbol used to be Python's
+    # structural test: a constant False / True whatever the potential) and in a chained comparison
+    f = tmp_path / "ind_values.ode"
+    f.write_text('states("S", V = -70.0, g = 0.0)\nexpressions("S")\ndV_dt = 0\n'
+                 'dg_dt = ((V > -60)*1.0 + Lt(V, -100)*2.0 + (V == -70)*4.0 + (V != -80)*8.0 + (V <= -80)*16.0 + (V >= 0)*32.0\n'
+                 '         + (V < -90)*64.0 + (-100 <= V < -60)*128.0)\n')
+    m = from_ode(f, scheme="forward_euler")
+    V = np.array([-120.0, -100.0, -90.0, -80.0, -70.0, -60.0, 0.0, 30.0])
+    want = ((V > -60) * 1.0 + (V < -100) * 2.0 + (V == -70) * 4.0 + (V != -80) * 8.0 + (V <= -80) * 16.0 + (V >= 0) * 32.0
+            + (V < -90) * 64.0 + ((-100 <= V) & (V < -60)) * 128.0)
+    got = m.numpy_step(np.vstack([V, np.zeros_like(V)]), 0.0, m.init_parameter_values(), 1.0)
+    np.testing.assert_array_equal(got[1], want)
+    np.testing.assert_array_equal(got[0], V)
