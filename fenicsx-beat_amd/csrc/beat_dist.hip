@@ -821,21 +821,19 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
   double *r = w.r, *q = w.q, *ring = w.ring;
   const int PR = pde->ring;     // (6 on a decomposed grid; a one-rank communicator on a single slab of per-node rows: 12)
   double* st = pde->d_st;
-  double* dev_x = o.x;
-  double* rbuf[2] = {r, q};  // rr: the residual update writes out of place
+  double* rbuf[2] = {r, q};
   const bool rr = o.rr, merged = o.merged, vpdot = o.vpdot;
   int rc;
   for (int it = 0; it < count; ++it) {
     const int i = o.launched + it, slot = i % PR;
     double* p_cur = ring + (int64_t)slot * fld;
     double* p_next = ring + (int64_t)((i + 1) % PR) * fld;
+    const double* p_old = ring + (int64_t)((i + PR - 1) % PR) * fld;
+    double *r_cur = rbuf[i & 1], *r_new = rbuf[(i + 1) & 1];  // (rr: the residual update writes out of place)
     if (merged) {
       // u_i . A u_i, r_i . u_i, r_i . r_i in one pass over r_i (interior planes while its ghost planes travel, then the
       // boundary planes), ONE all-reduce, the scalar step (stopping test, beta_i, alpha_i), then p_i = u_i + beta_i p_{i-1}
       // and r_{i+1} = r_i - alpha_i A p_i in one pass without a dot product; the ghost planes of r_{i+1} travel behind it
-      const double* p_old = ring + (int64_t)((i + PR - 1) % PR) * fld;
-      double* r_cur = rbuf[i & 1];
-      double* r_new = rbuf[(i + 1) & 1];
       if ((rc = beat_rr_udot_part(pde, st, r_cur, 0))) return rc;
       if ((rc = halo_wait(comm))) return rc;
       if ((rc = beat_rr_udot_part(pde, st, r_cur, 1))) return rc;
@@ -843,18 +841,12 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = beat_rr_merged_next(pde, st, slot))) return rc;
       if ((rc = beat_rr_prupd(pde, st, r_cur, p_old, p_cur, r_new))) return rc;
       if ((rc = halo_start(comm, r_new, n, plane))) return rc;
-      if (slot == PR - 1) {
-        if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR))))
-          return rc;
-      }
+      if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
       continue;
     }
     if (rr) {
       // p_i = D^-1 r_i + beta p_{i-1} and p_i . A p_i: the planes that need no ghost data while the ghost planes of
       // r_i travel, then the boundary planes, which also keep p_i on the ghost planes (no exchange of p)
-      const double* p_old = ring + (int64_t)((i + PR - 1) % PR) * fld;
-      double* r_cur = rbuf[i & 1];
-      double* r_new = rbuf[(i + 1) & 1];
       if ((rc = beat_rr_pdot_part(pde, st, r_cur, p_old, p_cur, 0))) return rc;
       if ((rc = halo_wait(comm))) return rc;
       if ((rc = beat_rr_pdot_part(pde, st, r_cur, p_old, p_cur, 1))) return rc;
@@ -862,10 +854,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = beat_rr_rupd(pde, st, r_cur, r_new, p_cur, slot, false))) return rc;  // r_{i+1}, local r.z and r.r
       if ((rc = halo_start(comm, r_new, n, plane))) return rc;  // travels behind the reductions and the next part 0
       if ((rc = allreduce_sum(comm, st + RZN, 2))) return rc;
-      if (slot == PR - 1) {
-        if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR))))
-          return rc;
-      }
+      if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
       if ((rc = beat_rr_next(pde, st))) return rc;
       continue;
     }
@@ -873,7 +862,6 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       // p_i = D^-1 r_i + beta p_{i-1}, q = A p_i and p_i . q in one pass over the coefficient rows: the tiles that need no ghost
       // plane while the ghost planes of r_i travel, then the boundary tiles (which keep p_i on the ghost planes); the residual
       // update in place, its ghost planes travelling behind the second reduction and the next pass's first part
-      const double* p_old = ring + (int64_t)((i + PR - 1) % PR) * fld;
       if ((rc = beat_vtl_pdot_part(pde, st, r, p_old, p_cur, q, i == 0, 0))) return rc;
       if ((rc = halo_wait(comm))) return rc;
       if ((rc = beat_vtl_pdot_part(pde, st, r, p_old, p_cur, q, i == 0, 1))) return rc;
@@ -881,10 +869,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = beat_pde_cg_update_r(pde, st, r, q, slot))) return rc;
       if ((rc = halo_start(comm, r, n, plane))) return rc;
       if ((rc = allreduce_sum(comm, st + RZN, 2))) return rc;
-      if (slot == PR - 1) {
-        if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR))))
-          return rc;
-      }
+      if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
       if ((rc = beat_rr_next(pde, st))) return rc;  // the scalar roll (beta, iteration count, latch)
       continue;
     }
@@ -895,10 +880,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
     if ((rc = allreduce_sum(comm, st + PQ, 1))) return rc;
     if ((rc = beat_pde_cg_update_r(pde, st, r, q, slot))) return rc;
     if ((rc = allreduce_sum(comm, st + RZN, 2))) return rc;
-    if (slot == PR - 1) {
-      if ((rc = beat_pde_x_flush_terms(pde, st, dev_x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR))))
-        return rc;
-    }
+    if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
     if ((rc = beat_pde_cg_next_oop(pde, st, r, p_cur, p_next))) return rc;
   }
   o.launched += count;
@@ -947,29 +929,18 @@ int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_pr
     const char* e = std::getenv("BEAT_DIST_RHS_SPLIT");
     return !(e && e[0] == '0');
   }();
-  if (rr) {
-    if (split_rhs) {
-      if ((rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st, 0))) return rc;
-      if ((rc = halo_wait(comm))) return rc;
-      rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st, 1);
-    } else {
-      if ((rc = halo_wait(comm))) return rc;
-      rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st);
-    }
-  } else if (pde->var) {
+  auto rhs = [&](int part) {  // (the start of the solve follows the all-reduce of the sums: no PcgStart)
+    if (rr) return beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st, part);
     const double* e = pde->guess.use_e ? pde->guess.e : nullptr;
-    if (split_rhs) {
-      if ((rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, e, 0))) return rc;
-      if ((rc = halo_wait(comm))) return rc;
-      rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, e, 1);
-    } else {
-      if ((rc = halo_wait(comm))) return rc;
-      rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, e);
-    }
-  } else {
-    if ((rc = halo_wait(comm))) return rc;
+    return beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, e, part);
+  };
+  const bool parts = rr || pde->var;  // (else the tiled stage kernels' right-hand side: one launch behind the exchange)
+  if (parts && split_rhs && (rc = rhs(0))) return rc;
+  if ((rc = halo_wait(comm))) return rc;
+  if (parts)
+    rc = rhs(split_rhs ? 1 : -1);
+  else
     rc = beat_pde_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st);
-  }
   if (rc) return rc;
   if ((rc = allreduce_sum(comm, st + BB, 3))) return rc;
   if ((rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;

@@ -308,10 +308,7 @@ __global__ __launch_bounds__(BEAT_BLOCK) void stencil_kernel(Geom g, StencilArgs
   }
 }
 
-// Sum `count` block partials of `nsum` quantities in a fixed order and store them at out[0..nsum).
-// `then` (round 5: one launch instead of two behind a residual update / a right-hand side on a single slab; the same arithmetic in the
-// same order as the kernels it replaces): 1 = the scalar roll of the iteration (pcg_next_kernel: beta, iteration count, latch) on the
-// state `roll_st` the sums were just written into; 2 = the start of a solve (pcg_begin_kernel) with rtol / atol / max_it.
+// The scalar steps of the PCG (each also a kernel of its own below; the reduction runs them behind its sums, see reduce_partials_kernel)
 __device__ __forceinline__ void beat_pcg_roll(double* st) {
   st[BETA] = st[RZN] / st[RZ];
   st[RZ] = st[RZN];
@@ -342,7 +339,7 @@ __device__ __forceinline__ void beat_pcg_begin(double* st, double rtol, double a
   st[STOP] = done ? 1.0 : 0.0;
   st[REASON] = done ? (rr <= tr ? 2.0 : 3.0) : 0.0;
 }
-// 3 = the predicted stop behind PDOT (beat_rr_pdot with a ring slot), with st[PQS..QQ] = p.q, r.q, q.q just summed (q = A p_i, r = r_i):
+// The predicted stop behind PDOT (beat_rr_pdot with a ring slot), with st[PQS..QQ] = p.q, r.q, q.q just summed (q = A p_i, r = r_i):
 //   r_{i+1} . r_{i+1} = RR - 2 alpha (r.q) + alpha^2 (q.q)   in exact arithmetic, alpha = RZ / PQ.
 // The prediction rho feeds no iterate: it only gates the stop.  E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds |rho - what the residual
 // update's reduction would compute| (c: beat_rr_predict_bound).  When rho + E settles the stopping test and its reason (and rho is
@@ -370,6 +367,10 @@ __device__ __forceinline__ void beat_pcg_predict(double* st, double* alpha_slot,
   st[REASON] = reason;
   st[STOP] = 1.0;
 }
+// Sum `count` block partials of `nsum` quantities in a fixed order and store them at out[0..nsum); then, in the same launch (round 5:
+// one launch instead of two; the same arithmetic in the same order as the kernels it replaces), the scalar step `then` (ScalarStep::Kind)
+// on the state `roll_st` the sums were just written into: 0 = none, 1 = the iteration's roll (pcg_next_kernel: beta, iteration count,
+// latch), 2 = the start of a solve (pcg_begin_kernel) with rtol / atol / max_it, 3 = the predicted stop (pcg_predict_kernel).
 __global__ __launch_bounds__(BEAT_BLOCK) void reduce_partials_kernel(const double* __restrict__ partials, int count, int nsum, double* out,
                                                                      const double* st, double* counter, int then, double* roll_st,
                                                                      double rtol, double atol, double max_it, double* alpha_slot,
@@ -797,22 +798,32 @@ extern "C" int beat_pde_apply(beat_pde* pde, int which, const double* dev_x, dou
   return BEAT_OK;
 }
 
-int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, double* counter, int then, double* roll_st,
-                           double rtol, double atol, int max_it, double* alpha_slot, double bound_c) {
+int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, const ScalarStep& step) {
   static const bool fuse = [] {  // BEAT_PCG_FUSE=0: the scalar step in a launch of its own, as before round 5 (A/B runs)
     const char* e = std::getenv("BEAT_PCG_FUSE");
     return !(e && e[0] == '0');
   }();
-  BEAT_KERNEL(reduce_partials_kernel, dim3(1), dim3(BEAT_BLOCK), 0, pde->ctx->stream, (const double*)pde->ctx->d_partials, count, nsum, out, st,
-              counter, fuse ? then : 0, roll_st, rtol, atol, (double)max_it, alpha_slot, bound_c);
+  hipStream_t s = pde->ctx->stream;
+  BEAT_KERNEL(reduce_partials_kernel, dim3(1), dim3(BEAT_BLOCK), 0, s, (const double*)pde->ctx->d_partials, count, nsum, out, st, step.counter,
+              fuse ? (int)step.kind : 0, step.st, step.rtol, step.atol, (double)step.max_it, step.alpha_slot, step.bound_c);
   BEAT_LAUNCH_CHECK();
-  if (then != 0 && !fuse) {
-    if (then == 1) BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st);
-    else if (then == 3) BEAT_KERNEL(pcg_predict_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st, alpha_slot, bound_c);
-    else BEAT_KERNEL(pcg_begin_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, roll_st, rtol, atol, (double)max_it);
+  if (step.kind != ScalarStep::NONE && !fuse) {
+    if (step.kind == ScalarStep::ROLL) BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, s, step.st);
+    else if (step.kind == ScalarStep::PREDICT) BEAT_KERNEL(pcg_predict_kernel, dim3(1), dim3(1), 0, s, step.st, step.alpha_slot, step.bound_c);
+    else BEAT_KERNEL(pcg_begin_kernel, dim3(1), dim3(1), 0, s, step.st, step.rtol, step.atol, (double)step.max_it);
     BEAT_LAUNCH_CHECK();
   }
   return BEAT_OK;
+}
+
+// q = A p with the block partials of p.q: the arguments every pass over operator A starts from
+static StencilArgs stencil_operator_args(const beat_pde* pde, const double* dev_st) {
+  StencilArgs a{};
+  a.tab = pde->d_tab(0);
+  a.ci = interior(pde->h_A);
+  a.partials = pde->ctx->d_partials;
+  a.st = dev_st;
+  return a;
 }
 
 extern "C" int beat_pde_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w,
@@ -840,13 +851,7 @@ extern "C" int beat_pde_rhs(beat_pde* pde, const double* dev_v_prev, const doubl
   a.cm = pde->C_m;
   a.omt_dt = (1.0 - pde->theta) * pde->dt;
   a.dt = pde->dt;
-  a.nstim = 0;
-  for (int k = 0; k < n_stim; ++k) {
-    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
-    a.w[a.nstim] = host_dev_stim_w[k];
-    a.amp[a.nstim] = host_stim_amp[k];
-    ++a.nstim;
-  }
+  beat_fill_stimuli(a, host_dev_stim_w, host_stim_amp, n_stim);
   a.partials = pde->ctx->d_partials;
   launch_stencil<MODE_RHS>(pde, a);
   BEAT_LAUNCH_CHECK();
@@ -865,13 +870,9 @@ extern "C" int beat_pde_spmv_dot(beat_pde* pde, const double* dev_p, double* dev
   BEAT_REQUIRE(pde != nullptr && dev_p && dev_q && dev_st, "null argument");
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   if (pde->var) return beat_var_spmv_dot(pde, dev_p, dev_q, dev_st);
-  StencilArgs a{};
+  StencilArgs a = stencil_operator_args(pde, dev_st);
   a.x = dev_p;
   a.y = dev_q;
-  a.tab = pde->d_tab(0);
-  a.ci = interior(pde->h_A);
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
   launch_stencil<MODE_SPMV_DOT>(pde, a);
   BEAT_LAUNCH_CHECK();
   return beat_pde_launch_reduce(pde, pde->g.total, 1, dev_st + PQ, dev_st);
@@ -882,35 +883,17 @@ extern "C" int beat_pde_spmv_dot_part(beat_pde* pde, const double* dev_p, double
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   BEAT_REQUIRE(part == 0 || part == 1, "part must be 0 (interior) or 1 (boundary planes + reduce)");
   if (pde->var) return beat_var_spmv_dot_part(pde, dev_p, dev_q, dev_st, part);
-  const Geom& f = pde->g;
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);  // planes that need no ghost data
-  StencilArgs a{};
+  StencilArgs a = stencil_operator_args(pde, dev_st);
   a.x = dev_p;
   a.y = dev_q;
-  a.tab = pde->d_tab(0);
-  a.ci = interior(pde->h_A);
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
-  const Geom gi = range_geom(f, lo, std::max(lo, hi), 0);
-  if (part == 0) {
-    launch_stencil<MODE_SPMV_DOT>(pde, a, &gi);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = gi.total;
-  if (!f.z_lo_phys) {
-    const Geom gb = range_geom(f, 0, 1, off);
-    launch_stencil<MODE_SPMV_DOT>(pde, a, &gb);
-    off += gb.total;
-  }
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) {
-    const Geom gb = range_geom(f, f.nz - 1, f.nz, off);
-    launch_stencil<MODE_SPMV_DOT>(pde, a, &gb);
-    off += gb.total;
-  }
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
-  return beat_pde_launch_reduce(pde, off, 1, dev_st + PQ, dev_st);
+  int count = 0;
+  auto launch = [&](int z_lo, int z_hi, int part_off) {
+    const Geom g = range_geom(pde->g, z_lo, z_hi, part_off);
+    launch_stencil<MODE_SPMV_DOT>(pde, a, &g);
+    return g.total;
+  };
+  if (int rc = beat_launch_parts(pde, PASS_SPMV, part, launch, &count)) return rc;
+  return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 1, dev_st + PQ, dev_st);
 }
 
 extern "C" int beat_pde_cg_update(beat_pde* pde, double* dev_st, double* dev_x, double* dev_r,
@@ -947,16 +930,12 @@ extern "C" int beat_pde_pc_pass(beat_pde* pde, int j, const double* dev_r, doubl
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   // outputs alternate and end in z: pass j writes z if (npass - 1 - j) is even, else q
   auto out_of = [&](int jj) { return ((npass - 1 - jj) % 2 == 0) ? dev_z : dev_q; };
-  StencilArgs a{};
+  StencilArgs a = stencil_operator_args(pde, dev_st);
   a.x = (j == 0) ? dev_r : out_of(j - 1);
   a.x2 = dev_r;
   a.y = out_of(j);
-  a.tab = pde->d_tab(0);
   a.dinv = pde->d_dinv();
   a.dinv_i = pde->h_dinv[13];
-  a.ci = interior(pde->h_A);
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
   a.pc_first = (j == 0);
   a.pc_last = (j == npass - 1);
   a.c_in = pde->pc_coef[npass];          // highest coefficient scales the first staged input
@@ -1032,7 +1011,7 @@ extern "C" int beat_pde_cg_update_r(beat_pde* pde, double* dev_st, double* dev_r
                      (const double*)dev_st, dev_r, dev_q, pde->dinv_arg(), pde->h_dinv[13], pde->ctx->d_partials,
                      pde->d_alphas, slot);
   BEAT_LAUNCH_CHECK();
-  return beat_pde_launch_reduce(pde, (int)pde->vec_grid, 2, dev_st + RZN, dev_st, dev_st + NUPD);
+  return beat_pde_launch_reduce(pde, (int)pde->vec_grid, 2, dev_st + RZN, dev_st, ScalarStep::after_update(dev_st, false));
 }
 
 // scalar roll (beta, latch, iteration count) then p_next = D^-1 r + beta p_cur
@@ -1304,6 +1283,14 @@ bool beat_solve_lazy_available(const beat_pde* pde) {
          (beat_rr_available(pde) || pde->var);
 }
 
+// Behind iteration i of a deferred-x loop: when it filled the ring, x is brought up to date before slot 0 is overwritten
+int beat_flush_if_ring_full(beat_pde* pde, int i) {
+  const int PR = pde->ring;
+  if (i % PR != PR - 1) return BEAT_OK;
+  const PcgWork w = beat_pcg_work(pde, pde->open.work);
+  return beat_pde_x_flush_terms(pde, pde->d_st, pde->open.x, w.ring, w.fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR));
+}
+
 // `count` more iterations of the open solve, enqueued
 static int solve_enqueue_iterations(beat_pde* pde, int count) {
   beat_pde::OpenSolve& o = pde->open;
@@ -1334,9 +1321,7 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
       double* rbuf[2] = {r, q};
       if ((rc = beat_rr_pdot(pde, st, rbuf[i & 1], p_old, p_cur, slot))) return rc;
       if ((rc = beat_rr_rupd(pde, st, rbuf[i & 1], rbuf[(i + 1) & 1], p_cur, slot))) return rc;
-      if (slot == PR - 1) {  // ring full: bring x up to date before slot 0 is overwritten
-        if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR)))) return rc;
-      }
+      if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
     } else {
       // per-node rows (round 4) or the LDS-tiled constant-coefficient kernels, deferred x: iteration i uses p_i = ring[i % PR].  With
       // o.pdot (per-node rows) the tile kernel forms p_i = D^-1 r + beta p_{i-1} while loading, stores it and q = A p_i in the same
@@ -1350,9 +1335,7 @@ static int solve_enqueue_iterations(beat_pde* pde, int count) {
       // (with the fused pass the scalar roll -- beta for the next pass, the latch, the iteration count -- runs in the launch that sums
       // the residual update's partials; the x update, when the ring is full, reads the update count only and may follow it)
       if ((rc = o.pdot ? beat_var_update_r(pde, st, r, q, slot, true) : beat_pde_cg_update_r(pde, st, r, q, slot))) return rc;
-      if (slot == PR - 1) {  // ring full: bring x up to date before slot 0 is overwritten
-        if ((rc = beat_pde_x_flush_terms(pde, st, o.x, ring, fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR)))) return rc;
-      }
+      if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
       if (!o.pdot && (rc = beat_pde_cg_next_oop(pde, st, r, p_cur, p_next))) return rc;
     }
   }
@@ -1405,19 +1388,17 @@ static int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const doubl
     return beat_solve_open(pde, o);
   }
   beat_guess_begin(pde);
-  pde->fuse_begin = beat_pde::FuseBegin{true, false, rtol, atol, max_it};
+  const PcgStart start{rtol, atol, max_it};  // (the register-row and the tile right-hand sides run it in the launch that sums their partials)
+  const double* e = pde->guess.use_e ? pde->guess.e : nullptr;
   if (o.kind == SOLVE_RR) {
-    rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, st);
+    rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, st, -1, &start);
   } else if (beat_vtl_rhs_available(pde)) {  // two tile passes (b = B v_ + dt stim, r = b - A (v_ + e)); q is free until iteration 0
-    rc = beat_vtl_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, w.q, st,
-                      pde->guess.use_e ? pde->guess.e : nullptr);
-  } else {  // the gather kernel: the guess increment e next to v_
-    rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, st, pde->guess.use_e ? pde->guess.e : nullptr);
+    rc = beat_vtl_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, w.q, st, e, &start);
+  } else {  // the gather kernel: the guess increment e next to v_; the start of the solve in a launch of its own
+    if ((rc = beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, st, e))) return rc;
+    rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it);
   }
-  const bool begun = pde->fuse_begin.done;  // (the right-hand side's reduction has run the start of the solve in its own launch)
-  pde->fuse_begin.on = false;
   if (rc) return rc;
-  if (!begun && (rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;
   return beat_solve_open(pde, o);
 }
 

@@ -3,6 +3,7 @@
 //   beat_pde_var.hip  per-node-coefficient operators, device-side row assembly, Dirichlet elimination
 #pragma once
 #include "beat_common.h"
+#include "beat_slab_parts.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -46,6 +47,9 @@ enum SolveKind {
   SOLVE_DIST     // a decomposed solve (beat_dist.hip; OpenSolve::rr / merged / vpdot say which of its loops runs)
 };
 
+// The passes that run in the two parts of beat_slab_parts.h (beat_pde::Part0::pass: which of them wrote part 0's block partials)
+enum PartPass { PASS_NONE = 0, PASS_SPMV, PASS_RR_RHS, PASS_RR_PDOT, PASS_RR_UDOT, PASS_VAR_RHS, PASS_VAR_SPMV, PASS_VRR_SPMV };
+
 }  // namespace beat_pde_detail
 
 struct beat_pde {
@@ -79,13 +83,11 @@ struct beat_pde {
     void* comm = nullptr;
     bool rr = false, merged = false, vpdot = false;
   } open;
-  // set by beat_solve_begin around its right-hand side: the start of the solve (pcg_begin_kernel's step) is to run in the launch that
-  // sums the right-hand side's partials; `done` says a right-hand side took it up
-  struct FuseBegin {
-    bool on = false, done = false;
-    double rtol = 0.0, atol = 0.0;
-    int max_it = 0;
-  } fuse_begin;
+  // part 0 of a pass in two parts (beat_launch_parts): the block partials it wrote, for the part 1 of the same pass that follows it
+  struct Part0 {
+    int pass = beat_pde_detail::PASS_NONE;
+    int blocks = 0;
+  } part0;
   double* h_st = nullptr;       // pinned copy of the scalar state of the open solve (16 doubles)
   hipEvent_t ev_st = nullptr;   // recorded behind that copy
   beat_ksp_info last_info{};    // of the last solve that was finished
@@ -126,9 +128,7 @@ struct beat_pde {
   beat_pde_detail::GuessTerms guess{};     // terms of the solve in progress (out == nullptr: not in use)
   bool guess_pending = false;              // the last solve left x += e + sum alpha_j p_j to its caller ...
   beat_pde_detail::GuessTerms guess_final{};  // ... with these terms
-  int rhs_part_blocks = 0;  // block partials written by part 0 of a right-hand side built in two parts
   void* vrr = nullptr;      // work lists of the z-marching per-node SpMV (beat_pde_vrr.hip), or nullptr
-  int vrr_part_blocks = 0;
   void* vtl = nullptr;      // tiles and lane masks of the workgroup-tile per-node SpMV (beat_pde_vtl.hip), or nullptr
   bool small_enabled = true;  // grids of a few thousand nodes: whole solve in one launch (beat_pde_small.hip)
   int pc_ncoef = 1;       // 1: Jacobi; m >= 2: Chebyshev polynomial of degree m-1 in D^-1 A (m-1 stencil passes)
@@ -182,12 +182,76 @@ inline int beat_pde_first_chunk(const beat_pde* pde) {
   return pde->last_iters >= 0 ? std::max(1, pde->last_iters + extra) : 8;
 }
 
-// fixed-order sum of `count` block partials of `nsum` quantities into out[0..nsum) (beat_pde.hip)
-// then / roll_st / rtol / atol / max_it: the scalar step that follows the sums, in the same launch (1: the iteration's roll, 2: the start of a solve)
-// (3: the predicted stop behind PDOT, beat_pcg_predict: alpha_slot = the ring slot's step length, bound_c = beat_rr_predict_bound)
-int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, double* counter = nullptr, int then = 0,
-                           double* roll_st = nullptr, double rtol = 0.0, double atol = 0.0, int max_it = 0, double* alpha_slot = nullptr,
-                           double bound_c = 0.0);
+// What a solve starts with (pcg_begin_kernel's step).  A right-hand side that is given one runs the start in the launch that sums its
+// partials; nullptr: the caller starts the solve itself (a decomposed solve: the all-reduce sits between the sums and the start)
+struct PcgStart {
+  double rtol, atol;
+  int max_it;
+};
+
+// The scalar step that follows a reduction's sums, in the same launch (BEAT_PCG_FUSE=0: in a launch of its own behind it)
+struct ScalarStep {
+  enum Kind { NONE = 0, ROLL, BEGIN, PREDICT };  // (the values of reduce_partials_kernel's `then`)
+  Kind kind = NONE;
+  double* st = nullptr;       // the scalar state the step works on: the one the sums were just written into
+  double* counter = nullptr;  // any kind: counts the executed residual update (st + NUPD) when the reduction is not latched
+  double rtol = 0.0, atol = 0.0;  // BEGIN: the start of a solve
+  int max_it = 0;
+  double* alpha_slot = nullptr;  // PREDICT (the predicted stop behind PDOT, beat_pcg_predict): the ring slot's step length ...
+  double bound_c = 0.0;          // ... and beat_rr_predict_bound
+  // behind a deferred-x residual update: counts it and, with `roll`, rolls the iteration (beta, iteration count, latch)
+  static ScalarStep after_update(double* st, bool roll) { return {roll ? ROLL : NONE, st, st + beat_pde_detail::NUPD}; }
+  static ScalarStep begin(double* st, const PcgStart* s) {
+    return s ? ScalarStep{BEGIN, st, nullptr, s->rtol, s->atol, s->max_it} : ScalarStep{};
+  }
+};
+// fixed-order sum of `count` block partials of `nsum` quantities into out[0..nsum), skipped when st[STOP] is set (st may be nullptr);
+// then `step` (beat_pde.hip)
+int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, const ScalarStep& step = {});
+
+// The hand-off between the two parts of a pass: part 0 puts its block count under the pass's name, the part 1 that follows takes it
+// (once) and must be of the same pass
+inline void beat_part0_put(beat_pde* pde, int pass, int blocks) { pde->part0 = {pass, blocks}; }
+inline int beat_part0_take(beat_pde* pde, int pass, int* blocks) {
+  BEAT_REQUIRE(pde->part0.pass == pass, "part 1 of a pass must follow part 0 of the same pass");
+  *blocks = pde->part0.blocks;
+  pde->part0 = {};
+  return BEAT_OK;
+}
+
+inline beat_pde_detail::SlabPart beat_slab_part(const beat_pde* pde, int part) {
+  return beat_pde_detail::beat_slab_part(pde->g.nz, pde->g.z_lo_phys != 0, pde->g.z_hi_phys != 0, part);
+}
+
+// A pass in the parts of beat_slab_parts.h.  launch(z_lo, z_hi, part_off) enqueues the pass on planes [z_lo, z_hi) with its block
+// partials from slot part_off on and returns how many it writes.  Part 0 leaves its count in pde->part0 under the pass's name; part 1
+// must follow the part 0 of the same pass and continues from that count: the slots are interior, lower plane, upper plane, the order
+// the fixed-order sums have always had.  *reduce_count = the partials to sum (parts -1 and 1; part 0 sums nothing: 0).
+template <class Launch>
+int beat_launch_parts(beat_pde* pde, int pass, int part, Launch&& launch, int* reduce_count) {
+  const beat_pde_detail::SlabPart sp = beat_slab_part(pde, part);
+  int off = 0;
+  if (part == 1)
+    if (int rc = beat_part0_take(pde, pass, &off)) return rc;
+  for (int k = 0; k < sp.count; ++k) off += launch(sp.range[k].z_lo, sp.range[k].z_hi, off);
+  BEAT_LAUNCH_CHECK();
+  if (part == 0) beat_part0_put(pde, pass, off);
+  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
+  *reduce_count = part == 0 ? 0 : off;
+  return BEAT_OK;
+}
+
+// the stimuli a right-hand side adds: those with a weight field and a non-zero amplitude, in the caller's order
+template <class Args>
+void beat_fill_stimuli(Args& a, const double* const* host_dev_stim_w, const double* host_stim_amp, int n_stim) {
+  a.nstim = 0;
+  for (int k = 0; k < n_stim; ++k) {
+    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
+    a.w[a.nstim] = host_dev_stim_w[k];
+    a.amp[a.nstim] = host_stim_amp[k];
+    ++a.nstim;
+  }
+}
 
 // per-node-coefficient variants of the stage operations (beat_pde_var.hip); same contracts as the beat_pde_*
 // entry points that dispatch to them
@@ -214,6 +278,8 @@ beat_pde_detail::GuessTerms beat_guess_terms(const beat_pde* pde, int ring_base)
 bool beat_guess_end(beat_pde* pde, int nupd, bool deferred);
 int beat_pde_x_flush_terms(beat_pde* pde, const double* dev_st, double* dev_x, const double* dev_ring0, int64_t field_stride,
                            int ring_base, int only_if_full, const beat_pde_detail::GuessTerms& gt);
+// behind iteration i of the open solve's deferred-x loop: the x update above when that iteration filled the ring, else nothing
+int beat_flush_if_ring_full(beat_pde* pde, int i);
 
 void beat_guess_advance(beat_pde* pde);
 void beat_guess_observe(beat_pde* pde, int iterations);  // of the solve that just ended (adaptive order)
@@ -240,7 +306,7 @@ bool beat_vtl_pdot_available(const beat_pde* pde);
 bool beat_vtl_rhs_available(const beat_pde* pde);
 bool beat_vtl_rhs_wanted(const beat_pde* pde);
 int beat_vtl_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp, int n_stim,
-                 double* dev_x, double* dev_r, double* dev_p, double* dev_t, double* dev_red, const double* dev_e);
+                 double* dev_x, double* dev_r, double* dev_p, double* dev_t, double* dev_red, const double* dev_e, const PcgStart* start);
 int beat_vtl_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, double* dev_q, int first);
 
 // The multi-launch solves in two halves.  beat_solve_open (beat_pde.hip), called by a begin once its right-hand side and start are
@@ -276,7 +342,8 @@ int beat_small_solve(beat_pde* pde, const double* dev_v_prev, const double* cons
 // register-row kernels of the constant-coefficient Jacobi-PCG that never stores q = A p (beat_pde_rr.hip)
 bool beat_rr_available(const beat_pde* pde);
 int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
-                int n_stim, double* dev_x, double* dev_r, double* dev_st, int part = -1);  // part: as beat_var_rhs
+                int n_stim, double* dev_x, double* dev_r, double* dev_st, int part = -1,  // part: as beat_var_rhs
+                const PcgStart* start = nullptr);  // part -1 only: the start of the solve behind the sums
 // slot >= 0: the single-slab loop's pass, which predicts the stop when the operator was created with it on (see beat_rr_pdot_part)
 int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, int slot = -1);
 int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,

@@ -743,11 +743,24 @@ RGeom make_geom(const beat_pde* pde, int z_lo, int z_hi, int part_off, int rows 
 RGeom make_geom(const beat_pde* pde) { return make_geom(pde, 0, pde->g.nz, 0); }
 
 inline int grid_blocks(const RGeom& g) { return ((g.total_blocks + 7) / 8) * 8; }
+inline int blocks_written(const RGeom& g) { return g.total_blocks > 0 ? grid_blocks(g) : 0; }  // (launch_rr skips an empty range)
 
 Coef interior_row(const double* tab) {
   Coef c;
   for (int k = 0; k < 15; ++k) c.c[k] = tab[13 * 15 + k];
   return c;
+}
+
+// the arguments every pass over operator A starts from (Jacobi: 1 / diag(A) beside it)
+RArgs rr_operator_args(const beat_pde* pde, double* dev_st) {
+  RArgs a{};
+  a.tab = pde->d_tab(0);
+  a.dinv = pde->d_dinv();
+  a.ci = interior_row(pde->h_A);
+  a.dinv_i = pde->h_dinv[13];
+  a.partials = pde->ctx->d_partials;
+  a.st = dev_st;
+  return a;
 }
 
 template <int MODE, bool GUESS = false, bool PRED = false>
@@ -779,7 +792,8 @@ bool beat_rr_available(const beat_pde* pde) {
 
 // Right-hand side in residual form (see beat_pde_rhs) without the p output.
 int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
-                int n_stim, double* dev_x, double* dev_r, double* dev_st, int part) {
+                int n_stim, double* dev_x, double* dev_r, double* dev_st, int part, const PcgStart* start) {
+  BEAT_REQUIRE(start == nullptr || part < 0, "only a right-hand side in one part starts the solve");
   const GuessTerms& gt = pde->guess;
   const bool guess = gt.d != nullptr && gt.use_e;
   // with a guess the kernel holds two register windows (v_ and e): 2 rows per wave keep it at the other kernels' occupancy
@@ -802,13 +816,7 @@ int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* ho
   a.cm = pde->C_m;
   a.omt_dt = (1.0 - pde->theta) * pde->dt;
   a.dt = pde->dt;
-  a.nstim = 0;
-  for (int k = 0; k < n_stim; ++k) {
-    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
-    a.w[a.nstim] = host_dev_stim_w[k];
-    a.amp[a.nstim] = host_stim_amp[k];
-    ++a.nstim;
-  }
+  beat_fill_stimuli(a, host_dev_stim_w, host_stim_amp, n_stim);
   a.partials = pde->ctx->d_partials;
   a.st = dev_st;
   if (guess) {  // r = b - A (v_ + e): the second register window holds x0; tab = B
@@ -818,39 +826,18 @@ int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* ho
     a.taba = pde->d_tab(0);
     a.cia = interior_row(pde->h_A);
   }
-  auto launch = [&](const RGeom& g) {
+  // (in two parts on a decomposed grid: part 0 while the ghost planes of v_ / e travel)
+  auto launch = [&](int z_lo, int z_hi, int part_off) {
+    const RGeom g = make_geom(pde, z_lo, z_hi, part_off, rows, RR_RHS);
     if (guess)
       launch_rr<RR_RHS, true>(pde, g, a);
     else
       launch_rr<RR_RHS>(pde, g, a);
-    return g.total_blocks > 0 ? grid_blocks(g) : 0;
+    return blocks_written(g);
   };
-  const Geom& f = pde->g;
-  if (part < 0) {
-    const int nb = launch(make_geom(pde, 0, f.nz, 0, rows, RR_RHS));
-    BEAT_LAUNCH_CHECK();
-    if (pde->fuse_begin.on) {  // a single-slab solve: its start in the same launch (beat_solve_begin)
-      pde->fuse_begin.done = true;
-      return beat_pde_launch_reduce(pde, nb, 3, dev_st, nullptr, nullptr, 2, dev_st, pde->fuse_begin.rtol, pde->fuse_begin.atol,
-                                    pde->fuse_begin.max_it);
-    }
-    return beat_pde_launch_reduce(pde, nb, 3, dev_st, nullptr);
-  }
-  // in two parts on a decomposed grid (as beat_rr_pdot_part): the planes whose stencil needs no ghost plane of v_ / e
-  // while those travel, then the one or two slab-boundary planes and the reduction over all block partials
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
-  const RGeom gi = make_geom(pde, lo, std::max(lo, hi), 0, rows, RR_RHS);
-  if (part == 0) {
-    launch(gi);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = gi.total_blocks > 0 ? grid_blocks(gi) : 0;
-  if (!f.z_lo_phys) off += launch(make_geom(pde, 0, 1, off, rows, RR_RHS));
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) off += launch(make_geom(pde, f.nz - 1, f.nz, off, rows, RR_RHS));
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
-  return beat_pde_launch_reduce(pde, off, 3, dev_st, nullptr);
+  int count = 0;
+  if (int rc = beat_launch_parts(pde, PASS_RR_RHS, part, launch, &count)) return rc;
+  return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 3, dev_st, nullptr, ScalarStep::begin(dev_st, start));
 }
 
 // Bound constant of the predicted stop (beat_pcg_predict in beat_pde.hip): E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds
@@ -882,9 +869,8 @@ double beat_rr_predict_bound(const beat_pde* pde) {
 }
 
 // p_new = D^-1 r + st[BETA] p_old (p_old unread while beta = 0), LOCAL p_new . A p_new -> dev_st[PQ].
-// In two parts on a decomposed grid (as beat_pde_spmv_dot_part): part 0 = the planes whose stencil needs no ghost
-// plane (enqueue it while the ghost planes of r travel), part 1 = the one or two slab-boundary planes -- which also
-// keep p_new on the ghost planes next to them -- and the reduction of all block partials.
+// In two parts on a decomposed grid: part 0 while the ghost planes of r travel; the boundary planes of part 1 also keep p_new on the
+// ghost planes next to them.
 // slot >= 0 (the single-slab loop, operators created with the predicted stop on): the pass also sums r . A p and A p . A p
 // into dev_st[PQS..QQ], and the launch that reduces them predicts r_{i+1} . r_{i+1} -- when the prediction settles the stopping
 // test it latches the solve as the residual update of ring slot `slot` and the roll behind it would have (beat_pcg_predict)
@@ -893,48 +879,29 @@ int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const 
   const Geom& f = pde->g;
   const bool pred = slot >= 0 && pde->predict_stop && f.z_lo_phys && f.z_hi_phys;
   if (pred && pde->predict_c <= 0.0) pde->predict_c = beat_rr_predict_bound(pde);
-  RArgs a{};
+  RArgs a = rr_operator_args(pde, dev_st);
   a.x = dev_r;
   a.x2 = dev_p_old;
   a.y = dev_p_new;
-  a.tab = pde->d_tab(0);
-  a.dinv = pde->d_dinv();
-  a.ci = interior_row(pde->h_A);
-  a.dinv_i = pde->h_dinv[13];
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
-  auto launch = [&](const RGeom& g) {
+  auto launch = [&](int z_lo, int z_hi, int part_off) {
+    const RGeom g = make_geom(pde, z_lo, z_hi, part_off, 0, RR_PDOT);
     if (pred)
       launch_rr<RR_PDOT, false, true>(pde, g, a);
     else
       launch_rr<RR_PDOT>(pde, g, a);
+    return blocks_written(g);
   };
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
-  const RGeom gi = make_geom(pde, lo, std::max(lo, hi), 0, 0, RR_PDOT);
-  if (part == 0) {
-    launch(gi);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = gi.total_blocks > 0 ? grid_blocks(gi) : 0;
-  if (!f.z_lo_phys) {
-    const RGeom gb = make_geom(pde, 0, 1, off, 0, RR_PDOT);
-    launch(gb);
-    off += grid_blocks(gb);
-  }
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) {
-    const RGeom gb = make_geom(pde, f.nz - 1, f.nz, off, 0, RR_PDOT);
-    launch(gb);
-    off += grid_blocks(gb);
-  }
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
+  int count = 0;
+  if (int rc = beat_launch_parts(pde, PASS_RR_PDOT, part, launch, &count)) return rc;
+  if (part == 0) return BEAT_OK;
   if (pred) {
     static_assert(RQ == PQS + 1 && QQ == PQS + 2, "the three sums are reduced into one run of slots");
-    return beat_pde_launch_reduce(pde, off, 3, dev_st + PQS, dev_st, nullptr, 3, dev_st, 0.0, 0.0, 0, pde->d_alphas + slot,
-                                  pde->predict_c);
+    ScalarStep predict{ScalarStep::PREDICT, dev_st};
+    predict.alpha_slot = pde->d_alphas + slot;
+    predict.bound_c = pde->predict_c;
+    return beat_pde_launch_reduce(pde, count, 3, dev_st + PQS, dev_st, predict);
   }
-  return beat_pde_launch_reduce(pde, off, 1, dev_st + PQ, dev_st);
+  return beat_pde_launch_reduce(pde, count, 1, dev_st + PQ, dev_st);
 }
 
 int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, int slot) {
@@ -948,22 +915,16 @@ int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const doubl
 int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev_r_new, const double* dev_p, int slot,
                  bool roll) {
   const RGeom g = make_geom(pde, 0, pde->g.nz, 0, 0, RR_RUPD);
-  RArgs a{};
+  RArgs a = rr_operator_args(pde, dev_st);
   a.x = dev_p;
   a.x2 = dev_r;
   a.y = dev_r_new;
-  a.tab = pde->d_tab(0);
-  a.dinv = pde->d_dinv();
-  a.ci = interior_row(pde->h_A);
-  a.dinv_i = pde->h_dinv[13];
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
   a.alphas = pde->d_alphas;
   a.slot = slot;
   launch_rr<RR_RUPD>(pde, g, a);
   BEAT_LAUNCH_CHECK();
   // (with `roll` the scalar step -- beta, iteration count, latch: rr_next_kernel's -- runs in the reduction's launch)
-  return beat_pde_launch_reduce(pde, grid_blocks(g), 2, dev_st + RZN, dev_st, dev_st + NUPD, roll ? 1 : 0, dev_st);
+  return beat_pde_launch_reduce(pde, grid_blocks(g), 2, dev_st + RZN, dev_st, ScalarStep::after_update(dev_st, roll));
 }
 
 // ---- single-reduction iteration (decomposed solve, BEAT_DIST_MERGED=1) --------------------------------------------
@@ -978,37 +939,17 @@ int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev
 // Part 0 / 1 as beat_rr_pdot_part; part 1 reduces the block partials into dev_st[PQ..RRN] (local sums).
 int beat_rr_udot_part(beat_pde* pde, double* dev_st, const double* dev_r, int part) {
   static_assert(RZN == PQ + 1 && RRN == PQ + 2, "the three sums travel as one all-reduce of dev_st[PQ..RRN]");
-  const Geom& f = pde->g;
-  RArgs a{};
+  RArgs a = rr_operator_args(pde, dev_st);
   a.x = dev_r;
   a.x2 = dev_r;
-  a.tab = pde->d_tab(0);
-  a.dinv = pde->d_dinv();
-  a.ci = interior_row(pde->h_A);
-  a.dinv_i = pde->h_dinv[13];
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
-  const RGeom gi = make_geom(pde, lo, std::max(lo, hi), 0, 0, RR_UDOT);
-  if (part == 0) {
-    launch_rr<RR_UDOT>(pde, gi, a);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = gi.total_blocks > 0 ? grid_blocks(gi) : 0;
-  if (!f.z_lo_phys) {
-    const RGeom gb = make_geom(pde, 0, 1, off, 0, RR_UDOT);
-    launch_rr<RR_UDOT>(pde, gb, a);
-    off += grid_blocks(gb);
-  }
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) {
-    const RGeom gb = make_geom(pde, f.nz - 1, f.nz, off, 0, RR_UDOT);
-    launch_rr<RR_UDOT>(pde, gb, a);
-    off += grid_blocks(gb);
-  }
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
-  return beat_pde_launch_reduce(pde, off, 3, dev_st + PQ, dev_st);
+  auto launch = [&](int z_lo, int z_hi, int part_off) {
+    const RGeom g = make_geom(pde, z_lo, z_hi, part_off, 0, RR_UDOT);
+    launch_rr<RR_UDOT>(pde, g, a);
+    return blocks_written(g);
+  };
+  int count = 0;
+  if (int rc = beat_launch_parts(pde, PASS_RR_UDOT, part, launch, &count)) return rc;
+  return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 3, dev_st + PQ, dev_st);
 }
 
 int beat_rr_merged_next(beat_pde* pde, double* dev_st, int slot) {
@@ -1022,17 +963,11 @@ int beat_rr_merged_next(beat_pde* pde, double* dev_st, int slot) {
 int beat_rr_prupd(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,
                   double* dev_r_new) {
   const RGeom g = make_geom(pde, 0, pde->g.nz, 0, 0, RR_PRUPD);
-  RArgs a{};
+  RArgs a = rr_operator_args(pde, dev_st);
   a.x = dev_r;
   a.x2 = dev_p_old;
   a.y = dev_p_new;
   a.y2 = dev_r_new;
-  a.tab = pde->d_tab(0);
-  a.dinv = pde->d_dinv();
-  a.ci = interior_row(pde->h_A);
-  a.dinv_i = pde->h_dinv[13];
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
   launch_rr<RR_PRUPD>(pde, g, a);
   BEAT_LAUNCH_CHECK();
   return BEAT_OK;

@@ -297,12 +297,7 @@ int beat_small_launch(beat_pde* pde, const double* dev_v_prev, const double* con
   a.dinv = pde->d_dinv();
   a.v = dev_v_prev;
   a.x = dev_x;
-  for (int k = 0; k < n_stim; ++k) {
-    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
-    a.w[a.nstim] = host_dev_stim_w[k];
-    a.amp[a.nstim] = host_stim_amp[k];
-    ++a.nstim;
-  }
+  beat_fill_stimuli(a, host_dev_stim_w, host_stim_amp, n_stim);
   a.dt = pde->dt;
   a.rtol = rtol;
   a.atol = atol;

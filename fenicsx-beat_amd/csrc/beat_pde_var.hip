@@ -985,74 +985,40 @@ int beat_var_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* h
                                   pde->ctx->stream));
   a.dinv = pde->v_dinv;
   a.dt = pde->dt;
-  for (int k = 0; k < n_stim; ++k) {
-    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
-    a.w[a.nstim] = host_dev_stim_w[k];
-    a.amp[a.nstim] = host_stim_amp[k];
-    ++a.nstim;
-  }
+  beat_fill_stimuli(a, host_dev_stim_w, host_stim_amp, n_stim);
   a.partials = pde->ctx->d_partials;
-  if (part < 0) {
-    const int nb = launch_var<MODE_RHS>(pde, a, 0, pde->g.nz, 0);
-    BEAT_LAUNCH_CHECK();
-    return beat_pde_launch_reduce(pde, nb, 3, dev_red, nullptr);
-  }
-  // in two parts on a decomposed grid (as beat_var_spmv_dot_part): the planes that need no ghost plane of v_ / e while
-  // those travel, then the slab-boundary planes and the reduction over all block partials
-  const Geom& f = pde->g;
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
-  if (part == 0) {
-    pde->rhs_part_blocks = launch_var<MODE_RHS>(pde, a, lo, std::max(lo, hi), 0);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = pde->rhs_part_blocks;
-  if (!f.z_lo_phys) off += launch_var<MODE_RHS>(pde, a, 0, 1, off);
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) off += launch_var<MODE_RHS>(pde, a, f.nz - 1, f.nz, off);
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
-  return beat_pde_launch_reduce(pde, off, 3, dev_red, nullptr);
+  // (in two parts on a decomposed grid: part 0 while the ghost planes of v_ / e travel)
+  auto launch = [&](int z_lo, int z_hi, int part_off) { return launch_var<MODE_RHS>(pde, a, z_lo, z_hi, part_off); };
+  int count = 0;
+  if (int rc = beat_launch_parts(pde, PASS_VAR_RHS, part, launch, &count)) return rc;
+  return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 3, dev_red, nullptr);
+}
+
+// the segment-list product q = A p and the sum p.q, whole (part -1) or in the two parts of a decomposed grid
+static int var_spmv_dot_parts(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st, int part) {
+  VarArgs a{};
+  var_offsets(pde, a);
+  a.T1 = pde->v_A;
+  a.x = dev_p;
+  a.y = dev_q;
+  a.partials = pde->ctx->d_partials;
+  a.st = dev_st;
+  auto launch = [&](int z_lo, int z_hi, int part_off) { return launch_var<MODE_SPMV_DOT>(pde, a, z_lo, z_hi, part_off); };
+  int count = 0;
+  if (int rc = beat_launch_parts(pde, PASS_VAR_SPMV, part, launch, &count)) return rc;
+  return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 1, dev_st + PQ, dev_st);
 }
 
 int beat_var_spmv_dot(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st) {
   if (beat_vrr_available(pde)) return beat_vrr_spmv_dot(pde, dev_p, dev_q, dev_st, -1);
   if (beat_vtl_available(pde)) return beat_vtl_spmv_dot(pde, dev_p, dev_q, dev_st);
-  VarArgs a{};
-  var_offsets(pde, a);
-  a.T1 = pde->v_A;
-  a.x = dev_p;
-  a.y = dev_q;
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
-  const int nb = launch_var<MODE_SPMV_DOT>(pde, a, 0, pde->g.nz, 0);
-  BEAT_LAUNCH_CHECK();
-  return beat_pde_launch_reduce(pde, nb, 1, dev_st + PQ, dev_st);
+  return var_spmv_dot_parts(pde, dev_p, dev_q, dev_st, -1);
 }
 
 int beat_var_spmv_dot_part(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st, int part) {
   if (beat_vrr_available(pde)) return beat_vrr_spmv_dot(pde, dev_p, dev_q, dev_st, part);
   if (beat_vtl_parts_available(pde)) return beat_vtl_spmv_dot_part(pde, dev_p, dev_q, dev_st, part);
-  const Geom& f = pde->g;
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);  // planes that need no ghost data
-  VarArgs a{};
-  var_offsets(pde, a);
-  a.T1 = pde->v_A;
-  a.x = dev_p;
-  a.y = dev_q;
-  a.partials = pde->ctx->d_partials;
-  a.st = dev_st;
-  // block-partial slots: the interior launch's come first, the boundary planes follow
-  if (part == 0) {
-    launch_var<MODE_SPMV_DOT>(pde, a, lo, std::max(lo, hi), 0);
-    BEAT_LAUNCH_CHECK();
-    return BEAT_OK;
-  }
-  int off = (int)var_stencil_grid<MODE_SPMV_DOT>(var_range(pde, lo, std::max(lo, hi), false).grid);  // partial slots of the interior launch (part 0)
-  if (!f.z_lo_phys) off += launch_var<MODE_SPMV_DOT>(pde, a, 0, 1, off);
-  if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) off += launch_var<MODE_SPMV_DOT>(pde, a, f.nz - 1, f.nz, off);
-  BEAT_LAUNCH_CHECK();
-  BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");
-  return beat_pde_launch_reduce(pde, off, 1, dev_st + PQ, dev_st);
+  return var_spmv_dot_parts(pde, dev_p, dev_q, dev_st, part);
 }
 
 int beat_var_update_r(beat_pde* pde, double* dev_st, double* dev_r, const double* dev_q, int slot, bool roll) {
@@ -1061,7 +1027,7 @@ int beat_var_update_r(beat_pde* pde, double* dev_st, double* dev_r, const double
                      (int)pde->h_seg.size(), pde->n, (const double*)dev_st, dev_r, dev_q, (const double*)pde->v_dinv,
                      pde->ctx->d_partials, pde->d_alphas, slot);
   BEAT_LAUNCH_CHECK();
-  return beat_pde_launch_reduce(pde, (int)grid, 2, dev_st + RZN, dev_st, dev_st + NUPD, roll ? 1 : 0, dev_st);  // (roll: the scalar step in the same launch)
+  return beat_pde_launch_reduce(pde, (int)grid, 2, dev_st + RZN, dev_st, ScalarStep::after_update(dev_st, roll));  // (roll: the scalar step in the same launch)
 }
 
 int beat_var_pupdate_oop(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_cur, double* dev_p_next) {

@@ -307,7 +307,7 @@ int beat_vrr_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
   auto tissue = [&](int64_t i) { return (flags[(size_t)(i >> 6)] >> (i & 63)) & 1ull; };
   std::vector<VrrItem> lists[3];
   std::vector<char> act((size_t)f.nz);
-  const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
+  const SlabPart inner = beat_slab_part(pde, 0), boundary = beat_slab_part(pde, 1);
   for (int rb = 0; rb < nrb; ++rb)
     for (int seg = 0; seg < nsegx; ++seg) {
       const int x0 = seg * SEG, x1 = std::min(f.nx, x0 + SEG), ya = rb * RY, yb = std::min(f.ny, ya + RY);
@@ -343,9 +343,8 @@ int beat_vrr_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
         }
       };
       runs(0, f.nz, lists[0]);
-      runs(lo, std::max(lo, hi), lists[1]);
-      if (!f.z_lo_phys) runs(0, 1, lists[2]);
-      if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) runs(f.nz - 1, f.nz, lists[2]);
+      runs(inner.range[0].z_lo, inner.range[0].z_hi, lists[1]);
+      for (int k = 0; k < boundary.count; ++k) runs(boundary.range[k].z_lo, boundary.range[k].z_hi, lists[2]);
     }
   std::vector<VrrItem> all;
   for (int k = 0; k < 3; ++k) {
@@ -417,12 +416,14 @@ int beat_vrr_spmv_dot(beat_pde* pde, const double* dev_p, double* dev_q, double*
     BEAT_LAUNCH_CHECK();
     return beat_pde_launch_reduce(pde, nb, 1, dev_st + PQ, dev_st);
   }
+  // (its lists are cut by beat_slab_part when they are built: the launches are per list, the hand-off is beat_launch_parts')
   if (part == 0) {
-    pde->vrr_part_blocks = launch(1, 0);
+    beat_part0_put(pde, PASS_VRR_SPMV, launch(1, 0));
     BEAT_LAUNCH_CHECK();
     return BEAT_OK;
   }
-  int off = pde->vrr_part_blocks;
+  int off = 0;
+  if (int rc = beat_part0_take(pde, PASS_VRR_SPMV, &off)) return rc;
   off += launch(2, off);
   BEAT_LAUNCH_CHECK();
   BEAT_REQUIRE(off <= BEAT_MAX_PARTIALS, "too many block partials");

@@ -734,14 +734,14 @@ int beat_vtl_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
   }
   if (!(f.z_lo_phys && f.z_hi_phys)) {
     // a decomposed grid: the planes that need no ghost plane of p (their launch overlaps the exchange), then the one or two
-    // slab-boundary planes -- the same split as beat_var_spmv_dot_part's
-    const int lo = f.z_lo_phys ? 0 : 1, hi = f.nz - (f.z_hi_phys ? 0 : 1);
-    std::vector<VtlItem> b_lo, b_hi;
-    bool ok = build(lo, std::max(lo, hi), max_run, part_items[0]);
-    if (!f.z_lo_phys) ok = build(0, 1, max_run, b_lo) && ok;
-    if (!f.z_hi_phys && (f.nz > 1 || f.z_lo_phys)) ok = build(f.nz - 1, f.nz, max_run, b_hi) && ok;
-    part_items[1] = b_lo;
-    part_items[1].insert(part_items[1].end(), b_hi.begin(), b_hi.end());
+    // slab-boundary planes (beat_slab_part)
+    const SlabPart inner = beat_slab_part(pde, 0), boundary = beat_slab_part(pde, 1);
+    std::vector<VtlItem> plane_items;
+    bool ok = build(inner.range[0].z_lo, inner.range[0].z_hi, max_run, part_items[0]);
+    for (int k = 0; k < boundary.count; ++k) {
+      ok = build(boundary.range[k].z_lo, boundary.range[k].z_hi, max_run, plane_items) && ok;
+      part_items[1].insert(part_items[1].end(), plane_items.begin(), plane_items.end());
+    }
     if (!ok || (int64_t)part_items[0].size() + (int64_t)part_items[1].size() > BEAT_MAX_PARTIALS) {
       part_items[0].clear();  // (the split launches keep the segment-list kernel)
       part_items[1].clear();
@@ -783,32 +783,52 @@ int beat_vtl_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
 
 bool beat_vtl_available(const beat_pde* pde) { return pde->var && pde->vtl != nullptr && ((VtlData*)pde->vtl)->nitems > 0; }
 
-// what the two passes of the right-hand side add to a launch
-struct VtlRhs {
-  const double* rows;  // coefficient rows of this pass (nullptr: A)
-  int mode;            // 2: b = rows v_ + dt stim (rows = B); 4: r = b - A (v_ + e)
-  const double* e;     // mode 4: guess increment or nullptr
-  const double* t;     // mode 4: b
-  double dt;
-  const double* w[BEAT_MAX_STIM];
-  double amp[BEAT_MAX_STIM];
-  int nstim;
-  double* red_out;     // b.b, r.z, r.r
+// One tile pass: what it computes, over which list of tiles, and what each of its operands is
+//   SPMV: q = A p, p.q -> st[PQ]                 PDOT: p_new = D^-1 r + beta p (first: D^-1 r) formed while loading and stored, q = A p_new
+//   BV:   q = B p + dt sum_k amp_k w_k (p = v_)  RES:  q = t - A (p + e) (p = v_), p_new = D^-1 q if wanted, the sums -> red_out[0..3)
+struct VtlPass {
+  enum Kind { SPMV, PDOT, BV, RES };
+  Kind kind = SPMV;
+  int list = 0;           // 0: the whole slab | 1, 2: the tiles of part 0 / part 1 of a decomposed grid (beat_vtl_setup)
+  int part_off = 0;       // partial slot of the list's first tile (one partial per tile, in list order)
+  enum Reduce { NO_SUM, LIST, BOTH_PARTS };  // the partials summed behind the launch: none, this list's, lists 1 and 2 (part 1)
+  Reduce reduce = LIST;
+  double* st = nullptr;   // the scalar state: the latch and beta (SPMV, PDOT)
+  const double* p = nullptr;  // SPMV: p | PDOT: p_old | BV, RES: v_
+  double* q = nullptr;        // SPMV, PDOT: q | BV: b | RES: r
+  const double* r = nullptr;  // PDOT: r
+  double* p_new = nullptr;    // PDOT: p_new | RES: z = D^-1 r, or nullptr where nothing reads it
+  bool first = false;         // PDOT: the first iteration (beta = 0, p unread)
+  const double* const* stim_w = nullptr;  // BV: the caller's stimuli (beat_fill_stimuli)
+  const double* stim_amp = nullptr;
+  int n_stim = 0;
+  const double* e = nullptr;  // RES: guess increment or nullptr
+  const double* t = nullptr;  // RES: b
+  double* red_out = nullptr;  // RES: b.b (from the BV pass), r.z, r.r
+  const PcgStart* start = nullptr;  // RES: the start of the solve behind the sums, or nullptr
 };
-static int vtl_launch(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st, const double* dev_r, double* dev_p_new, int first,
-                      int list = 0, int part_off = 0, bool reduce = true, int reduce_count = 0, const VtlRhs* rhs = nullptr);
+static int vtl_launch(beat_pde* pde, const VtlPass& ps);
+
+// part -1: the whole slab (the defaults).  The two parts of a decomposed grid: part 0 = list 1 without a reduction, part 1 = list 2 and
+// the sum over both lists' tiles
+static void vtl_set_part(const beat_pde* pde, VtlPass& ps, int part) {
+  if (part < 0) return;
+  const VtlData* d = (const VtlData*)pde->vtl;
+  ps.list = part + 1;
+  ps.part_off = part == 0 ? 0 : d->list_count[1];
+  ps.reduce = part == 0 ? VtlPass::NO_SUM : VtlPass::BOTH_PARTS;
+}
 
 // whole-slab q = A p and the sum p.q
 int beat_vtl_spmv_dot(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st) {
-  return vtl_launch(pde, dev_p, dev_q, dev_st, nullptr, nullptr, 0);
+  return beat_vtl_spmv_dot_part(pde, dev_p, dev_q, dev_st, -1);
 }
 
 // the solver's iteration in one pass: p_new = D^-1 r + beta p_old (beta from dev_st; first: p_new = D^-1 r) formed while
 // loading and stored, q = A p_new, the sum p_new.q.  Single-slab operators only (both faces physical).
 int beat_vtl_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, double* dev_q, int first) {
   BEAT_REQUIRE(pde->g.z_lo_phys && pde->g.z_hi_phys, "beat_vtl_pdot is the single-slab path");
-  BEAT_REQUIRE(dev_p_old != dev_p_new, "the direction update is out of place");
-  return vtl_launch(pde, dev_p_old, dev_q, dev_st, dev_r, dev_p_new, first);
+  return beat_vtl_pdot_part(pde, dev_st, dev_r, dev_p_old, dev_p_new, dev_q, first, -1);
 }
 
 bool beat_vtl_pdot_available(const beat_pde* pde) {
@@ -816,10 +836,8 @@ bool beat_vtl_pdot_available(const beat_pde* pde) {
   return beat_vtl_available(pde) && ((VtlData*)pde->vtl)->pdot && ((VtlData*)pde->vtl)->ry == 8 && pde->g.z_lo_phys && pde->g.z_hi_phys;
 }
 
-static int vtl_launch(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st, const double* dev_r, double* dev_p_new, int first,
-                      int list, int part_off, bool reduce, int reduce_count, const VtlRhs* rhs) {
-  const bool bv = rhs != nullptr && rhs->mode == 2, res = rhs != nullptr && rhs->mode == 4;
-  const bool pdot = dev_r != nullptr && !res;
+static int vtl_launch(beat_pde* pde, const VtlPass& ps) {
+  const bool bv = ps.kind == VtlPass::BV, res = ps.kind == VtlPass::RES, pdot = ps.kind == VtlPass::PDOT;
   VtlData* d = (VtlData*)pde->vtl;
   const Geom& f = pde->g;
   VtlArgs a{};
@@ -831,37 +849,31 @@ static int vtl_launch(beat_pde* pde, const double* dev_p, double* dev_q, double*
   a.nsegx = d->nsegx;
   a.nzp = d->nzp;
   a.partials = pde->ctx->d_partials;
-  const int count = d->list_count[list];
+  const int count = d->list_count[ps.list];
+  const int reduce_count = ps.reduce == VtlPass::BOTH_PARTS ? d->list_count[1] + d->list_count[2] : count;
   if (count == 0) {  // (a split launch without tiles: only the reduction over what the other part wrote)
-    return reduce ? beat_pde_launch_reduce(pde, reduce_count, 1, dev_st + PQ, dev_st) : BEAT_OK;
+    return ps.reduce != VtlPass::NO_SUM ? beat_pde_launch_reduce(pde, reduce_count, 1, ps.st + PQ, ps.st) : BEAT_OK;
   }
-  a.part_off = part_off - d->list_base[list];  // the kernel indexes its partial by the tile's position in the whole array
-  a.st = dev_st;
+  a.part_off = ps.part_off - d->list_base[ps.list];  // the kernel indexes its partial by the tile's position in the whole array
+  a.st = ps.st;
   // blocks in eights (one per XCD), at most the resident number, at least one tile per block on average
   const unsigned grid = std::max(8u, std::min(d->resident, (unsigned)((count + 7) & ~7)));
-  a.x = dev_p;
-  a.y = dev_q;
-  a.rows = (rhs != nullptr && rhs->rows != nullptr) ? rhs->rows : pde->v_A;
-  a.ignore_stop = rhs != nullptr;
+  a.x = res ? ps.e : ps.p;  // (RES forms its window from v_ and e: nullptr = no guess on record)
+  a.y = ps.q;
+  a.rows = bv ? pde->v_B : pde->v_A;
+  a.ignore_stop = bv || res;
   if (bv) {
-    a.dt = rhs->dt;
-    a.nstim = rhs->nstim;
-    for (int k = 0; k < rhs->nstim; ++k) {
-      a.w[k] = rhs->w[k];
-      a.amp[k] = rhs->amp[k];
-    }
+    a.dt = pde->dt;
+    beat_fill_stimuli(a, ps.stim_w, ps.stim_amp, ps.n_stim);
   }
-  if (res) {
-    a.t = rhs->t;
-    a.x = rhs->e;  // the second operand of the formed window (nullptr: no guess on record)
-  }
+  a.t = ps.t;
   a.mask = d->d_mask;
   a.items = d->d_items;
-  a.xcd_first = d->d_xcd_first + 9 * list;
+  a.xcd_first = d->d_xcd_first + 9 * ps.list;
   a.next = d->d_xcd_first + 27;
-  a.r = res ? dev_p : dev_r;  // (RES: the first operand of the formed window is v_, passed as dev_p)
-  a.pnew = dev_p_new;
-  a.first = first ? 1 : 0;
+  a.r = res ? ps.p : ps.r;
+  a.pnew = ps.p_new;
+  a.first = ps.first ? 1 : 0;
   if (pdot && pde->v_gc0 != nullptr) {  // a slab with live neighbours: the direction is formed and kept on the ghost planes too
     a.gc0_lo = f.z_lo_phys ? nullptr : pde->v_gc0;
     a.gc0_hi = f.z_hi_phys ? nullptr : pde->v_gc0 + f.plane;
@@ -880,16 +892,9 @@ static int vtl_launch(beat_pde* pde, const double* dev_p, double* dev_q, double*
     d->dyn ? launch(vtl_spmv_kernel<4, true, 0>, 4) : launch(vtl_spmv_kernel<4, false, 0>, 4);
   }
   BEAT_LAUNCH_CHECK();
-  if (!reduce) return BEAT_OK;
-  if (res) {  // (b.b from the BV pass, r.z and r.r from this one; on a single-slab solve its start in the same launch)
-    if (pde->fuse_begin.on) {
-      pde->fuse_begin.done = true;
-      return beat_pde_launch_reduce(pde, count, 3, rhs->red_out, nullptr, nullptr, 2, rhs->red_out, pde->fuse_begin.rtol, pde->fuse_begin.atol,
-                                    pde->fuse_begin.max_it);
-    }
-    return beat_pde_launch_reduce(pde, count, 3, rhs->red_out, nullptr);
-  }
-  return beat_pde_launch_reduce(pde, reduce_count ? reduce_count : count, 1, dev_st + PQ, dev_st);  // one partial per tile, in list order
+  if (ps.reduce == VtlPass::NO_SUM) return BEAT_OK;
+  if (res) return beat_pde_launch_reduce(pde, count, 3, ps.red_out, nullptr, ScalarStep::begin(ps.red_out, ps.start));
+  return beat_pde_launch_reduce(pde, reduce_count, 1, ps.st + PQ, ps.st);
 }
 
 // The right-hand side of a step on the tiles (what beat_var_rhs computes with gathers: 352 B/node from beyond the L2 on the 401^3
@@ -915,28 +920,31 @@ bool beat_vtl_rhs_wanted(const beat_pde* pde) {  // (before the rows of B exist:
 }
 
 int beat_vtl_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp, int n_stim,
-                 double* dev_x, double* dev_r, double* dev_p, double* dev_t, double* dev_red, const double* dev_e) {
+                 double* dev_x, double* dev_r, double* dev_p, double* dev_t, double* dev_red, const double* dev_e, const PcgStart* start) {
   if (dev_x != dev_v_prev)  // nodes outside the tissue keep their value: copy everything first (as beat_var_rhs does)
     BEAT_HIP_CHECK(hipMemcpyAsync(dev_x, dev_v_prev, sizeof(double) * (size_t)pde->n, hipMemcpyDeviceToDevice, pde->ctx->stream));
-  VtlRhs one{};
-  one.rows = pde->v_B;
-  one.mode = 2;
-  one.dt = pde->dt;
-  for (int k = 0; k < n_stim; ++k) {
-    if (host_dev_stim_w[k] == nullptr || host_stim_amp[k] == 0.0) continue;
-    one.w[one.nstim] = host_dev_stim_w[k];
-    one.amp[one.nstim] = host_stim_amp[k];
-    ++one.nstim;
-  }
-  if (int rc = vtl_launch(pde, dev_v_prev, dev_t, pde->d_st, nullptr, nullptr, 0, 0, 0, false, 0, &one)) return rc;
-  VtlRhs two{};
-  two.mode = 4;
-  two.e = dev_e;
-  two.t = dev_t;
-  two.red_out = dev_red;
-  // (dev_p of vtl_launch carries v_ here; its dev_p_new is where z = D^-1 r goes: only the three-kernel iteration reads it --
-  // the fused pass forms its first direction from r itself)
-  return vtl_launch(pde, dev_v_prev, dev_r, pde->d_st, nullptr, beat_vtl_pdot_available(pde) ? nullptr : dev_p, 0, 0, 0, true, 0, &two);
+  VtlPass bv;
+  bv.kind = VtlPass::BV;
+  bv.reduce = VtlPass::NO_SUM;  // (its partials of b.b are summed behind the second pass)
+  bv.st = pde->d_st;
+  bv.p = dev_v_prev;
+  bv.q = dev_t;
+  bv.stim_w = host_dev_stim_w;
+  bv.stim_amp = host_stim_amp;
+  bv.n_stim = n_stim;
+  if (int rc = vtl_launch(pde, bv)) return rc;
+  VtlPass res;
+  res.kind = VtlPass::RES;
+  res.st = pde->d_st;
+  res.p = dev_v_prev;
+  res.e = dev_e;
+  res.t = dev_t;
+  res.q = dev_r;
+  // (z: only the three-kernel iteration reads it -- the fused pass forms its first direction from r itself)
+  res.p_new = beat_vtl_pdot_available(pde) ? nullptr : dev_p;
+  res.red_out = dev_red;
+  res.start = start;
+  return vtl_launch(pde, res);
 }
 
 // The fused pass on a slab with live neighbours, in the two parts of the split launches: part 0 = the planes whose stencil
@@ -956,9 +964,16 @@ bool beat_vtl_pdot_dist_available(const beat_pde* pde) {
 int beat_vtl_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new, double* dev_q,
                        int first, int part) {
   BEAT_REQUIRE(dev_p_old != dev_p_new, "the direction update is out of place");
-  const VtlData* d = (const VtlData*)pde->vtl;
-  if (part == 0) return vtl_launch(pde, dev_p_old, dev_q, dev_st, dev_r, dev_p_new, first, 1, 0, false, 0);
-  return vtl_launch(pde, dev_p_old, dev_q, dev_st, dev_r, dev_p_new, first, 2, d->list_count[1], true, d->list_count[1] + d->list_count[2]);
+  VtlPass ps;
+  ps.kind = VtlPass::PDOT;
+  ps.st = dev_st;
+  ps.p = dev_p_old;
+  ps.r = dev_r;
+  ps.p_new = dev_p_new;
+  ps.q = dev_q;
+  ps.first = first != 0;
+  vtl_set_part(pde, ps, part);
+  return vtl_launch(pde, ps);
 }
 
 // the split launches of a decomposed grid: part 0 = the planes that need no ghost plane of p (no reduction), part 1 = the
@@ -970,7 +985,10 @@ bool beat_vtl_parts_available(const beat_pde* pde) {
 }
 
 int beat_vtl_spmv_dot_part(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st, int part) {
-  const VtlData* d = (const VtlData*)pde->vtl;
-  if (part == 0) return vtl_launch(pde, dev_p, dev_q, dev_st, nullptr, nullptr, 0, 1, 0, false, 0);
-  return vtl_launch(pde, dev_p, dev_q, dev_st, nullptr, nullptr, 0, 2, d->list_count[1], true, d->list_count[1] + d->list_count[2]);
+  VtlPass ps;
+  ps.st = dev_st;
+  ps.p = dev_p;
+  ps.q = dev_q;
+  vtl_set_part(pde, ps, part);
+  return vtl_launch(pde, ps);
 }

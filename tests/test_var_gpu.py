@@ -290,6 +290,59 @@ def test_per_node_spmv_in_two_parts_equals_whole(hip_ctx, lo_phys, hi_phys, nzl)
     assert np.isclose(float(ops.st[3]), pq, rtol=1e-13)
 
 
+def test_per_node_spmv_in_two_parts_sums_the_slots_its_launch_wrote(hip_ctx, monkeypatch):
+    """A single slab (both faces physical) large enough for the tile-ordered segment list: part 0 is the whole slab and its
+    launch is rounded down to whole eights of blocks, so the sum of part 1 must cover those blocks and no more.  48 x 64 x 87
+    nodes, all tissue: 4176 segments of 64 nodes, 1044 blocks wanted, 1040 launched (below the 1536 resident blocks of
+    var_spmv_kernel) -- the smallest family of shapes that reaches that list with a block count that is no multiple of 8.
+    A residual update first leaves non-zero partials in every slot up to 1044; then spmv_interior + spmv_boundary give the
+    same q and bit for bit the same st[PQ] as spmv_dot."""
+    from beat import _stencil
+    from beat._engine import HipOps
+
+    ctx = hip_ctx
+    cells = (47, 63, 86)
+    nn = tuple(c + 1 for c in cells)
+    n = int(np.prod(nn))
+    assert n == 4176 * 64 and (4176 + 3) // 4 == 1044 and 1044 % 8 == 4
+    ncells = int(np.prod(cells))
+    M = np.broadcast_to(np.diag([9.5e-4, 1.25e-4, 1.25e-4]), (ncells, 3, 3)).copy()
+    mf, kf = _stencil.stencil_fields(3, cells, (0.1, 0.1, 0.1), M, np.ones(ncells, dtype=bool))
+    monkeypatch.setenv("BEAT_VTL", "0")  # both routes through var_spmv_kernel
+    monkeypatch.setenv("BEAT_VRR", "0")
+    ops = HipOps(ctx, nn, True, True, mf, kf, per_node=True)
+    ops.set_timestep(0.01, 0.5, 0.05)
+    rng = np.random.default_rng(21)
+    p = ops.ring[0]
+    p.set(rng.standard_normal(n))
+    p.ghost_lo.fill_(float("nan"))
+    p.ghost_hi.fill_(float("nan"))
+
+    def dirty_every_partial_slot():
+        ops.r.set(rng.standard_normal(n))
+        ops.q.set(rng.standard_normal(n))
+        ops.st.zero_()
+        ops.st[1], ops.st[3] = 1.0, 2.0  # alpha = st[RZ] / st[PQ]
+        ops.cg_update_r(0)
+        ctx.synchronize()
+        assert float(ops.st[4]) > 0.0 and float(ops.st[5]) > 0.0  # r.z and r.r: the update ran
+
+    dirty_every_partial_slot()
+    ops.q.fill(float("nan"))
+    ops.spmv_dot()
+    ctx.synchronize()
+    q1 = ops.q.numpy().copy()
+    pq = float(ops.st[3])
+    assert np.isfinite(q1).all() and pq > 0.0
+    dirty_every_partial_slot()
+    ops.q.fill(float("nan"))
+    ops.spmv_interior(p)
+    ops.spmv_boundary(p)
+    ctx.synchronize()
+    np.testing.assert_array_equal(ops.q.numpy(), q1)
+    assert float(ops.st[3]) == pq, f"p.q whole {pq!r}, in two parts {float(ops.st[3])!r}"
+
+
 @pytest.mark.parametrize("cells,L", CASES + [((70, 9, 40), (7.0, 0.9, 4.0))])
 def test_marching_spmv_equals_the_stored_row_kernel_bit_for_bit(hip_ctx, cells, L, monkeypatch):
     """vrr_spmv_kernel (csrc/beat_pde_vrr.hip: marches along z, loads the forward half of each row and takes the backward
