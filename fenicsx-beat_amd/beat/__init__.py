@@ -10,6 +10,7 @@ from . import (  # noqa: F401
     butcher,
     conductivities,
     ecg,
+    events,
     geometry,
     grid,
     io,
@@ -25,6 +26,7 @@ from . import (  # noqa: F401
     utils,
 )
 from .ecg import ECGRecovery
+from .events import EventRecorder
 from .irksome_model import IrksomeMonodomainModel
 from .monodomain_model import MonodomainModel
 from .monodomain_solver import MonodomainSplittingSolver
@@ -37,5 +39,5 @@ __program_name__ = "fenicsx-beat-amd"
 __all__ = [
     "monodomain_model", "irksome_model", "IrksomeMonodomainModel", "butcher", "odesolver", "base_model", "MonodomainModel", "monodomain_solver",
     "MonodomainSplittingSolver", "utils", "single_cell", "conductivities", "stimulation", "geometry", "grid", "models",
-    "Stimulus", "io", "ecg", "ECGRecovery", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
+    "Stimulus", "io", "ecg", "ECGRecovery", "events", "EventRecorder", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
 ]

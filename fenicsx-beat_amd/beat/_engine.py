@@ -480,6 +480,21 @@ class HipOps:
             _hip.check(self.lib.beat_pde_x_flush(self.handle, C.c_void_p(self.st_ptr_for_flush), x.ptr, self.ring[0].ptr,
                                                  self.fld, ring_base, 0))
 
+    def flush_pending_events(self, field, maps, t0: float, t1: float) -> bool:
+        """``flush_pending`` and the event maps' pass over ``field`` in one (beat_pde_x_flush_events; ``maps``: a reference to a
+        ``_hip.EventMaps``), if it is ``field`` whose update is pending.  False: nothing of that field is pending (an open solve has
+        been finished), the caller observes the field as it is."""
+        if self.open_x is not None:
+            self.solve_finish()
+        if self.pending is None or self.pending[0].ptr.value != field.ptr.value:
+            return False
+        x, ring_base, _ = self.pending
+        _hip.check(self.lib.beat_pde_x_flush_events(self.handle, C.c_void_p(self.st_ptr_for_flush), x.ptr, self.ring[0].ptr,
+                                                    self.fld, ring_base, maps, t0, t1))
+        self.pending = None
+        self.flushes = getattr(self, "flushes", 0) + 1
+        return True
+
     def apply(self, which, x, y):
         _hip.check(self.lib.beat_pde_apply(self.handle, which, x.ptr, y.ptr))
 

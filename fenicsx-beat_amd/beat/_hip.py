@@ -55,6 +55,25 @@ _i64 = C.c_int64
 _dbl = C.c_double
 _int = C.c_int
 
+
+class EventMaps(C.Structure):
+    """beat_event_maps: thresholds, mode (0 step, 1 linear), strict (0: >=, 1: >) and the device fields of the maps (None: not kept)."""
+
+    _fields_ = [
+        ("thr_up", _dbl),
+        ("thr_down", _dbl),
+        ("mode", C.c_int32),
+        ("strict", C.c_int32),
+        ("v_prev", _vp),
+        ("act_first", _vp),
+        ("act_last", _vp),
+        ("repol", _vp),
+        ("apd", _vp),
+        ("dvdt_max", _vp),
+        ("v_max", _vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/beat_hip.h
 SIGNATURES = {
     "beat_abi_version": (_int, []),
@@ -139,6 +158,8 @@ SIGNATURES = {
     "beat_field_probe_record": (_int, [_vp, _vp, _vp, _vp, _int, _vp]),
     "beat_field_dot": (_int, [_vp, _vp, _vp, _i64, C.POINTER(_dbl)]),
     "beat_field_minmax": (_int, [_vp, _vp, _i64, C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "beat_field_events": (_int, [_vp, _vp, _i64, C.POINTER(EventMaps), _dbl, _dbl]),
+    "beat_pde_x_flush_events": (_int, [_vp, _vp, _vp, _vp, _i64, _int, C.POINTER(EventMaps), _dbl, _dbl]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)

@@ -50,7 +50,9 @@ class MonodomainSplittingSolver:
 
     def solve(self, interval, dt, recorder=None):
         """The reference's loop (monodomain_solver.py:53-66).  ``recorder`` (a ``grid.ProbeRecorder`` on ``pde.state``;
-        not part of the reference's signature) gets one row per step.  On a grid small enough for the one-launch
+        not part of the reference's signature) gets one row per step; an ``events.EventRecorder`` -- or a list of recorders,
+        event maps next to probes -- is shown every step (``observe(t0, t1)``; the event maps first: their pass completes the
+        potential, which the probes then read) and keeps the step loop.  On a grid small enough for the one-launch
         diffusion solve, with a device cell model, theta = 1, stimuli whose time dependence is a scalar factor and no
         monitor attached, the steps are handed to the library in batches (beat_split_steps): same kernels, same
         values, no host round trip between steps."""
@@ -64,17 +66,28 @@ class MonodomainSplittingSolver:
             steps.append((t0, t1))
             t0 = t1
             t1 = t0 + dt
-        if steps and self._can_batch(recorder):
-            self._batched_steps(steps, recorder)
+        from .events import EventRecorder
+
+        recorders = list(recorder) if isinstance(recorder, (list, tuple)) else [recorder] if recorder is not None else []
+        single = recorders[0] if len(recorders) == 1 else None
+        if steps and len(recorders) <= 1 and self._can_batch(single):
+            self._batched_steps(steps, single)
             return
+        recorders.sort(key=lambda r: not isinstance(r, EventRecorder))  # (stable: event maps first)
         for iv in steps:
             self.step(iv)
-            if recorder is not None:
-                recorder.record()
+            for r in recorders:
+                if isinstance(r, EventRecorder):
+                    r.observe(*iv)
+                else:
+                    r.record()
 
     def _can_batch(self, recorder) -> bool:
+        from .events import EventRecorder
         from .odesolver import DolfinODESolver
 
+        if isinstance(recorder, EventRecorder):
+            return False  # event maps inside the library's step loops: not built
         if not (isinstance(self.ode, DolfinODESolver) and self._can_fuse() and np.isclose(self.theta, 1.0)):
             return False
         ode, pde = self.ode, self.pde

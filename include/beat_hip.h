@@ -632,6 +632,48 @@ int beat_field_dot(beat_ctx* ctx, const double* dev_x, const double* dev_y, int6
  * numpy.min / numpy.max: a NaN anywhere makes both results NaN.  Synchronises. */
 int beat_field_minmax(beat_ctx* ctx, const double* dev_field, int64_t n, double* host_min, double* host_max);
 
+/* ---- per-node event maps: activation, repolarisation, APD, maximal upstroke velocity, maximal potential --------------
+ * What the reference's tissue demos build on the host from the whole potential after every step
+ * (demos/irksome_model_gotranx.py:251-254: crossed = (v_arr >= activation_threshold) & (tact_arr < 0.0); tact_arr[crossed] = t;
+ * demos/niederer_benchmark.py:285-287: the same rule with > 0.0 at probe points), kept on the device: one pass per step, nothing
+ * returns to the host.  Every pointer is a DEVICE field laid out as any field (n nodes, a ghost plane on either side; only the n
+ * owned nodes are touched) and may be NULL: that map is not kept.  The caller initialises the time maps (act_first, act_last, repol,
+ * apd) with NaN, dvdt_max and v_max with -inf and v_prev with the potential before the first observed step.
+ * One step (t0, t1), vp = v_prev[i], vn = v[i], above(x) = strict ? x > thr_up : x >= thr_up:
+ *  - up event: above(vn) and (!above(vp) or act_last[i] is NaN -- the reference's rule: a node that is above the threshold when
+ *    first observed is activated at that step).  Its time: t1 (mode 0, step) or t0 + (t1 - t0) (thr_up - vp) / (vn - vp) when
+ *    vp < thr_up, else t0 (mode 1, linear).  Writes act_last[i], and act_first[i] if that is NaN.  (Without act_last, act_first alone
+ *    is the same map: a node's first event is the first step that finds it above the threshold.)
+ *  - down event: act_last[i] is not NaN, vp >= thr_down and vn < thr_down; its time likewise with thr_down.  Writes repol[i] and
+ *    apd[i] = repol - act_last.  Both need act_last.
+ *  - dvdt_max[i] = max(dvdt_max[i], (vn - vp) / (t1 - t0));  v_max[i] = max(v_max[i], vn);  then v_prev[i] = vn.
+ * v_prev is needed by act_last, repol, apd, dvdt_max and by every time map in linear mode; act_first in step mode and v_max do
+ * without it: pass NULL then and the pass neither reads nor writes that stream (16 bytes per node for the two of them).  Maps are
+ * stored on events only. */
+typedef struct beat_event_maps {
+  double thr_up, thr_down;
+  int32_t mode;   /* 0 = step, 1 = linear */
+  int32_t strict; /* 0: >=, 1: > */
+  double* v_prev;
+  double* act_first;
+  double* act_last;
+  double* repol;
+  double* apd;
+  double* dvdt_max;
+  double* v_max;
+} beat_event_maps;
+/* The pass on a potential that is up to date.  EINVAL (nothing enqueued, nothing touched): a null argument, n <= 0, mode or strict
+ * out of range, t1 <= t0, a NaN threshold in use, repol / apd without act_last, a map or mode that needs v_prev without it. */
+int beat_field_events(beat_ctx* ctx, const double* dev_v, int64_t n, const beat_event_maps* maps, double t0, double t1);
+/* beat_pde_x_flush(pde, dev_st, dev_x, dev_ring0, field_stride, ring_base, only_if_full = 0) and the pass above on dev_x as ONE pass
+ * over x (the host loop of the reference reads the potential the solve has just completed, src/beat/base_model.py:236, then applies
+ * demos/irksome_model_gotranx.py:251-254): x and the fields of the initial guess come out bit for bit as from beat_pde_x_flush, the maps
+ * bit for bit as from beat_pde_x_flush followed by beat_field_events.  A per-node-row operator (beat_pde_create_var), whose flush
+ * works on its list of tissue segments, takes exactly those two passes.  Refuses as beat_pde_x_flush (an open solve on the handle
+ * included) and as beat_field_events do, before anything is enqueued. */
+int beat_pde_x_flush_events(beat_pde* pde, const double* dev_st, double* dev_x, const double* dev_ring0, int64_t field_stride,
+                            int ring_base, const beat_event_maps* maps, double t0, double t1);
+
 #ifdef __cplusplus
 }
 #endif
