@@ -29,6 +29,7 @@ MATH_IN = (1, 1, 1, 1, 1, 1, 2, 3, 4, 2, 3, 4, 1, 1, 1, 1, 4, 4, 4, 4, 4, 4)
 MATH_OUT = (1, 1, 1, 1, 1, 1, 2, 3, 4, 2, 3, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)
 MAX_STIM = 8
 MAX_CLASSES = 32
+MAX_LEADS = 16  # BEAT_MAX_LEADS: rows per beat_field_leads call
 
 # slots of the PCG scalar state (see include/beat_hip.h)
 ST_BB, ST_RZ, ST_RR, ST_PQ, ST_RZN, ST_RRN, ST_TOL2, ST_BETA, ST_STOP, ST_ITERS, ST_REASON = range(11)
@@ -160,6 +161,7 @@ SIGNATURES = {
     "beat_field_minmax": (_int, [_vp, _vp, _i64, C.POINTER(_dbl), C.POINTER(_dbl)]),
     "beat_field_events": (_int, [_vp, _vp, _i64, C.POINTER(EventMaps), _dbl, _dbl]),
     "beat_pde_x_flush_events": (_int, [_vp, _vp, _vp, _vp, _i64, _int, C.POINTER(EventMaps), _dbl, _dbl]),
+    "beat_field_leads": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)

@@ -3,7 +3,9 @@
 ``ECGRecovery.solve`` recovers the transmembrane current density  Im  from  -C_m (Im, w) = (M grad v, grad w)
 -- one consistent-mass solve with right-hand side K v, done with the diffusion step's PCG on the device --
 and ``eval(point)`` gives the lead integral  1/(4 pi sigma_b) int Im / |x - p| dx  as a dot product with nodal
-weights integrated once per electrode."""
+weights integrated once per electrode.  ``LeadRecorder`` records the same leads at every step of a time loop without the
+solve: the recovery is linear in v, so each electrode has a lead field q with  lead = q . v,  made once.  (It is defined
+below ``Leads12``.)"""
 
 from __future__ import annotations
 
@@ -166,6 +168,115 @@ class Leads12(NamedTuple):
     @property
     def V6_(self):
         return self._precordial("V6")
+
+
+# ---- lead traces recorded on the device -----------------------------------------------------------------------------
+_LEADS12_NAMES = Leads12._fields
+
+
+class LeadRecorder:
+    """``LeadRecorder(ecg, electrodes, capacity=4096, rtol=1e-12, atol=1e-30)``: the leads ``ecg.solve()`` followed by
+    ``assemble_scalar(ecg.eval(p))`` per electrode give (ecg.py:282-298), recorded step by step ON THE DEVICE.
+
+    With w the nodal weights of an electrode (``ecg.eval(p).weights``) and  Mass Im = -(1/C_m) K v,  the lead is
+    w . Im = q . v  with the *lead field*  q = -(1/C_m) K Mass^-1 w  -- both matrices are symmetric.  q depends on the mesh, the
+    tensor and the electrode only: one mass solve (through the recovery's own solver, at ``rtol`` / ``atol``) and one stiffness
+    apply per electrode, here.  ``record()`` is then one pass over the potential against the L stored rows (beat_field_leads):
+    no solve, and nothing returns to the host until ``values()`` or a full buffer (``capacity`` rows) is read back.
+
+    ``electrodes``: a dict name -> point, or a sequence of points (named "0", "1", ...); at most ``_hip.MAX_LEADS``.  ``C_m`` and
+    ``sigma_b`` are read from ``ecg`` once, here.  ``MonodomainSplittingSolver.solve(..., recorder=rec)`` calls ``record()`` after
+    every step (also next to an ``EventRecorder``, in a list).
+
+    Memory: the rows take 8 L N bytes of device memory for N nodes -- 9.7 GB for nine electrodes at 512^3."""
+
+    def __init__(self, ecg: ECGRecovery, electrodes, capacity: int = 4096, rtol: float = 1e-12, atol: float = 1e-30):
+        points = dict(electrodes) if isinstance(electrodes, dict) else {str(k): p for k, p in enumerate(electrodes)}
+        if not points:
+            raise ValueError("LeadRecorder needs at least one electrode")
+        if len(points) > _hip.MAX_LEADS:
+            raise ValueError(f"at most {_hip.MAX_LEADS} electrodes per LeadRecorder, got {len(points)}")
+        if ecg.mesh.comm.size > 1:
+            raise NotImplementedError("LeadRecorder on a decomposed mesh: the leads would need one all-reduce per read-back, but nothing tests them yet")
+        self._ecg = ecg
+        self._ctx = ecg._ctx
+        self.names = tuple(points)
+        self.points = {k: tuple(float(c) for c in p) for k, p in points.items()}
+        self.nleads = len(self.names)
+        self.capacity = int(capacity)
+        if self.capacity < 1:
+            raise ValueError("capacity must be positive")
+        self._n = n = ecg.v.num_values
+        self._ldq = (n + 63) // 64 * 64
+        self._q = self._ctx.zeros(self.nleads * self._ldq)
+        ops, opts = ecg._ops, ecg.petsc_options or {}
+        scale = -1.0 / float(ecg.C_m)
+        y, ky = ops.new_field(), ops.new_field()
+        self.ksp = []
+        for l, name in enumerate(self.names):
+            w = ecg.eval(self.points[name]).weights  # (sigma_b goes in here)
+            y.fill(0.0)
+            res = ecg._solver.solve(ecg._zero, [w], [scale], y, rtol=float(rtol), atol=float(atol),
+                                    max_it=int(opts.get("ksp_max_it", 10_000)))
+            if res.converged_reason < 0:
+                raise RuntimeError(f"lead field of electrode {name!r}: the mass solve did not converge ({res.iterations} iterations, "
+                                   f"residual {res.residual_norm:.3e})")
+            self.ksp.append(res)
+            ops.apply(3, y, ky)
+            row = C.c_void_p(self._q.data_ptr() + 8 * l * self._ldq)
+            _hip.check(self._ctx.lib.beat_copy(self._ctx.handle, row, ky.ptr, n))
+        del y, ky, w  # the work fields go back
+        self._buf = self._ctx.zeros(self.capacity * self.nleads)
+        self._rows = 0   # rows in the device buffer
+        self._done = []  # host copies of full buffers
+
+    def record(self) -> None:
+        """One sample of every lead from the potential as it is now.  Enqueues and returns."""
+        if self._rows == self.capacity:
+            self._done.append(self._read())
+            self._rows = 0
+        v = self._ecg.v.field  # (brings an aliased potential up to date, as ECGRecovery.solve does)
+        out = C.c_void_p(self._buf.data_ptr() + 8 * self._rows * self.nleads)
+        _hip.check(self._ctx.lib.beat_field_leads(self._ctx.handle, v.ptr, self._n, C.c_void_p(self._q.data_ptr()), self._ldq,
+                                                  self.nleads, out))
+        self._rows += 1
+
+    def _read(self) -> np.ndarray:
+        return self._buf[: self._rows * self.nleads].cpu().numpy().reshape(self._rows, self.nleads).copy()
+
+    def __len__(self) -> int:
+        return sum(len(a) for a in self._done) + self._rows
+
+    def values(self) -> np.ndarray:
+        """All samples recorded so far, (samples, L), columns in the order of the electrodes.  Synchronises."""
+        parts = self._done + ([self._read()] if self._rows else [])
+        return np.concatenate(parts) if parts else np.zeros((0, self.nleads))
+
+    def _column(self, name) -> int:
+        try:
+            return self.names.index(name)
+        except ValueError:
+            raise KeyError(f"no electrode named {name!r} (have {self.names!r})") from None
+
+    def signal(self, name) -> np.ndarray:
+        """The trace of one electrode."""
+        return self.values()[:, self._column(name)]
+
+    def leads12(self) -> Leads12:
+        """``Leads12`` of the electrodes named RA, LA, LL, RL, V1 .. V6 (RL and the precordial ones may be missing: None)."""
+        missing = [k for k in ("RA", "LA", "LL") if k not in self.names]
+        if missing:
+            raise KeyError(f"leads12 needs electrodes named RA, LA and LL; missing {missing}")
+        vals = self.values()
+        return Leads12(**{k: vals[:, self.names.index(k)].copy() for k in _LEADS12_NAMES if k in self.names})
+
+    def lead_field(self, name) -> grid.Function:
+        """q of one electrode as a function on the potential's space: ``q.x.array @ v.x.array`` is the lead."""
+        f = grid.Function(self._ecg.V, name=f"lead_field_{name}")
+        row = C.c_void_p(self._q.data_ptr() + 8 * self._column(name) * self._ldq)
+        _hip.check(self._ctx.lib.beat_copy(self._ctx.handle, f.writable_field().ptr, row, self._n))
+        f._touch()
+        return f
 
 
 # ---- QT-interval helpers on a lead signal (ecg.py:20-227), post-processing on the host ------------------------------

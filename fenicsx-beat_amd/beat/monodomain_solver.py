@@ -50,8 +50,8 @@ class MonodomainSplittingSolver:
 
     def solve(self, interval, dt, recorder=None):
         """The reference's loop (monodomain_solver.py:53-66).  ``recorder`` (a ``grid.ProbeRecorder`` on ``pde.state``;
-        not part of the reference's signature) gets one row per step; an ``events.EventRecorder`` -- or a list of recorders,
-        event maps next to probes -- is shown every step (``observe(t0, t1)``; the event maps first: their pass completes the
+        not part of the reference's signature) gets one row per step, as does an ``ecg.LeadRecorder``; an ``events.EventRecorder`` -- or a
+        list of recorders, event maps next to probes and leads -- is shown every step (``observe(t0, t1)``; the event maps first: their pass completes the
         potential, which the probes then read) and keeps the step loop.  On a grid small enough for the one-launch
         diffusion solve, with a device cell model, theta = 1, stimuli whose time dependence is a scalar factor and no
         monitor attached, the steps are handed to the library in batches (beat_split_steps): same kernels, same
@@ -83,11 +83,12 @@ class MonodomainSplittingSolver:
                     r.record()
 
     def _can_batch(self, recorder) -> bool:
+        from .ecg import LeadRecorder
         from .events import EventRecorder
         from .odesolver import DolfinODESolver
 
-        if isinstance(recorder, EventRecorder):
-            return False  # event maps inside the library's step loops: not built
+        if isinstance(recorder, (EventRecorder, LeadRecorder)):
+            return False  # event maps and lead traces inside the library's step loops: not built
         if not (isinstance(self.ode, DolfinODESolver) and self._can_fuse() and np.isclose(self.theta, 1.0)):
             return False
         ode, pde = self.ode, self.pde

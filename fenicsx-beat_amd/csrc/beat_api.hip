@@ -33,6 +33,7 @@ extern "C" int beat_ctx_create(int device, void* hip_stream, beat_ctx** out) {
   ctx->stream = (hipStream_t)hip_stream;
   BEAT_HIP_CHECK(hipMalloc(&ctx->d_partials, sizeof(double) * BEAT_NRED * BEAT_MAX_PARTIALS));
   BEAT_HIP_CHECK(hipMalloc(&ctx->d_small, sizeof(double) * 64));
+  BEAT_HIP_CHECK(hipMalloc(&ctx->d_lead_partials, sizeof(double) * BEAT_MAX_LEADS * BEAT_LEADS_MAX_BLOCKS));
   BEAT_HIP_CHECK(hipHostMalloc(&ctx->h_pinned, sizeof(double) * 64));
   BEAT_HIP_CHECK(hipMemset(ctx->d_partials, 0, sizeof(double) * BEAT_NRED * BEAT_MAX_PARTIALS));
   *out = ctx;
@@ -44,6 +45,7 @@ extern "C" int beat_ctx_destroy(beat_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)hipFree(ctx->d_partials);
   (void)hipFree(ctx->d_small);
+  (void)hipFree(ctx->d_lead_partials);
   (void)hipHostFree(ctx->h_pinned);
   delete ctx;
   return BEAT_OK;

@@ -19,9 +19,11 @@ struct beat_ctx {
   double* d_partials = nullptr;  // scratch for block partial sums: BEAT_NRED * BEAT_MAX_PARTIALS
   double* h_pinned = nullptr;    // small pinned staging buffer (64 doubles)
   double* d_small = nullptr;     // small device staging buffer (64 doubles)
+  double* d_lead_partials = nullptr;  // block partial sums of beat_field_leads: BEAT_MAX_LEADS * BEAT_LEADS_MAX_BLOCKS
 };
 #define BEAT_MAX_PARTIALS 16384
 #define BEAT_NRED 3
+#define BEAT_LEADS_MAX_BLOCKS 1024
 
 void beat_set_error(const char* fmt, ...);
 

@@ -674,6 +674,21 @@ int beat_field_events(beat_ctx* ctx, const double* dev_v, int64_t n, const beat_
 int beat_pde_x_flush_events(beat_pde* pde, const double* dev_st, double* dev_x, const double* dev_ring0, int64_t field_stride,
                             int ring_base, const beat_event_maps* maps, double t0, double t1);
 
+/* ---- ECG lead traces: several dot products with the potential in one pass -------------------------------------------------
+ * The reference recovers the current density with a mass solve and integrates it once per electrode, every sample
+ * (src/beat/ecg.py:282-298: ECGRecovery.solve, then assemble_scalar(eval(point)) per electrode).  Both steps are linear in v and
+ * both matrices symmetric: lead_l = w_l . Im = q_l . v with the lead field q_l = -(1/C_m) K Mass^-1 w_l, which the caller makes once
+ * per electrode (beat_pde_solve with A = Mass, beat_pde_apply(which = 3)) and stores as row l of dev_q, rows ldq doubles apart.
+ *   out[l] = sum_{i<n} q[l*ldq + i] * v[i],  l < nleads.  Enqueued on the context's stream; does not synchronise.
+ * dev_v and the rows may start at any 8-byte-aligned address (v is usually a row of the state array); only the n owned nodes of v
+ * and the first n entries of a row are read.  v is read once per group of 8 rows.  fp64 accumulators, block partials in scratch of
+ * the context, a second launch of one block adds them in a fixed order; no atomics.  The same input gives the same bits on every
+ * call, and out[l] does not depend on which other rows the call holds: nleads = 9 and nine calls with nleads = 1 give the same bits.
+ * EINVAL (nothing enqueued, nothing touched): a null argument, n <= 0, nleads outside 1..BEAT_MAX_LEADS, ldq < n, a pointer that
+ * is not 8-byte aligned. */
+#define BEAT_MAX_LEADS 16
+int beat_field_leads(beat_ctx* ctx, const double* dev_v, int64_t n, const double* dev_q, int64_t ldq, int nleads, double* dev_out);
+
 #ifdef __cplusplus
 }
 #endif
