@@ -916,22 +916,22 @@ int beat_dist_solve_begin(beat_pde* pde, beat_comm* comm, const double* dev_v_pr
   // ghost planes of v_ for the right-hand side (the reference's scatter_forward after the previous solve) and, in the
   // same exchange, of the guess increment e (written by the x update of the previous solve): they travel while the
   // right-hand side is built on the planes that need neither, the one or two boundary planes follow
-  const bool guess_path = (rr || pde->var) && pde->guess_order != 0 && pde->d_guess != nullptr && pde->hist_n >= 1;
+  double* const ghost_e = (rr || pde->var) ? pde->guess.ghost_e() : nullptr;
   if (rr || pde->var) {
     BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
     BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
-    BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
-    beat_guess_begin(pde);
-    BEAT_REQUIRE(!pde->guess.use_e || guess_path, "guess increment without ghost planes");
+    BEAT_REQUIRE(!pde->guess.pending, "the previous solve's deferred update has not been applied");
+    pde->guess.begin();
+    BEAT_REQUIRE(!pde->guess.cur.use_e || ghost_e != nullptr, "guess increment without ghost planes");
   }
-  if ((rc = halo_start(comm, const_cast<double*>(dev_v_prev), n, plane, guess_path ? pde->d_guess : nullptr))) return rc;
+  if ((rc = halo_start(comm, const_cast<double*>(dev_v_prev), n, plane, ghost_e))) return rc;
   static const bool split_rhs = [] {  // BEAT_DIST_RHS_SPLIT=0: wait for the planes first, one launch (A/B runs)
     const char* e = std::getenv("BEAT_DIST_RHS_SPLIT");
     return !(e && e[0] == '0');
   }();
   auto rhs = [&](int part) {  // (the start of the solve follows the all-reduce of the sums: no PcgStart)
     if (rr) return beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, st, part);
-    const double* e = pde->guess.use_e ? pde->guess.e : nullptr;
+    const double* e = pde->guess.cur.use_e ? pde->guess.cur.e : nullptr;
     return beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, r, ring, st, e, part);
   };
   const bool parts = rr || pde->var;  // (else the tiled stage kernels' right-hand side: one launch behind the exchange)

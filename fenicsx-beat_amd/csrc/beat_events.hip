@@ -82,10 +82,7 @@ extern "C" int beat_pde_x_flush_events(beat_pde* pde, const double* dev_st, doub
   fa.ring_base = ring_base;
   fa.R = pde->ring;
   // the application a deferring solve left to its caller carries that solve's guess terms (as beat_pde_x_flush)
-  if (pde->guess_pending) {
-    fa.gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
+  fa.gt = pde->guess.take_pending();
   if (fa.gt.d != nullptr) return launch_events<2>(pde->ctx, dev_x, pde->n, *maps, t0, t1, fa);
   return launch_events<1>(pde->ctx, dev_x, pde->n, *maps, t0, t1, fa);
 }

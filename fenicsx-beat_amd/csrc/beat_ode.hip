@@ -227,13 +227,8 @@ extern "C" int beat_ode_step(beat_ctx* ctx, int model_id, double* dev_states, in
 // step): the update is applied by the flush pass instead and the launch proceeds without a pending update.
 static int flush_long_ring(beat_pde* pde, double* v_row, const double* dev_ring0, int64_t field_stride, int& pending) {
   if (pending <= BEAT_MAX_PENDING) return BEAT_OK;
-  beat_pde_detail::GuessTerms gt{};
-  if (pde->guess_pending) {
-    gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
   pending = 0;
-  return beat_pde_x_flush_terms(pde, nullptr, v_row, dev_ring0, field_stride, pde->last_base, 0, gt);
+  return beat_pde_x_flush_terms(pde, nullptr, v_row, dev_ring0, field_stride, pde->last_base, 0, pde->guess.take_pending());
 }
 
 // pending = -1 (round 5): `pde` has an OPEN solve (beat_pde_solve_begin) whose result the host has not looked at.  The launch is
@@ -248,29 +243,20 @@ static int step_behind_open_solve(beat_ctx* ctx, beat_pde* pde, const double* de
   BEAT_REQUIRE(pde != nullptr && pde->open.on, "pending = -1 needs an operator with an open solve");
   BEAT_REQUIRE(dev_ring0 != nullptr && field_stride >= n, "bad pending update");
   BEAT_REQUIRE(pde->open.x == v_row, "the open solve does not work on this row");
-  PendingV behind{dev_ring0, field_stride, pde->d_alphas, 0, pde->guess, pde->d_st, pde->ring};
+  PendingV behind{dev_ring0, field_stride, pde->d_alphas, 0, pde->guess.cur, pde->d_st, pde->ring};
   if (int rc = launch(behind)) return rc;
   beat_ksp_info info{};
   int pend2[2] = {0, 0};
   bool needed_more = false;
   const int rc_solve = beat_solve_end(pde, 1, &info, pend2, &needed_more);
   if (rc_solve != BEAT_OK && rc_solve != BEAT_ENOTCONV) return rc_solve;
-  pde->applied_behind = false;
+  pde->guess.applied_behind = false;
   if (!needed_more) {  // the launch behind the solve has applied the update: nothing is left to the caller
-    if (pde->guess_pending) {
-      pde->applied_terms = pde->guess_final;
-      pde->applied_behind = true;
-    }
-    pde->guess_pending = false;
+    pde->guess.pending_applied_behind();
     return BEAT_OK;
   }
   // the first launch saw an unlatched solve and returned at once: again, with what the finished solve left
-  PendingV pend{dev_ring0, field_stride, pend2[1] ? pde->d_alphas : nullptr, pend2[1], {}, nullptr, 0};
-  if (pde->guess_pending) {
-    pend.gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
-  return launch(pend);
+  return launch(PendingV{dev_ring0, field_stride, pend2[1] ? pde->d_alphas : nullptr, pend2[1], pde->guess.take_pending(), nullptr, 0});
 }
 
 // The pending-update protocol of the step entry points (beat_ode_step_pending / _rows / _classes): what a deferred solve left to
@@ -292,10 +278,7 @@ static int step_with_pending(beat_ctx* ctx, beat_pde* pde, double* v_row, int64_
   if (!long_ring)
     if (int rc = flush_long_ring(pde, v_row, dev_ring0, field_stride, pending)) return rc;
   PendingV pend{dev_ring0, field_stride, pending ? pde->d_alphas : nullptr, pending, {}};
-  if (pde != nullptr && pde->guess_pending) {  // this launch is the application the deferring solve left open
-    pend.gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
+  if (pde != nullptr) pend.gt = pde->guess.take_pending();  // this launch is the application the deferring solve left open
   return launch(pend);
 }
 
@@ -497,7 +480,7 @@ extern "C" int beat_split_steps(beat_ctx* ctx, int model_id, double* dev_states,
   BEAT_REQUIRE(pde->n == n, "the operator has %lld nodes, the state array %lld", (long long)pde->n, (long long)n);
   BEAT_REQUIRE(beat_small_available(pde), "beat_split_steps is for grids the one-launch solve takes "
                "(beat_pde_small_grid_solve_active)");
-  BEAT_REQUIRE(!pde->guess_pending, "a deferred update of the potential is pending: apply it first");
+  BEAT_REQUIRE(!pde->guess.pending, "a deferred update of the potential is pending: apply it first");
   BEAT_REQUIRE(n_stim == 0 || (host_dev_stim_w != nullptr && host_stim_amp != nullptr), "null stimulus arrays");
   BEAT_REQUIRE(n_probe == 0 || (host_probe_idx && host_probe_w && dev_probe_out), "null probe arrays");
   if (n_steps == 0) return BEAT_OK;
@@ -510,12 +493,11 @@ extern "C" int beat_split_steps(beat_ctx* ctx, int model_id, double* dev_states,
     if (int rc = beat_small_launch(pde, v_row, host_dev_stim_w, host_stim_amp ? host_stim_amp + (size_t)s * n_stim : nullptr,
                                    n_stim, v_row, rtol, atol, max_it, pde->d_batch_st + 16 * s))
       return rc;
-    if (pde->guess.d != nullptr) beat_guess_advance(pde);  // (the adaptive order keeps its choice through a batch, see below)
+    if (pde->guess.cur.d != nullptr) pde->guess.advance();  // (the adaptive order keeps its choice through a batch, see below)
     if (n_probe > 0)
       if (int rc = beat_field_probe_record(ctx, v_row, host_probe_idx, host_probe_w, n_probe, dev_probe_out + (size_t)s * n_probe))
         return rc;
   }
-  pde->auto_e_order = 0;
   std::vector<double> h((size_t)16 * n_steps);
   BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), pde->d_batch_st, sizeof(double) * 16 * n_steps, hipMemcpyDeviceToHost, ctx->stream));
   BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -526,18 +508,7 @@ extern "C" int beat_split_steps(beat_ctx* ctx, int model_id, double* dev_states,
     if (worst == BEAT_OK) worst = beat_pcg_check(k, s);
   }
   pde->last_iters = (int)h[(size_t)16 * (n_steps - 1) + beat_pde_detail::ITERS];
-  if (pde->guess_order < 0 && n_steps >= 4) {
-    // adaptive order, batch-wise: the whole batch ran with one order (its first solves on the guess the previous
-    // batch left); score it by the mean iteration count of the later steps and let the policy move (beat_guess_policy:
-    // here one "solve" is one batch)
-    double sum = 0.0;
-    for (int s = 2; s < n_steps; ++s) sum += h[(size_t)16 * s + beat_pde_detail::ITERS];
-    const int k = pde->auto_next - 1;
-    const double mean = sum / (n_steps - 2);
-    pde->auto_score[k] = pde->auto_seen[k] ? 0.5 * pde->auto_score[k] + 0.5 * mean : mean;
-    pde->auto_seen[k] = 1;
-    pde->auto_since_probe += 5;  // (a batch stands for many solves: look at a neighbour every second or third batch)
-    pde->auto_next = beat_guess_policy(pde);
-  }
+  // (adaptive order: the batch ran with one order and is scored as one solve)
+  pde->guess.observe_batch(h.data() + beat_pde_detail::ITERS, 16, n_steps);
   return worst;
 }

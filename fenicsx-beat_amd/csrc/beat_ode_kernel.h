@@ -54,7 +54,7 @@ __device__ __forceinline__ PendingNow beat_pending_now(const PendingV& p, int nu
     o.count = nupd % p.ring_len;
     o.gt.accumulate = nupd >= p.ring_len ? 1 : 0;
     const bool e_due = nupd == 0 && p.gt.use_e != 0;
-    if (o.count == 0 && !e_due) o.gt.d = nullptr;  // nothing to apply, nothing to record (beat_guess_end)
+    if (o.count == 0 && !e_due) o.gt.d = nullptr;  // nothing to apply, nothing to record (beat_guess_state::end)
   }
   return o;
 }

@@ -694,7 +694,7 @@ extern "C" int beat_pde_destroy(beat_pde* pde) {
   (void)hipFree(pde->d_st);
   (void)hipFree(pde->d_alphas);
   (void)hipFree(pde->d_batch_st);
-  (void)hipFree(pde->d_hist_alloc);
+  (void)hipFree(pde->guess.alloc);
   if (pde->h_st) (void)hipHostFree(pde->h_st);
   if (pde->ev_st) (void)hipEventDestroy(pde->ev_st);
   (void)hipFree(pde->v_A);
@@ -743,8 +743,7 @@ extern "C" int beat_pde_set_timestep(beat_pde* pde, double C_m, double theta, do
   pde->dt = dt;
   pde->have_dt = true;
   pde->last_iters = -1;
-  pde->hist_n = 0;  // increments of another time step say nothing about this one
-  pde->auto_e_order = 0;
+  pde->guess.reset();  // increments of another time step say nothing about this one
   if (pde->var) return beat_var_form_A(pde);
   return upload_tables(pde);
 }
@@ -833,8 +832,8 @@ extern "C" int beat_pde_rhs(beat_pde* pde, const double* dev_v_prev, const doubl
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
   BEAT_REQUIRE(dev_r != dev_v_prev && dev_p != dev_v_prev && dev_r != dev_p, "r, p must be distinct work fields");
-  BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
-  beat_guess_skip(pde);  // the stage-driven loops start from x0 = v_
+  BEAT_REQUIRE(!pde->guess.pending, "the previous solve's deferred update has not been applied");
+  pde->guess.skip();  // the stage-driven loops start from x0 = v_
   if (pde->var)
     return beat_var_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, dev_r, dev_p, dev_red);
   StencilArgs a{};
@@ -1046,11 +1045,7 @@ extern "C" int beat_pde_x_flush(beat_pde* pde, const double* dev_st, double* dev
   BEAT_REQUIRE(pde != nullptr && dev_x && dev_ring0, "null argument");
   BEAT_REQUIRE(!pde->open.on, "the operator has an open solve: finish it first (beat_pde_solve_end)");
   // the application a deferring solve left to its caller carries that solve's guess terms
-  GuessTerms gt{};
-  if (pde->guess_pending && !only_if_full) {
-    gt = pde->guess_final;
-    pde->guess_pending = false;
-  }
+  const GuessTerms gt = only_if_full ? GuessTerms{} : pde->guess.take_pending();
   return beat_pde_x_flush_terms(pde, dev_st, dev_x, dev_ring0, field_stride, ring_base, only_if_full, gt);
 }
 
@@ -1083,35 +1078,22 @@ extern "C" int beat_pde_set_guess_order(beat_pde* pde, int order) {
   BEAT_REQUIRE(pde != nullptr, "null pde");
   BEAT_REQUIRE(order >= -1 && order <= BEAT_GUESS_MAX_ORDER, "guess order must be -1 (adaptive) or 0..%d, got %d",
                BEAT_GUESS_MAX_ORDER, order);
-  BEAT_REQUIRE(!pde->guess_pending, "a deferred update is pending: apply it before changing the guess order");
-  pde->guess_order = order;
-  pde->hist_n = 0;
-  pde->guess = GuessTerms{};
-  pde->auto_cur = pde->auto_next = 3;
-  pde->auto_e_order = 0;
-  for (int k = 0; k < 4; ++k) pde->auto_seen[k] = 0;
-  pde->auto_since_probe = 0;
-  if (order < 0) order = BEAT_GUESS_MAX_ORDER;  // adaptive: the fields the cubic needs
-  // fields: the max(order - 1, 1) increments kept + the guess (1024^3: 8.6 GB each -- only what the order needs)
-  const int need = order > 0 ? std::max(1, order - 1) + 1 : 0;
-  if (need > pde->hist_fields) {
+  BEAT_REQUIRE(!pde->guess.pending, "a deferred update is pending: apply it before changing the guess order");
+  const int need = pde->guess.configure(order);
+  if (need > pde->guess.fields()) {
     const int64_t fld = beat_pde_field_stride(pde);
     BEAT_HIP_CHECK(hipStreamSynchronize(pde->ctx->stream));
-    (void)hipFree(pde->d_hist_alloc);
-    pde->d_hist_alloc = nullptr;
-    pde->hist_fields = 0;
-    pde->d_hist[0] = pde->d_hist[1] = pde->d_hist[2] = pde->d_guess = nullptr;
-    if (hipMalloc(&pde->d_hist_alloc, sizeof(double) * need * fld) != hipSuccess) {
+    (void)hipFree(pde->guess.alloc);
+    pde->guess.attach(nullptr, 0, 0, 0);
+    if (hipMalloc(&pde->guess.alloc, sizeof(double) * need * fld) != hipSuccess) {
       (void)hipGetLastError();
-      pde->d_hist_alloc = nullptr;
-      pde->guess_order = 0;  // no room for the history: the solves keep starting from x0 = v_
+      pde->guess.alloc = nullptr;
+      pde->guess.configure(0);  // no room for the history: the solves keep starting from x0 = v_
       beat_set_error("no device memory for the %d fields of the initial guess (%.1f GB)", need, 8e-9 * need * fld);
       return BEAT_EHIP;
     }
-    BEAT_HIP_CHECK(hipMemsetAsync(pde->d_hist_alloc, 0, sizeof(double) * need * fld, pde->ctx->stream));
-    pde->hist_fields = need;
-    for (int j = 0; j < need - 1; ++j) pde->d_hist[j] = pde->d_hist_alloc + pde->g.plane + (int64_t)j * fld;
-    pde->d_guess = pde->d_hist_alloc + pde->g.plane + (int64_t)(need - 1) * fld;
+    BEAT_HIP_CHECK(hipMemsetAsync(pde->guess.alloc, 0, sizeof(double) * need * fld, pde->ctx->stream));
+    pde->guess.attach(pde->guess.alloc, need, pde->g.plane, fld);
   }
   return BEAT_OK;
 }
@@ -1119,154 +1101,27 @@ extern "C" int beat_pde_set_guess_order(beat_pde* pde, int order) {
 extern "C" int beat_pde_guess_reset(beat_pde* pde) {
   BEAT_REQUIRE(pde != nullptr, "null pde");
   BEAT_REQUIRE(!pde->open.on, "the operator has an open solve: finish it first (beat_pde_solve_end)");
-  BEAT_REQUIRE(!pde->guess_pending, "a deferred update is pending");
-  pde->hist_n = 0;
-  pde->auto_e_order = 0;
+  BEAT_REQUIRE(!pde->guess.pending, "a deferred update is pending");
+  pde->guess.reset();
   return BEAT_OK;
 }
 
 // 1 when the last deferring solve left an application to its caller that carries guess terms (it is due even when the
 // count of pending search directions is 0)
-extern "C" int beat_pde_guess_pending(const beat_pde* pde) { return pde != nullptr && pde->guess_pending ? 1 : 0; }
+extern "C" int beat_pde_guess_pending(const beat_pde* pde) { return pde != nullptr && pde->guess.pending ? 1 : 0; }
 
 // device pointers of the last recorded increment d = x - v_ and of the guess increment e prepared for the next solve,
 // and the number of solves recorded since the history was dropped (0: the next solve starts from x0 = v_)
 extern "C" int beat_pde_guess_history(const beat_pde* pde, double** dev_d, double** dev_e, int* count) {
   BEAT_REQUIRE(pde != nullptr, "null pde");
-  if (dev_d) *dev_d = pde->d_hist[0];
-  if (dev_e) *dev_e = pde->d_guess;
-  if (count) *count = pde->hist_n;
+  pde->guess.history(dev_d, dev_e, count);
   return BEAT_OK;
 }
 
 extern "C" int beat_pde_guess_traffic(const beat_pde* pde, int* host_out) {
   BEAT_REQUIRE(pde != nullptr && host_out != nullptr, "null argument");
-  // (an update applied by a launch enqueued behind an open solve: its terms were kept when that solve was finished)
-  const GuessTerms& g = pde->guess_pending ? pde->guess_final : (pde->applied_behind ? pde->applied_terms : pde->guess);
-  int reads = 0, writes = 0;
-  if (g.d != nullptr) {
-    reads += (g.accumulate || g.use_e) ? 1 : 0;          // e
-    reads += (g.accumulate || g.cd != 0.0) ? 1 : 0;      // the oldest increment kept
-    for (int j = 0; j < BEAT_GUESS_MAX_ORDER - 2; ++j) reads += (!g.accumulate && g.cp[j] != 0.0) ? 1 : 0;
-    writes = 2;                                          // d, e
-  }
-  host_out[0] = reads;
-  host_out[1] = writes;
-  host_out[2] = pde->guess_order < 0 ? pde->auto_cur : pde->guess_order;
-  host_out[3] = pde->guess_pending ? 1 : (pde->applied_behind ? 2 : 0);  // 2: applied by the launch behind the open solve
+  pde->guess.traffic(host_out);
   return BEAT_OK;
-}
-
-void beat_guess_skip(beat_pde* pde) {
-  pde->hist_n = 0;
-  pde->auto_e_order = 0;
-  pde->guess = GuessTerms{};
-}
-
-static inline int guess_max_order(const beat_pde* pde) { return pde->guess_order < 0 ? BEAT_GUESS_MAX_ORDER : pde->guess_order; }
-
-void beat_guess_begin(beat_pde* pde) {
-  pde->guess = GuessTerms{};
-  if (pde->guess_order == 0 || pde->d_hist[0] == nullptr) return;
-  GuessTerms& g = pde->guess;
-  // increments kept: order - 1 (at least one), newest first in d_hist; the oldest one's storage takes this solve's
-  const int nb = std::max(1, guess_max_order(pde) - 1);
-  g.d = pde->d_hist[nb - 1];
-  for (int j = 0; j + 1 < nb; ++j) g.dp[j] = pde->d_hist[j];
-  g.e = pde->d_guess;
-  g.use_e = pde->hist_n >= 1;
-  // the guess after this solve extrapolates through the m increments then on record (this one included):
-  // e = sum_{i=0}^{m-1} (-1)^i C(m, i+1) D_i,  D_0 = this solve's, D_i = d_hist[i-1] as it is now
-  const int want = pde->guess_order < 0 ? pde->auto_next : pde->guess_order;
-  const int m = std::min(want, pde->hist_n + 1);
-  static const double binom[5][5] = {{1, 0, 0, 0, 0}, {1, 1, 0, 0, 0}, {1, 2, 1, 0, 0}, {1, 3, 3, 1, 0}, {1, 4, 6, 4, 1}};
-  g.a = binom[m][1];
-  for (int i = 1; i < m; ++i) {
-    const double c = ((i & 1) ? -1.0 : 1.0) * binom[m][i + 1];
-    if (i - 1 == nb - 1)
-      g.cd = c;
-    else
-      g.cp[i - 1] = c;
-  }
-}
-
-// Terms of an x update for the ring cycle starting at iteration ring_base: the first cycle carries e and records the
-// increment, later ones add to it.
-GuessTerms beat_guess_terms(const beat_pde* pde, int ring_base) {
-  GuessTerms g = pde->guess;
-  if (g.d != nullptr && ring_base > 0) g.accumulate = 1;
-  return g;
-}
-
-void beat_guess_advance(beat_pde* pde) {
-  const int nb = std::max(1, guess_max_order(pde) - 1);
-  double* newest = pde->d_hist[nb - 1];
-  for (int j = nb - 1; j > 0; --j) pde->d_hist[j] = pde->d_hist[j - 1];
-  pde->d_hist[0] = newest;
-  pde->hist_n = std::min(BEAT_GUESS_MAX_ORDER, pde->hist_n + 1);
-}
-
-// Adaptive order: called by the solve paths once the host has the scalar state of the solve that just ended, before
-// beat_guess_end / beat_guess_advance.  Scores the order the guess was built with by what it is for -- the
-// iterations the solve took (the norm of the initial residual is a poor judge: the cubic's is smaller even where it
-// costs more iterations, because what is left is the amplified noise of the recorded increments, rough, and Jacobi-PCG
-// takes longer over it than over the smooth truncation error of the quadratic) -- and picks the order of the guess
-// after next (the next one is being prepared by this solve's x update, whose coefficients were fixed when it began).
-// beat_guess_policy is the move itself (hill climbing over the orders 1..4, see beat_pde_internal.h).
-int beat_guess_policy(beat_pde* pde) {
-  constexpr int LO = 1, HI = BEAT_GUESS_MAX_ORDER;
-  int& cur = pde->auto_cur;
-  // a neighbour that has been looked at and costs fewer iterations takes over (ties stay)
-  for (int nb = cur - 1; nb <= cur + 1; nb += 2) {
-    if (nb < LO || nb > HI || !pde->auto_seen[nb - 1] || !pde->auto_seen[cur - 1]) continue;
-    if (pde->auto_score[nb - 1] < pde->auto_score[cur - 1] - 0.05) {
-      cur = nb;
-      pde->auto_since_probe = 0;  // look around from the new position soon
-      break;
-    }
-  }
-  int next = cur;
-  if (pde->auto_seen[cur - 1] && ++pde->auto_since_probe >= 12) {
-    pde->auto_since_probe = 0;
-    int nb = cur + (pde->auto_probe_up ? 1 : -1);
-    if (nb < LO || nb > HI) nb = cur - (pde->auto_probe_up ? 1 : -1);
-    pde->auto_probe_up = !pde->auto_probe_up;
-    if (nb >= LO && nb <= HI) next = nb;
-  }
-  return next;
-}
-
-void beat_guess_observe(beat_pde* pde, int iterations) {
-  if (pde->guess_order >= 0) return;
-  const int used = pde->auto_e_order;  // order behind the e this solve started from (0: none yet, or fewer increments)
-  if (used >= 1) {
-    const int k = used - 1;
-    pde->auto_score[k] = pde->auto_seen[k] ? 0.5 * pde->auto_score[k] + 0.5 * iterations : (double)iterations;
-    pde->auto_seen[k] = 1;
-  }
-  // the e the x update of THIS solve prepares has order min(auto_next, increments on record): remember it for the
-  // next observation, then choose for the one after
-  const int prepared = std::min(pde->auto_next, pde->hist_n + 1);
-  pde->auto_e_order = prepared == pde->auto_next ? prepared : 0;
-  pde->auto_next = beat_guess_policy(pde);
-}
-
-bool beat_guess_end(beat_pde* pde, int nupd, bool deferred) {
-  const int PR = pde->ring;
-  const bool partial = nupd % PR != 0;
-  if (pde->guess.d == nullptr) return partial;
-  const bool e_due = nupd == 0 && pde->guess.use_e;  // no ring cycle carried e to x yet
-  if (nupd == 0 && !e_due) {  // x = v_ is the answer and nothing was recorded: the history ends here
-    beat_guess_skip(pde);
-    return false;
-  }
-  const bool due = partial || e_due;
-  if (due && deferred) {
-    pde->guess_final = beat_guess_terms(pde, (nupd / PR) * PR);
-    pde->guess_pending = true;
-  }
-  beat_guess_advance(pde);
-  return due;
 }
 
 extern "C" int beat_pde_solve(beat_pde* pde, const double* dev_v_prev,
@@ -1288,7 +1143,7 @@ int beat_flush_if_ring_full(beat_pde* pde, int i) {
   const int PR = pde->ring;
   if (i % PR != PR - 1) return BEAT_OK;
   const PcgWork w = beat_pcg_work(pde, pde->open.work);
-  return beat_pde_x_flush_terms(pde, pde->d_st, pde->open.x, w.ring, w.fld, i + 1 - PR, 1, beat_guess_terms(pde, i + 1 - PR));
+  return beat_pde_x_flush_terms(pde, pde->d_st, pde->open.x, w.ring, w.fld, i + 1 - PR, 1, pde->guess.terms(i + 1 - PR));
 }
 
 // `count` more iterations of the open solve, enqueued
@@ -1366,7 +1221,7 @@ static int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const doubl
   BEAT_REQUIRE(max_it >= 0, "max_it must be >= 0");
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
-  BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
+  BEAT_REQUIRE(!pde->guess.pending, "the previous solve's deferred update has not been applied");
   beat_pde::OpenSolve o{};
   o.kind = pde->pc_ncoef > 1 ? SOLVE_POLY : beat_rr_available(pde) ? SOLVE_RR : pde->var ? SOLVE_ROWS : SOLVE_TILED;
   o.pdot = o.kind == SOLVE_ROWS && beat_vtl_pdot_available(pde);
@@ -1377,7 +1232,7 @@ static int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const doubl
   double* st = pde->d_st;
   int rc;
   if (o.kind == SOLVE_TILED || o.kind == SOLVE_POLY) {
-    // the stage kernels' right-hand side, which starts from x0 = v_ (beat_guess_skip), and the start of the solve
+    // the stage kernels' right-hand side, which starts from x0 = v_ (beat_guess_state::skip), and the start of the solve
     if ((rc = beat_pde_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, w.ring, st))) return rc;
     if ((rc = beat_pde_cg_begin(pde, st, rtol, atol, max_it))) return rc;
     if (o.kind == SOLVE_POLY) {  // z = M^-1 r, p = z
@@ -1387,9 +1242,9 @@ static int beat_solve_begin(beat_pde* pde, const double* dev_v_prev, const doubl
     }
     return beat_solve_open(pde, o);
   }
-  beat_guess_begin(pde);
+  pde->guess.begin();
   const PcgStart start{rtol, atol, max_it};  // (the register-row and the tile right-hand sides run it in the launch that sums their partials)
-  const double* e = pde->guess.use_e ? pde->guess.e : nullptr;
+  const double* e = pde->guess.cur.use_e ? pde->guess.cur.e : nullptr;
   if (o.kind == SOLVE_RR) {
     rc = beat_rr_rhs(pde, dev_v_prev, host_dev_stim_w, host_stim_amp, n_stim, dev_x, w.r, st, -1, &start);
   } else if (beat_vtl_rhs_available(pde)) {  // two tile passes (b = B v_ + dt stim, r = b - A (v_ + e)); q is free until iteration 0
@@ -1428,9 +1283,9 @@ static int poll_until_latched(beat_pde* pde, bool* needed_more) {
 static int finish_ring_cycle(beat_pde* pde, const double* h, int defer_flush, int* host_pending) {
   const int PR = pde->ring;
   const int nupd = (int)h[NUPD], base = (nupd / PR) * PR;
-  const GuessTerms last = beat_guess_terms(pde, base);
-  beat_guess_observe(pde, (int)h[ITERS]);
-  if (!beat_guess_end(pde, nupd, defer_flush != 0)) return BEAT_OK;
+  const GuessTerms last = pde->guess.terms(base);
+  pde->guess.observe((int)h[ITERS]);
+  if (!pde->guess.end(nupd, defer_flush != 0, PR)) return BEAT_OK;
   if (defer_flush) {
     host_pending[0] = pde->last_base = base;
     host_pending[1] = nupd % PR;
@@ -1472,7 +1327,7 @@ int beat_solve_end(beat_pde* pde, int defer_flush, beat_ksp_info* info, int* hos
   int rc = poll_until_latched(pde, needed_more);
   o.on = false;
   if (rc) return rc;
-  pde->applied_behind = false;  // (step_behind_open_solve sets it again when its launch has applied this solve's update)
+  pde->guess.applied_behind = false;  // (step_behind_open_solve sets it again when its launch has applied this solve's update)
   if (o.kind == SOLVE_DIST && (rc = beat_dist_drain(pde))) return rc;
   const double* h = pde->h_st;
   if (o.kind != SOLVE_POLY && (rc = finish_ring_cycle(pde, h, defer_flush, host_pending))) return rc;  // (POLY: x is up to date)

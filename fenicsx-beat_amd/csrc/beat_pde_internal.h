@@ -62,7 +62,7 @@ struct beat_pde {
   double C_m = 1.0, theta = 0.5, dt = 0.0;
   // device: 4 padded tables (A, B, Mass, K), then dinv[32]
   double* d_tabs = nullptr;
-  double* d_st = nullptr;  // 16 doubles, PCG scalar state of beat_pde_solve
+  double* d_st = nullptr;  // BEAT_ST_DOUBLES doubles, PCG scalar state of beat_pde_solve (the host reads the first 16)
   int last_iters = -1;
   int z_last_iters = -1;  // iterations of the last shifted solve (beat_pde_zsolve: its first chunk of enqueued iterations)
   unsigned vec_grid = 1;
@@ -91,8 +91,6 @@ struct beat_pde {
   double* h_st = nullptr;       // pinned copy of the scalar state of the open solve (16 doubles)
   hipEvent_t ev_st = nullptr;   // recorded behind that copy
   beat_ksp_info last_info{};    // of the last solve that was finished
-  bool applied_behind = false;  // its x update was applied by the launch enqueued behind it, with these terms (beat_pde_guess_traffic)
-  beat_pde_detail::GuessTerms applied_terms{};
   int last_rc = 0;
   int ring = beat_pde_detail::PRING;  // search directions kept before x is brought up to date (6; 12: per-node rows on a single slab)
   int last_base = 0;                  // first iteration of the ring cycle the last deferring solve left pending
@@ -104,30 +102,8 @@ struct beat_pde {
   // z node type of the ghost planes (the neighbouring slabs' boundary planes): 1 unless that plane is a face of the
   // whole grid (a neighbour that owns a single plane); set with beat_pde_set_ghost_types
   int ghost_lo_tz = 1, ghost_hi_tz = 1;
-  // initial guess from the previous solves' increments (0: x0 = v_; m: + the degree-(m-1) extrapolation of the last m), see GuessTerms
   int single_reduction = -1;               // decomposed solve: 1 one all-reduce per iteration, 0 two, -1 as BEAT_DIST_MERGED says
-  int guess_order = 0;                     // as configured: 0..4, or -1 = choose between 3 and 4 per solve (below)
-  // adaptive choice (guess_order = -1).  No order is right everywhere: each recorded increment carries an rtol-sized
-  // error, which an extrapolation of order m amplifies by the sum of its |coefficients| (1, 3, 7, 15) -- where the
-  // increments are smooth in time (plateau, repolarisation, rest) that noise sets the initial residual and the lowest
-  // order wins (0.3 iterations per step against 1.6), on a travelling front the truncation error does and the cubic
-  // wins (3.6 against 8).  Hill climbing on the order: a running mean of the iteration count per order, the current
-  // order used, one of its neighbours tried every 12th solve (up and down in turn), the move made when the neighbour
-  // has been costing fewer iterations.  Iteration counts are global: every rank of a decomposed solve decides alike.
-  int auto_cur = 3;                        // order the policy currently favours
-  int auto_next = 3;                       // order of the guess the NEXT x update prepares (auto_cur or a probe)
-  int auto_e_order = 0;                    // order the guess now in e was built with (0: none / not adaptive)
-  double auto_score[4] = {0.0, 0.0, 0.0, 0.0};  // running mean of the iterations per solve for orders 1..4
-  int auto_seen[4] = {0, 0, 0, 0};
-  int auto_since_probe = 0, auto_probe_up = 1;
-  double* d_hist[3] = {nullptr, nullptr, nullptr};  // fields with ghost planes: the last increments, newest first
-  double* d_guess = nullptr;               // the guess increment e prepared for the next solve
-  double* d_hist_alloc = nullptr;
-  int hist_fields = 0;                     // fields in d_hist_alloc
-  int hist_n = 0;                          // solves recorded since the history was last dropped (capped at the maximal order)
-  beat_pde_detail::GuessTerms guess{};     // terms of the solve in progress (out == nullptr: not in use)
-  bool guess_pending = false;              // the last solve left x += e + sum alpha_j p_j to its caller ...
-  beat_pde_detail::GuessTerms guess_final{};  // ... with these terms
+  beat_guess_state guess;                  // the extrapolated initial guess: order, history fields, terms of the solve in progress (beat_guess.h)
   void* vrr = nullptr;      // work lists of the z-marching per-node SpMV (beat_pde_vrr.hip), or nullptr
   void* vtl = nullptr;      // tiles and lane masks of the workgroup-tile per-node SpMV (beat_pde_vtl.hip), or nullptr
   bool small_enabled = true;  // grids of a few thousand nodes: whole solve in one launch (beat_pde_small.hip)
@@ -268,22 +244,11 @@ int beat_var_pupdate_oop(beat_pde* pde, double* dev_st, const double* dev_r, con
 int beat_var_flush(beat_pde* pde, const double* dev_st, double* dev_x, const double* dev_ring0, int64_t field_stride,
                    int ring_base, int only_if_full, const beat_pde_detail::GuessTerms& gt);
 
-// initial-guess bookkeeping (beat_pde.hip).  A solve path that supports the guess calls beat_guess_begin before its
-// right-hand side, passes beat_guess_terms(pde, ring_base) to every x update and ends with beat_guess_end; every
-// other path calls beat_guess_skip (the history does not survive a solve that did not record its increment).
-void beat_guess_begin(beat_pde* pde);
-void beat_guess_skip(beat_pde* pde);
-beat_pde_detail::GuessTerms beat_guess_terms(const beat_pde* pde, int ring_base);
-// nupd = executed updates; returns true when an application (e and/or the last partial ring cycle) is still due
-bool beat_guess_end(beat_pde* pde, int nupd, bool deferred);
+// the x update of a deferred-x solve with the guess's terms for that ring cycle (beat_guess_state::terms, take_pending)
 int beat_pde_x_flush_terms(beat_pde* pde, const double* dev_st, double* dev_x, const double* dev_ring0, int64_t field_stride,
                            int ring_base, int only_if_full, const beat_pde_detail::GuessTerms& gt);
 // behind iteration i of the open solve's deferred-x loop: the x update above when that iteration filled the ring, else nothing
 int beat_flush_if_ring_full(beat_pde* pde, int i);
-
-void beat_guess_advance(beat_pde* pde);
-void beat_guess_observe(beat_pde* pde, int iterations);  // of the solve that just ended (adaptive order)
-int beat_guess_policy(beat_pde* pde);                     // hill-climbing move; returns the order to prepare next  // this solve's increment has been recorded: it is the most recent one now
 
 // per-node-coefficient SpMV that marches along z and loads only the forward half of each row (beat_pde_vrr.hip)
 int beat_vrr_setup(beat_pde* pde, const std::vector<unsigned long long>& host_tissue_flags);

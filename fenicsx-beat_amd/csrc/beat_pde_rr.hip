@@ -794,7 +794,7 @@ bool beat_rr_available(const beat_pde* pde) {
 int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
                 int n_stim, double* dev_x, double* dev_r, double* dev_st, int part, const PcgStart* start) {
   BEAT_REQUIRE(start == nullptr || part < 0, "only a right-hand side in one part starts the solve");
-  const GuessTerms& gt = pde->guess;
+  const GuessTerms& gt = pde->guess.cur;
   const bool guess = gt.d != nullptr && gt.use_e;
   // with a guess the kernel holds two register windows (v_ and e): 2 rows per wave keep it at the other kernels' occupancy
   static const int guess_rows = [] {  // BEAT_RR_GUESS_RY = 2 | 4 (experiments)

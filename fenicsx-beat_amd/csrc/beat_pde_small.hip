@@ -274,15 +274,15 @@ bool beat_small_available(const beat_pde* pde) {
   return small_lds_bytes(pde, small_margin(pde)) <= (size_t)150 * 1024;
 }
 
-// Enqueue one solve (initial-guess terms taken with beat_guess_begin, scalar results to dev_st[0..16)); no
-// synchronisation: the caller reads dev_st back when it wants to and calls beat_guess_advance (after
-// beat_guess_observe, if it has the iteration count by then).
+// Enqueue one solve (initial-guess terms taken with beat_guess_state::begin, scalar results to dev_st[0..16)); no
+// synchronisation: the caller reads dev_st back when it wants to and calls the guess's advance() (after
+// observe(), if it has the iteration count by then).
 int beat_small_launch(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w,
                       const double* host_stim_amp, int n_stim, double* dev_x, double rtol, double atol, int max_it,
                       double* dev_st) {
   BEAT_REQUIRE(pde->have_dt, "beat_pde_set_timestep has not been called");
   BEAT_REQUIRE(n_stim >= 0 && n_stim <= BEAT_MAX_STIM, "at most %d stimuli", BEAT_MAX_STIM);
-  BEAT_REQUIRE(!pde->guess_pending, "the previous solve's deferred update has not been applied");
+  BEAT_REQUIRE(!pde->guess.pending, "the previous solve's deferred update has not been applied");
   const Geom& f = pde->g;
   SmallArgs a{};
   a.nx = f.nx;
@@ -302,8 +302,8 @@ int beat_small_launch(beat_pde* pde, const double* dev_v_prev, const double* con
   a.rtol = rtol;
   a.atol = atol;
   a.max_it = max_it;
-  beat_guess_begin(pde);
-  a.gt = pde->guess;
+  pde->guess.begin();
+  a.gt = pde->guess.cur;
   a.st = dev_st;
   const size_t lds = small_lds_bytes(pde, a.margin);
   const int per_thread = (a.n + SMALL_THREADS - 1) / SMALL_THREADS;
@@ -347,9 +347,9 @@ int beat_small_solve(beat_pde* pde, const double* dev_v_prev, const double* cons
   double* h = pde->ctx->h_pinned;
   BEAT_HIP_CHECK(hipMemcpyAsync(h, pde->d_st, sizeof(double) * 16, hipMemcpyDeviceToHost, s));
   BEAT_HIP_CHECK(hipStreamSynchronize(s));
-  if (pde->guess.d != nullptr) {  // the kernel recorded this solve's increment
-    beat_guess_observe(pde, (int)h[ITERS]);
-    beat_guess_advance(pde);
+  if (pde->guess.cur.d != nullptr) {  // the kernel recorded this solve's increment
+    pde->guess.observe((int)h[ITERS]);
+    pde->guess.advance();
   }
   const beat_ksp_info k = beat_pcg_info(h);
   pde->last_iters = k.iterations;

@@ -7,6 +7,7 @@ the x0 = v_ iteration within that tolerance and with a sparse direct solve, the 
 (it rides with the deferred update), and all it changes is the iteration count.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
@@ -146,6 +147,53 @@ def test_guess_on_a_masked_domain_with_per_node_rows(hip_ctx, defer):
         for step in range(9):
             np.testing.assert_array_equal(sols[order][step][outside], _moving_bump(mesh, 0.02 * step)[outside])
     assert totals[4] <= totals[3] < totals[2] < totals[1] < totals[0], totals
+
+
+def _read(hip_ctx, ops, ptr, n):
+    from beat import _hip
+
+    out = hip_ctx.torch.empty(n, dtype=hip_ctx.torch.float64, device=hip_ctx.device)
+    _hip.check(ops.lib.beat_copy(hip_ctx.handle, C.c_void_p(out.data_ptr()), C.c_void_p(ptr), n))
+    return out.cpu().numpy()
+
+
+@pytest.mark.parametrize("rtol,orders", [(1e-8, (1, 2, 3, 4)), (1e-13, (3,))])
+def test_device_fields_are_what_the_host_bookkeeping_says(hip_ctx, rtol, orders):
+    """After every solve the device's e is the extrapolation through the increments the host counts: e = sum_{i=1..m}
+    (-1)^(i+1) C(m, i) d_i, m = min(order, count), with d_i the recorded increments as read from the device after each
+    solve, and count = min(4, solves since the history was last dropped).  Per node the difference is bounded by
+    4 eps sum |C(m, i)| |d_i|: the chain a inc, then one fma per older increment, is at most four roundings, each bounded
+    by eps times the running magnitude.  rtol = 1e-13: a solve takes more iterations than the ring holds, so its
+    increment is recorded in several cycles (the later ones accumulate into d and e)."""
+    cells = (12, 10, 8)
+    mesh, M, _, _ = _system(cells)
+    n = mesh.num_nodes
+    eps = np.finfo(np.float64).eps
+    for order in orders:
+        for defer in (False, True):
+            ops = _ops(hip_ctx, cells, M, order)
+            fv, fx = ops.new_field(), ops.new_field()
+            incs, its = [], []  # the increments on record, newest first
+            for step in range(8):
+                if step == 5:
+                    ops.guess_reset()
+                    incs = []
+                    assert _history(ops)[2] == 0
+                fv.set(_moving_bump(mesh, 0.02 * step))
+                res = ops.solve_single(fv, [], [], fx, rtol, 1e-50, 500, defer_flush=defer)
+                assert res.converged_reason > 0
+                its.append(res.iterations)
+                ops.flush_pending()
+                h0, h1, cnt = _history(ops)
+                incs.insert(0, _read(hip_ctx, ops, h0, n))
+                assert cnt == min(4, len(incs)), (order, defer, step)
+                m = min(order, cnt)
+                terms = [(-1) ** (i + 1) * math.comb(m, i) * incs[i - 1] for i in range(1, m + 1)]
+                e = _read(hip_ctx, ops, h1, n)
+                err, bound = np.abs(e - sum(terms)), 4 * eps * sum(np.abs(t) for t in terms)
+                assert np.abs(incs[0]).max() > 0 and (err <= bound).all(), (order, defer, step, (err - bound).max())
+            if rtol < 1e-12:
+                assert max(its) > 6  # several ring cycles per solve
 
 
 def test_guess_that_already_solves_the_system(hip_ctx, small_grid_path):
