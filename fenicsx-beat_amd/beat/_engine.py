@@ -458,6 +458,14 @@ class HipOps:
         """True when solves of this operator run as one launch of one workgroup (and beat_split_steps accepts it)."""
         return bool(self.lib.beat_pde_small_grid_solve_active(self.handle))
 
+    RR_ROUTE_KEYS = ("available", "ry", "pd", "by_rows_mask", "nsegx", "nrb", "zc", "nchunks", "total_blocks", "guess_ry")
+
+    def rr_route(self) -> dict:
+        """The register-row instance this operator's iteration runs and its whole-slab launch geometry (beat_pde_rr_route)."""
+        out = (C.c_int * len(self.RR_ROUTE_KEYS))()
+        _hip.check(self.lib.beat_pde_rr_route(self.handle, out))
+        return {k: int(v) for k, v in zip(self.RR_ROUTE_KEYS, out)}
+
     def guess_traffic(self) -> dict:
         """Fields the last solve's x update reads / writes for the initial guess (beat_pde_guess_traffic)."""
         out = (C.c_int * 4)()

@@ -690,6 +690,16 @@ int rr_prefetch() {  // planes fetched ahead of their use (BEAT_RR_PD = 1, 2 or 
   return pd;
 }
 
+// with a guess the right-hand side holds two register windows (v_ and e): 2 rows per wave keep it at the other kernels' occupancy
+int rr_guess_rows() {  // BEAT_RR_GUESS_RY = 2 | 4 (experiments)
+  static const int rows = [] {
+    const char* e = std::getenv("BEAT_RR_GUESS_RY");
+    const int v = e ? std::atoi(e) : 2;
+    return v == 4 ? 4 : 2;
+  }();
+  return rows;
+}
+
 // Decomposition of the planes [z_lo, z_hi) of the slab into waves; block partials are written from slot part_off on.
 // BEAT_RR_BY_ROWS: bit m set = launches of MODE m put the four waves of a block on four adjacent row blocks (RGeom::nrg)
 int rr_by_rows_mask() {
@@ -790,19 +800,30 @@ bool beat_rr_available(const beat_pde* pde) {
   return (int64_t)grid_blocks(g) + 2 * grid_blocks(gb) <= BEAT_MAX_PARTIALS;
 }
 
+// What the register-row loop of this operator would launch now (tests assert the instance they mean to check): read only.
+extern "C" int beat_pde_rr_route(const beat_pde* pde, int* host_out) {
+  BEAT_REQUIRE(pde != nullptr && host_out != nullptr, "null argument");
+  const RGeom g = make_geom(pde, 0, pde->g.nz, 0, 0, RR_PDOT);
+  host_out[0] = beat_rr_available(pde) ? 1 : 0;
+  host_out[1] = g.ry;
+  host_out[2] = rr_prefetch();
+  host_out[3] = rr_by_rows_mask();
+  host_out[4] = g.nsegx;
+  host_out[5] = g.nrb;
+  host_out[6] = g.zc;
+  host_out[7] = g.nchunks;
+  host_out[8] = g.total_blocks;
+  host_out[9] = rr_guess_rows();
+  return BEAT_OK;
+}
+
 // Right-hand side in residual form (see beat_pde_rhs) without the p output.
 int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* host_dev_stim_w, const double* host_stim_amp,
                 int n_stim, double* dev_x, double* dev_r, double* dev_st, int part, const PcgStart* start) {
   BEAT_REQUIRE(start == nullptr || part < 0, "only a right-hand side in one part starts the solve");
   const GuessTerms& gt = pde->guess.cur;
   const bool guess = gt.d != nullptr && gt.use_e;
-  // with a guess the kernel holds two register windows (v_ and e): 2 rows per wave keep it at the other kernels' occupancy
-  static const int guess_rows = [] {  // BEAT_RR_GUESS_RY = 2 | 4 (experiments)
-    const char* e = std::getenv("BEAT_RR_GUESS_RY");
-    const int v = e ? std::atoi(e) : 2;
-    return v == 4 ? 4 : 2;
-  }();
-  const int rows = guess ? guess_rows : 0;
+  const int rows = guess ? rr_guess_rows() : 0;
   RArgs a{};
   a.x = dev_v_prev;
   a.y = dev_r;

@@ -391,6 +391,12 @@ int beat_pde_fused_dist_pass(const beat_pde* pde);
  * workgroup-tile product (beat_pde_spmv_dot and the solves), bit 1 its fused pass (direction formed while loading), bit 2 the
  * right-hand side on the tiles, bit 3 the ring of 12 search directions.  0 for a constant-coefficient operator. */
 int beat_pde_tile_route(const beat_pde* pde);
+/* Which instance of the register-row kernels a constant-coefficient operator runs, for the whole-slab geometry of the pass that
+ * forms the direction and sums p.Ap as it would be launched now (BEAT_RR_BLOCKS is read per call): host_out[10] = {1 if the
+ * register-row loop is available (0: the LDS-tiled loop solves; always 0 for per-node rows), rows per wave (2 or 4), planes in
+ * flight (1..3), the BEAT_RR_BY_ROWS mask, x segments, row blocks, planes per z-chunk, z-chunks, workgroups, rows per wave of a
+ * right-hand side with an initial guess}.  Reads only: no solve is affected. */
+int beat_pde_rr_route(const beat_pde* pde, int* host_out);
 int beat_pde_guess_reset(beat_pde* pde);
 int beat_pde_guess_pending(const beat_pde* pde);
 /* the last recorded increment, the guess increment prepared for the next solve, and the number of solves on record

@@ -1,0 +1,148 @@
+"""The host PCG of tests/_pcg_ref.py held to account, and the conditions its cases must meet for tests/test_rr_iterates_gpu.py to
+mean what it says: the reference converges to a direct solve and counts like oracle/fem.pcg_jacobi, no stop is a near tie (so
+the device's iteration count can be asked to EQUAL the host's), every cut happens while the iterate still moves, and every
+bound is positive."""
+import numpy as np
+import pytest
+import scipy.sparse.linalg as spla
+
+import _pcg_ref as ref
+from oracle import fem
+
+SHAPES = list(ref.SHAPES)
+
+
+def test_longdouble_has_a_64_bit_mantissa():
+    assert np.finfo(np.longdouble).nmant >= 63
+
+
+def test_case_table_is_consistent():
+    assert set(ref.CHUNK_SHAPES) <= set(ref.SHAPES) and set(ref.GUESS_SHAPES) <= set(ref.SHAPES)
+    assert len({ref.seed_of(s) for s in ref.SHAPES}) == len(ref.SHAPES)
+    assert max(int(np.prod(s)) for s in ref.SHAPES) <= 8192  # a few thousand nodes: where the index arithmetic branches, not the workload
+    for s in ref.SHAPES:
+        v = ref.field(s)
+        assert abs(v.mean()) < 1e-12 and 0.1 < np.abs(v).max() < 10.0
+        assert np.array_equal(v, ref.field(s))  # fixed seeds
+
+
+def test_matvec_matches_scipy_and_gains_precision():
+    p = ref.problem((65, 3, 5))
+    x = ref.field(p.shape)
+    y64 = ref.matvec(p.A, x, np.float64)
+    yL = ref.matvec(p.A, x.astype(np.longdouble), np.longdouble)
+    scale = np.abs(p.A).dot(np.abs(x)).max()
+    assert np.abs(y64 - p.A @ x).max() <= 8 * 2.0**-53 * scale
+    # one row in exact rational arithmetic
+    from fractions import Fraction
+
+    row = 567
+    sl = slice(p.A.indptr[row], p.A.indptr[row + 1])
+    exact = sum(Fraction(float(a)) * Fraction(float(b)) for a, b in zip(p.A.data[sl], x[p.A.indices[sl]]))
+    hi = float(yL[row])
+    got = Fraction(hi) + Fraction(float(yL[row] - np.longdouble(hi)))
+    assert abs(got - exact) <= Fraction(2.0**-60 * scale)
+    assert abs(Fraction(float(y64[row])) - exact) <= Fraction(8 * 2.0**-53 * scale)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=ref.shape_key)
+def test_expanded_tables_are_the_assembled_matrices(shape):
+    """The matrices of a case -- oracle/fem's per-node-type tables, which the device is given, expanded over the box -- are the
+    P1 matrices assembled on the whole mesh, an axis of one node 'interior' with its neighbours outside the box, up to the last
+    digits (in which the assembled entries differ from node to node); and the product's own tables agree with them as closely."""
+    from beat import _stencil
+
+    p = ref.problem(shape)
+    mass, stiff, _ = ref.assembled(shape)
+    noise = 4 * max(shape) * 2.0**-53  # the assembly takes a cell's geometry from its nodes' coordinates: u * coordinate / h
+    for mine, theirs in ((p.mass, mass), (p.stiff, stiff)):
+        assert abs(mine - theirs).max() <= noise * abs(theirs).max()
+    mt, kt = _stencil.stencil_tables(p.dim, (ref.H,) * p.dim, ref.conductivity(p.dim))
+    assert np.abs(mt - p.mass_tab).max() <= 64 * 2.0**-53 * np.abs(mt).max() and np.abs(kt - p.stiff_tab).max() <= 64 * 2.0**-53 * np.abs(kt).max()
+    x = ref.field(shape)
+    np.testing.assert_allclose(p.A @ x, fem.apply_stencil(ref.C_M * p.mass_tab + ref.THETA * ref.DT * p.stiff_tab, shape, x), rtol=0,
+                               atol=8 * 2.0**-53 * np.abs(p.A).dot(np.abs(x)).max())
+    assert (p.A != p.A.T).nnz == 0 or abs(p.A - p.A.T).max() <= 8 * 2.0**-53 * abs(p.A).max()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=ref.shape_key)
+def test_reference_is_right_and_no_stop_is_a_near_tie(shape):
+    p, r = ref.problem(shape), ref.plain_reference(shape)
+    v = ref.field(shape)
+    bL = ref.rhs_longdouble(p, v)
+    # the right-hand side: the float64 form of the same expression
+    b64 = ref.C_M * (p.mass @ v) - (1 - ref.THETA) * ref.DT * (p.stiff @ v) + ref.DT * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights))
+    assert np.abs(bL.astype(np.float64) - b64).max() <= 16 * 2.0**-53 * np.abs(b64).max()
+    assert float(r.bL) == pytest.approx(np.linalg.norm(b64), rel=1e-14)
+    # converged: the direct solve
+    x = spla.spsolve(p.A.tocsc(), bL.astype(np.float64))
+    assert np.abs(r.xL[r.kmax].astype(np.float64) - x).max() <= 1e-12 * np.abs(x).max()
+    for rtol in ref.RTOLS:
+        k = r.stop(rtol)
+        _, its, _ = fem.pcg_jacobi(p.A, b64, v.copy(), rtol=rtol, atol=1e-300, maxit=ref.KMAX)
+        assert its == k, (rtol, its, k)
+        thr = np.longdouble(rtol) * r.bL
+        assert r.rL[k] <= thr * (1 - 1e-6), (rtol, k, float(r.rL[k] / thr))
+        below = r.rL[k - 1] if k > 1 else None
+        if below is not None:
+            assert below >= thr * (1 + 1e-6), (rtol, k, float(below / thr))
+        assert k < ref.KMAX - 5 and k <= r.kmax
+    # every cut happens before convergence: the iterate it is compared with is still moving.  The one exception there can be is
+    # (1, 1, 7): CG on 7 unknowns ends with its 7th step, so the cut at 7 compares the solution itself; its cuts below 7 move.
+    if p.n > max(ref.CUTS):
+        assert r.rL[max(ref.CUTS)] > np.longdouble(1e-12) * r.bL
+    else:
+        assert shape == (1, 1, 7)
+        assert r.rL[p.n - 1] > np.longdouble(1e-12) * r.bL and r.rL[p.n] <= np.longdouble(1e-12) * r.bL
+    assert r.stop(ref.RTOLS[0]) >= 1
+    for k in ref.CUTS:
+        assert r.x_bound(k) > 0.0 and r.residual_bound(k) > 0.0 and np.isfinite(r.x_bound(k))
+        assert r.delta(k) > 0.0 or r.x_floor(k) > 0.0
+        assert r.x_bound(k) <= 1e-12 * max(1.0, np.abs(r.xL[k]).max())  # the yardstick is rounding error, nothing coarser
+    assert r.rhs_norm_bound() > 0.0
+
+
+@pytest.mark.parametrize("shape", ref.GUESS_SHAPES, ids=ref.shape_key)
+def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(shape):
+    """The fields of the guess cases with exact increments in place of the device's: the extrapolated start is still O(1) wrong, so
+    the cut iterates (k = 1, 3) are far from converged."""
+    p = ref.problem(shape)
+    solve = spla.factorized(p.A.tocsc())
+    incs = []
+    for j in range(1, ref.GUESS_SOLVES + 1):
+        v = ref.field(shape, j)
+        incs.insert(0, solve(ref.rhs_longdouble(p, v).astype(np.float64)) - v)
+    v = ref.field(shape, ref.GUESS_SOLVES + 1)
+    bL = ref.rhs_longdouble(p, v)
+    for order in ref.GUESS_ORDERS:
+        e = ref.guess_increment(order, incs)
+        expect = {1: incs[0], 3: 3 * incs[0] - 3 * incs[1] + incs[2]}[order]
+        np.testing.assert_allclose(e.astype(np.float64), expect, rtol=0, atol=1e-14 * np.abs(expect).max())
+        r = ref.reference(p, bL, v.astype(np.longdouble) + e, max(ref.GUESS_CUTS))
+        assert r.rL[max(ref.GUESS_CUTS)] > np.longdouble(1e-12) * r.bL
+        assert r.rL[1] > np.longdouble(1e-3) * r.bL  # the guess did not all but solve it
+        for k in ref.GUESS_CUTS:
+            assert r.x_bound(k) > 0.0
+
+
+def test_single_reduction_recurrence_gives_the_same_iterates():
+    """Chronopoulos & Gear's step lengths (rr_merged_next_kernel's expressions), in longdouble: the iterates of the classic loop."""
+    L = np.longdouble
+    shape = (65, 3, 5)
+    p, r = ref.problem(shape), ref.plain_reference(shape)
+    v = ref.field(shape).astype(L)
+    b = ref.rhs_longdouble(p, ref.field(shape))
+    A = p.operator(L)
+    dinv = L(1) / (L(ref.C_M) * p.mass.diagonal().astype(L) + L(ref.THETA) * L(ref.DT) * p.stiff.diagonal().astype(L))
+    x, res = v.copy(), b - ref.matvec(A, v, L)
+    pdir, alpha, g_old = np.zeros_like(x), L(0), L(0)
+    for k in range(1, 9):
+        u = dinv * res
+        g, d = res @ u, u @ ref.matvec(A, u, L)
+        beta = L(0) if k == 1 else g / g_old
+        alpha = g / d if k == 1 else g / (d - beta * g / alpha)
+        pdir = u + beta * pdir
+        x = x + alpha * pdir
+        res = res - alpha * ref.matvec(A, pdir, L)
+        g_old = g
+        assert np.abs(x - r.xL[k]).max() <= 2.0**-56 * np.abs(r.xL[k]).max(), k
