@@ -30,6 +30,7 @@ MATH_OUT = (1, 1, 1, 1, 1, 1, 2, 3, 4, 2, 3, 4, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1)
 MAX_STIM = 8
 MAX_CLASSES = 32
 MAX_LEADS = 16  # BEAT_MAX_LEADS: rows per beat_field_leads call
+MAX_MONITORS = 32  # BEAT_MAX_MONITORS: monitored values per beat_ode_monitor launch
 
 # slots of the PCG scalar state (see include/beat_hip.h)
 ST_BB, ST_RZ, ST_RR, ST_PQ, ST_RZN, ST_RRN, ST_TOL2, ST_BETA, ST_STOP, ST_ITERS, ST_REASON = range(11)
@@ -97,6 +98,8 @@ SIGNATURES = {
     "beat_ode_class_table_fill": (_int, [_vp, _int, _vp, _int, _int, _vp]),
     "beat_ode_step_classes": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _int, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _i64, _int]),
     "beat_ode_run": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64, _dbl, _dbl, _i64, _int, _int, _vp, _int, _vp]),
+    "beat_ode_monitor_register": (_int, [_int, C.c_char_p, C.c_char_p, _int, C.POINTER(_int)]),
+    "beat_ode_monitor": (_int, [_vp, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64, _vp, _int, _vp, _dbl, _vp, _i64]),
     "beat_copy": (_int, [_vp, _vp, _vp, _i64]),
     "beat_fill": (_int, [_vp, _vp, _dbl, _i64]),
     "beat_stream_probe": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _int, _i64]),

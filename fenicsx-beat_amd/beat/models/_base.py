@@ -63,6 +63,11 @@ class DeviceModel:
             d[k] = v
         return np.array([d[k] for k in self.parameter_names], dtype=np.float64)
 
+    def monitor_values(self, t, states, parameters, names=None):
+        """gotranx's ``monitor_values``: only a model generated from an ``.ode`` file has it."""
+        raise NotImplementedError(f"{self.name} is a hand-written kernel whose intermediates are not kept by name: "
+                                  "use beat.models.from_ode on the model's .ode file to monitor its currents")
+
     # ---- the reference's `fun` calling convention ---------------------------------------------
     def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
         """Advance ``states`` ((S,) or (S, N) NumPy) by one step on the GPU; returns a new array."""

@@ -19,6 +19,11 @@ The same expressions, lambdified for NumPy, are the handle's HOST evaluation (``
 with, and what runs where no GPU / compiler is to be had.  Parameters: a (P,) vector or per node (P, N); what a generated model
 does not get is the instance compiled for a FEW varying rows (beat_ode_step_rows: a (P, N) array of a generated model is read
 whole, or runs as classes when its columns are few).  SymPy is needed (it is what gotranx itself builds on).
+
+Every assignment of the file -- currents, fluxes, rates, the ``d<state>_dt`` -- stays available by name, as in a gotranx module:
+``monitor_names`` / ``monitor_index(name)`` / ``monitor_values(t, states, parameters, names)``.  For a selection of names a second
+struct is printed (``_monitor_cxx``: same printer, common subexpressions over the selection alone) and evaluated by a read-only
+kernel over the state array (``ode_monitor_kernel``, ``beat_ode_monitor``); ``numpy_monitor`` is its host twin.
 """
 
 from __future__ import annotations
@@ -30,7 +35,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ._base import DeviceModel
+from ._base import DeviceModel, host_and_device_parameters
 
 _SCHEMES = ("generalized_rush_larsen", "forward_euler")
 # gotranx's own names for the same two schemes (gotranx.schemes: what its code generator is asked for)
@@ -208,7 +213,7 @@ class OdeFileModel(DeviceModel):
                    "_indicator": lambda c: sympy.Piecewise((sympy.Integer(1), c), (sympy.Integer(0), True))})
         ns.update(psym)
         ns.update(ysym)
-        rhs, line = {}, {}
+        rhs, line, assigned = {}, {}, {}
         for nm, node in assigns:
             _check_expression(node, str(self.path), set(_FUNCTIONS))
             node = ast.fix_missing_locations(_ComparisonsAsNumbers(str(self.path)).visit(node))
@@ -216,7 +221,7 @@ class OdeFileModel(DeviceModel):
                 expr = sympy.sympify(eval(compile(ast.Expression(node), str(self.path), "eval"), {"__builtins__": {}}, ns))
             except Exception as exc:  # noqa: BLE001
                 raise ValueError(f"{self.path}: cannot turn `{nm} = ...` into an expression: {exc}") from exc
-            ns[nm] = expr
+            ns[nm] = assigned[nm] = expr
             if nm.startswith("d") and nm.endswith("_dt") and nm[1:-3] in states:
                 rhs[nm[1:-3]], line[nm[1:-3]] = expr, node.lineno
         missing = [s for s in states if s not in rhs]
@@ -230,6 +235,12 @@ class OdeFileModel(DeviceModel):
         repl, red = sympy.cse(f + J, symbols=sympy.numbered_symbols("x_"), optimizations="basic")
         self._sym = dict(y=[ysym[s] for s in names], p=[psym[p] for p in params], t=tsym, dt=dtsym, repl=repl,
                          f=red[: len(names)], J=red[len(names):])
+        # every assignment of the file, in dependency order: what monitor_values / numpy_monitor can be asked for
+        self.monitor_names = tuple(assigned)
+        self._mon_expr = assigned
+        self._mon_numpy_fn = None
+        self._monitors = {}       # names of one launch -> the library's monitor id (beat_ode_monitor_register), once self-checked
+        self._stem = stem
         self._numpy_fn = None
         self._registered = None   # the library's id, once the compiled kernel has passed _self_check
         self._library_id = None   # the id beat_ode_model_register gave (the source is handed over once per process)
@@ -252,10 +263,10 @@ class OdeFileModel(DeviceModel):
         return j
 
     # ------------------------------------------------------------------------------------------------ C++
-    def _cxx(self, stem: str) -> str:
+    def _printer(self):
+        """The C++ printer of the generated code (the step's and the monitors') and the list it notes a use of ``%`` in."""
         import os
 
-        import sympy
         from sympy.printing.c import C99CodePrinter
 
         class Printer(C99CodePrinter):
@@ -293,23 +304,14 @@ class OdeFileModel(DeviceModel):
 
         # exp(): the library's table-driven evaluation (FastMath::exp of csrc/ionic_models.h, what the shipped models use: 13 VALU
         # instructions, <= 1 ulp, the 256-entry table in LDS) with the argument kept inside double range -- or libm's
-        exp_name = "fexp" if self.fast_exp else "exp"
         uses_mod = []
-        pr = Printer({"contract": False, "user_functions": {"exp": exp_name}})
-        y, p = self._sym["y"], self._sym["p"]
-        sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
-        sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-        sub[self._sym["t"]] = sympy.Symbol("t")
-        used = set()
-        ns_, np_ = len(y), len(p)
-        vi = self.state_index(self.v_name) if self.v_name else 0
-        # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
-        # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
-        # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
-        # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
-        # per lane that way.)
-        temp = {lhs: e.xreplace(sub) for lhs, e in self._sym["repl"]}
-        emitted, lines = set(), []
+        return Printer({"contract": False, "user_functions": {"exp": "fexp" if self.fast_exp else "exp"}}), uses_mod
+
+    @staticmethod
+    def _emitter(temp, pr, lines):
+        """``emit(expr)``: the common subexpressions ``expr`` needs and that are not out yet, appended to ``lines`` depth first --
+        a temporary is defined next to its first use -- and the set of those emitted so far."""
+        emitted = set()
 
         def emit(expr):
             stack = [(sym, False) for sym in sorted(expr.free_symbols, key=str, reverse=True) if sym in temp]
@@ -325,6 +327,44 @@ class OdeFileModel(DeviceModel):
                 for dep in sorted(temp[sym].free_symbols, key=str, reverse=True):
                     if dep in temp and dep not in emitted:
                         stack.append((dep, False))
+
+        return emit, emitted
+
+    def _cxx_helpers(self, uses_mod) -> str:
+        """The lambdas the printed expressions call (fexp, beat_sel, beat_mod), as the first lines of a generated function body."""
+        return (("    // (what libm / NumPy give everywhere: NaN stays NaN, overflow is inf, underflow goes through the subnormals to 0)\n"
+                 "    // (k = round(x 256 / ln 2) must fit 32 bits: the clamp; inside it v_ldexp_f64 underflows to 0 through the subnormals and\n"
+                 "    // overflows to inf as libm does; the clamp turns a NaN argument into a number, hence the select)\n"
+                 "    const auto fexp = [&fm](double x) { const double e = fm.exp(fmin(fmax(x, -1.0e6), 1.0e3)); return x != x ? x : e; };\n" if self.fast_exp else "")
+                + "    const auto beat_sel = [](bool c, double a, double b) { return c ? a : b; };\n"
+                + ("    // (a % b with Python's and NumPy's meaning: fmod's result moved by b where it has the other sign; a zero takes b's sign)\n"
+                   "    const auto beat_mod = [](double a, double b) {\n"
+                   "      const double m = fmod(a, b);\n"
+                   "      return m != 0.0 ? ((m < 0.0) != (b < 0.0) ? m + b : m) : copysign(0.0, b);\n"
+                   "    };\n" if uses_mod else ""))
+
+    def _cxx(self, stem: str) -> str:
+        import os
+
+        import sympy
+
+        exp_name = "fexp" if self.fast_exp else "exp"
+        pr, uses_mod = self._printer()
+        y, p = self._sym["y"], self._sym["p"]
+        sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
+        sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
+        sub[self._sym["t"]] = sympy.Symbol("t")
+        used = set()
+        ns_, np_ = len(y), len(p)
+        vi = self.state_index(self.v_name) if self.v_name else 0
+        # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
+        # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
+        # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
+        # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
+        # per lane that way.)
+        temp = {lhs: e.xreplace(sub) for lhs, e in self._sym["repl"]}
+        lines = []
+        emit, emitted = self._emitter(temp, pr, lines)
 
         order = list(range(ns_))
         if os.environ.get("BEAT_ODE_V_LAST", "1") == "1" and self.v_name:  # the potential's equation sums every current: last, when the currents exist
@@ -363,27 +403,57 @@ class OdeFileModel(DeviceModel):
                 "  template <class P> __host__ __device__ static Derived derive(const P&) { return Derived{0.0}; }\n"
                 "  template <class IO, class P>\n"
                 "  __device__ static __forceinline__ void step(const IO& io, const P& p, const Derived&, const FastMath& fm, double t, double dt) {\n"
-                + ("    // (what libm / NumPy give everywhere: NaN stays NaN, overflow is inf, underflow goes through the subnormals to 0)\n"
-                   "    // (k = round(x 256 / ln 2) must fit 32 bits: the clamp; inside it v_ldexp_f64 underflows to 0 through the subnormals and\n"
-                   "    // overflows to inf as libm does; the clamp turns a NaN argument into a number, hence the select)\n"
-                   "    const auto fexp = [&fm](double x) { const double e = fm.exp(fmin(fmax(x, -1.0e6), 1.0e3)); return x != x ? x : e; };\n" if self.fast_exp else "")
-                + "    const auto beat_sel = [](bool c, double a, double b) { return c ? a : b; };\n"
-                + ("    // (a % b with Python's and NumPy's meaning: fmod's result moved by b where it has the other sign; a zero takes b's sign)\n"
-                   "    const auto beat_mod = [](double a, double b) {\n"
-                   "      const double m = fmod(a, b);\n"
-                   "      return m != 0.0 ? ((m < 0.0) != (b < 0.0) ? m + b : m) : copysign(0.0, b);\n"
-                   "    };\n" if uses_mod else "")
+                + self._cxx_helpers(uses_mod)
                 + "\n".join(loads + pl + lines + body) + "\n  }\n};\n")
 
-    # ------------------------------------------------------------------------------------------------ NumPy
-    def numpy_step(self, states, t, parameters, dt):
-        """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``)."""
+    def _monitor_cxx(self, names):
+        """(struct name, source) of ``Mon_<stem>_<digest>`` for csrc/beat_ode_kernel.h's ode_monitor_kernel: the assignments ``names``
+        (at most _hip.MAX_MONITORS) evaluated from the node's states and parameters and stored to output rows 0 .. M-1.  Common
+        subexpressions are eliminated over the SELECTION alone; printer, helpers and the order -- a temporary next to its first
+        use, an output stored as soon as it is final -- are the step's; only the states and parameters the selection uses are
+        loaded."""
         import sympy
 
-        if self._numpy_fn is None:
-            s = self._sym
-            # (the common subexpressions found at construction are handed to lambdify as they are: local assignments in the generated function)
-            self._numpy_fn = sympy.lambdify(s["y"] + s["p"] + [s["t"]], [s["f"], s["J"]], "numpy", cse=lambda exprs: (s["repl"], exprs))
+        pr, uses_mod = self._printer()
+        y, p = self._sym["y"], self._sym["p"]
+        sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
+        sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
+        sub[self._sym["t"]] = sympy.Symbol("t")
+        repl, red = sympy.cse([self._mon_expr[nm] for nm in names], symbols=sympy.numbered_symbols("x_"), optimizations="basic")
+        temp = {lhs: e.xreplace(sub) for lhs, e in repl}
+        lines = []
+        emit, emitted = self._emitter(temp, pr, lines)
+        used = set()
+        for j, e in enumerate(red):
+            ej = sympy.sympify(e).xreplace(sub)
+            emit(ej)
+            used |= ej.free_symbols
+            lines.append(f"    out.store({j}, {pr.doprint(ej)});  // {names[j]}")
+        for e in emitted:
+            used |= temp[e].free_symbols
+        loads = [f"    const double y_{k} = io.load({k});" for k in range(len(y)) if sympy.Symbol(f"y_{k}") in used]
+        pl = [f"    const double p_{k} = p[{k}];" for k in range(len(p)) if sympy.Symbol(f"p_{k}") in used]
+        digest = hashlib.sha1("\n".join(loads + pl + lines).encode()).hexdigest()[:12]
+        name = f"Mon_{self._stem}_{digest}"
+        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {len(y)} states read\n"
+                      f"struct {name} {{\n"
+                      f"  static constexpr int NS = {len(y)}, NP = {max(len(p), 1)}, NM = {len(names)};\n"
+                      "  template <class IO, class P, class OUT>\n"
+                      "  __device__ static __forceinline__ void eval(const IO& io, const P& p, const FastMath& fm, double t, const OUT& out) {\n"
+                      + self._cxx_helpers(uses_mod)
+                      + "\n".join(loads + pl + lines) + "\n  }\n};\n")
+
+    def monitor_sources(self, names=None):
+        """[(struct name, source, names)] -- one per launch: ``names`` (None: all) in runs of at most _hip.MAX_MONITORS."""
+        from .. import _hip
+
+        names = self._monitor_selection(names)
+        return [self._monitor_cxx(names[k:k + _hip.MAX_MONITORS]) + (tuple(names[k:k + _hip.MAX_MONITORS]),)
+                for k in range(0, len(names), _hip.MAX_MONITORS)]
+
+    # ------------------------------------------------------------------------------------------------ NumPy
+    def _numpy_args(self, states, t, parameters):
+        """(states as (S, N), the arguments of a lambdified function over y + p + [t], whether ``states`` was (S,))."""
         y = np.asarray(states, dtype=np.float64)
         one_d = y.ndim == 1
         y2 = y.reshape(y.shape[0], -1)
@@ -394,8 +464,36 @@ class OdeFileModel(DeviceModel):
         # would otherwise be a reduction over a ragged pair)
         n = y2.shape[1]
         pn = [np.broadcast_to(np.asarray(p[k], dtype=np.float64), (n,)) for k in range(len(p))]
+        return y2, [y2[k] for k in range(y2.shape[0])] + pn + [np.full(n, float(t))], one_d
+
+    @staticmethod
+    def _numpy_printer():
+        """lambdify's NumPy printer with every constant at full precision: the stock one writes a Float with 15 significant
+        digits (0.147058823529412 for 1/6.8), which moves exp(c V) by 2e-14 of its value at V = -95 -- the generated C++ has 17."""
+        from sympy.printing.numpy import NumPyPrinter
+
+        class FullPrecision(NumPyPrinter):
+            def _print_Float(self, expr):
+                return repr(float(expr))
+
+        return FullPrecision({"fully_qualified_modules": False, "inline": True, "allow_unknown_functions": True})
+
+    def _numpy_rhs(self):
+        """The lambdified right-hand sides f and self-derivatives J (what numpy_step integrates)."""
+        import sympy
+
+        if self._numpy_fn is None:
+            s = self._sym
+            # (the common subexpressions found at construction are handed to lambdify as they are: local assignments in the generated function)
+            self._numpy_fn = sympy.lambdify(s["y"] + s["p"] + [s["t"]], [s["f"], s["J"]], "numpy", cse=lambda exprs: (s["repl"], exprs),
+                                            printer=self._numpy_printer())
+        return self._numpy_fn
+
+    def numpy_step(self, states, t, parameters, dt):
+        """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``)."""
+        y2, args, one_d = self._numpy_args(states, t, parameters)
         with np.errstate(all="ignore"):
-            f, J = self._numpy_fn(*[y2[k] for k in range(y2.shape[0])], *pn, np.full(n, float(t)))
+            f, J = self._numpy_rhs()(*args)
         out = np.empty_like(y2)
         for k in range(y2.shape[0]):
             fk = np.broadcast_to(np.asarray(f[k], dtype=np.float64), y2[k].shape)
@@ -405,6 +503,50 @@ class OdeFileModel(DeviceModel):
                     out[k] = y2[k] + np.where(np.abs(Jk) > 1e-8, fk / np.where(Jk == 0, 1.0, Jk) * (np.exp(Jk * dt) - 1.0), fk * dt)
             else:
                 out[k] = y2[k] + dt * fk
+        return out[:, 0].copy() if one_d else out
+
+    def monitor_index(self, name: str) -> int:
+        try:
+            return self.monitor_names.index(name)
+        except ValueError:
+            raise KeyError(f"Unknown monitor {name}") from None
+
+    def _monitor_selection(self, names):
+        """``names`` (None: all) as a list, each one checked."""
+        if names is None:
+            return list(self.monitor_names)
+        if isinstance(names, str):
+            names = [names]
+        names = list(names)
+        for nm in names:
+            self.monitor_index(nm)
+        return names
+
+    def numpy_monitor(self, states, t, parameters, names=None):
+        """The values of the file's assignments ``names`` (None: all of ``monitor_names``) on the HOST with NumPy: (M,) for (S,)
+        states, (M, N) for (S, N); parameters (P,) or per node (P, N).  What the monitor kernel is compared with, as ``numpy_step``
+        is for the step.  The ``d<state>_dt`` rows are the right-hand sides ``numpy_step`` integrates, bit for bit (the same
+        lambdified function); every other row comes from ONE function over all assignments, so that a selection gives the numbers
+        of the matching rows of ``names=None``."""
+        import sympy
+
+        names = self._monitor_selection(names)
+        y2, args, one_d = self._numpy_args(states, t, parameters)
+        n = y2.shape[1]
+        rhs_row = {f"d{s}_dt": k for k, s in enumerate(self.state_names)}
+        plain = [nm for nm in self.monitor_names if nm not in rhs_row]
+        out = np.empty((len(names), n))
+        with np.errstate(all="ignore"):
+            if any(nm in rhs_row for nm in names):
+                f, _ = self._numpy_rhs()(*args)
+            if any(nm not in rhs_row for nm in names):
+                if self._mon_numpy_fn is None:
+                    s = self._sym
+                    self._mon_numpy_fn = sympy.lambdify(s["y"] + s["p"] + [s["t"]], [self._mon_expr[nm] for nm in plain], "numpy", cse=True,
+                                                        printer=self._numpy_printer())
+                vals = dict(zip(plain, self._mon_numpy_fn(*args)))
+        for j, nm in enumerate(names):
+            out[j] = np.broadcast_to(np.asarray(f[rhs_row[nm]] if nm in rhs_row else vals[nm], dtype=np.float64), (n,))
         return out[:, 0].copy() if one_d else out
 
     # ------------------------------------------------------------------------------------------------ device
@@ -482,6 +624,122 @@ class OdeFileModel(DeviceModel):
             worst = max(worst, float(err.max()) if err.size else 0.0)
         self._verified = True
         self.self_check_error = worst
+
+    # ---- monitored values --------------------------------------------------------------------------------
+    def _monitor_launches(self, names):
+        """[(the library's monitor id, number of rows)] for ``names``, one per launch of at most _hip.MAX_MONITORS rows
+        (beat_ode_monitor_register: a selection's source is handed over once per process; its kernel is compiled when a launch
+        first needs it).  The id is handed out once the selection's plain instance has passed ``_monitor_self_check``."""
+        import ctypes as C
+
+        from .. import _hip
+
+        self.register()
+        out = []
+        for k in range(0, len(names), _hip.MAX_MONITORS):
+            run = tuple(names[k:k + _hip.MAX_MONITORS])
+            if run not in self._monitors:
+                name, source = self._monitor_cxx(list(run))
+                mid = C.c_int(-1)
+                _hip.check(_hip.load().beat_ode_monitor_register(self._registered, name.encode(), source.encode(), len(run), C.byref(mid)))
+                self._monitor_self_check(int(mid.value), run)
+                self._monitors[run] = int(mid.value)
+            out.append((self._monitors[run], len(run)))
+        return out
+
+    def monitor_on_device(self, ctx, names, states_ptr, n, ld, t, out_ptr, out_ld, host_params=None, per_node=None, classes=None):
+        """Enqueue the monitor kernel(s) for ``names`` on a RESIDENT state array (``states_ptr``: its row 0, rows ``ld`` apart):
+        row j of the selection goes to ``out_ptr`` + 8 j ``out_ld`` bytes.  Parameters: ``host_params`` (a (P,) NumPy vector), or
+        ``per_node`` = (device pointer of the (P, n) rows, their stride), or ``classes`` = (marker bytes, table, number of classes)
+        as ``_DeviceODE.set_classes`` keeps them.  Does not wait."""
+        row = 0
+        for mid, m in self._monitor_launches(self._monitor_selection(names)):
+            self._monitor_call(ctx, mid, states_ptr, n, ld, t, out_ptr.value + 8 * row * int(out_ld), out_ld, host_params, per_node, classes)
+            row += m
+
+    def _monitor_call(self, ctx, mid, states_ptr, n, ld, t, out_addr, out_ld, host_params, per_node, classes):
+        """beat_ode_monitor for one registered selection (see monitor_on_device for the arguments)."""
+        import ctypes as C
+
+        from .. import _hip
+
+        hp = None if host_params is None else np.ascontiguousarray(host_params, dtype=np.float64)
+        ppn, pld = (None, 0) if per_node is None else per_node
+        mk, table, ncls = (None, None, 0) if classes is None else (C.c_void_p(classes[0].data_ptr()), C.c_void_p(classes[1].data_ptr()), int(classes[2]))
+        _hip.check(ctx.lib.beat_ode_monitor(ctx.handle, mid, states_ptr, int(n), int(ld), None if hp is None else hp.ctypes.data_as(C.c_void_p),
+                                            max(self.num_parameters, 1) if (hp is not None or ppn is not None) else 0, ppn, int(pld), table, ncls, mk,
+                                            float(t), C.c_void_p(out_addr), int(out_ld)))
+
+    def _monitor_staged(self, mid, m, y2, t, parameters):
+        """One launch on host arrays staged through the device: (m, N)."""
+        import ctypes as C
+
+        from .._device import Context, StateArray
+
+        ctx = Context.default()
+        S, n = y2.shape
+        sa = StateArray(ctx, S, n)
+        sa.set(y2)
+        hp, ppn, pld = host_and_device_parameters(ctx, parameters, self.num_parameters, n)
+        out = ctx.zeros(m * n)
+        self._monitor_call(ctx, mid, sa.ptr, n, sa.ld, t, out.data_ptr(), n, hp, None if ppn is None else (C.c_void_p(ppn.data_ptr()), pld), None)
+        return out.cpu().numpy().reshape(m, n)
+
+    @staticmethod
+    def monitor_error(dev, ref):
+        """|dev - ref| / max(|ref|, S_k), S_k the largest finite |ref| of row k (a sum of currents that cancel is measured against
+        the row's scale), over the finite reference values; inf where ``dev`` is not finite there."""
+        dev, ref = np.atleast_2d(dev), np.atleast_2d(ref)
+        ok = np.isfinite(ref)
+        with np.errstate(all="ignore"):
+            scale = np.where(ok, np.abs(ref), 0.0).max(axis=1, keepdims=True)
+            err = np.abs(dev - ref) / np.maximum(np.maximum(np.abs(ref), scale), 1e-300)
+        err = np.where(ok, np.where(np.isfinite(dev), err, np.inf), 0.0)
+        return err
+
+    def _monitor_self_check(self, mid: int, names) -> None:
+        """A selection's PLAIN kernel instance (uniform parameters) against ``numpy_monitor`` on the 2048 states of
+        ``_sample_states``, to 1e-6 of each value (of its row's scale where the value is smaller), at its first use in a process:
+        the reason is ``_self_check``'s.  The per-node and class instances are held against this one by the library at their first
+        launch (csrc/beat_ode_jit.hip: monitor_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both; a failing instance raises."""
+        import os
+
+        if os.environ.get("BEAT_JIT_SELF_CHECK", "1") == "0":
+            return
+        y = self._sample_states(2048)
+        p = self.init_parameter_values()
+        for t in (0.0, 0.37):
+            dev = self._monitor_staged(mid, len(names), y, t, p)
+            ref = self.numpy_monitor(y, t, p, list(names))
+            err = self.monitor_error(dev, ref)
+            if err.max() > 1e-6:
+                k, i = np.unravel_index(int(np.argmax(err)), err.shape)
+                raise RuntimeError(
+                    f"{self.name}: the compiled monitor kernel differs from the NumPy evaluation of the same expressions ({names[k]}, sample {i}: "
+                    f"{dev[k, i]!r} against {ref[k, i]!r}; {int((err > 1e-6).sum())} of {err.size} values) -- a miscompiled (heavily spilled) "
+                    "kernel; other compiler flags (BEAT_JIT_EXTRA_FLAGS) may help, BEAT_JIT_SELF_CHECK=0 skips this check")
+
+    def monitor_values(self, t, states, parameters, names=None):
+        """gotranx's ``monitor_values(t, states, parameters)``: the values of the file's assignments ``names`` (None: all, in the
+        order of ``monitor_names``; ``monitor_index(name)`` gives a row) for (S,) or (S, N) states and (P,) or (P, N) parameters,
+        as (M,) or (M, N).  With a GPU the arrays are staged through the device and the monitor kernel runs; without one this is
+        ``numpy_monitor``, as ``__call__`` is ``numpy_step``."""
+        try:
+            import torch
+
+            on_gpu = torch.cuda.is_available()
+        except Exception:  # noqa: BLE001
+            on_gpu = False
+        if not on_gpu:
+            return self.numpy_monitor(states, t, parameters, names)
+        names = self._monitor_selection(names)
+        y = np.asarray(states, dtype=np.float64)
+        one_d = y.ndim == 1
+        y2 = np.ascontiguousarray(y.reshape(y.shape[0], -1))
+        if y2.shape[0] != self.num_states:
+            raise ValueError(f"{self.name} has {self.num_states} states, got {y2.shape[0]}")
+        out = np.concatenate([self._monitor_staged(mid, m, y2, t, parameters) for mid, m in self._monitor_launches(names)], axis=0)
+        return out[:, 0].copy() if one_d else out
 
     def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
         if dt is None:

@@ -88,6 +88,26 @@ def _initial_values(init_states, shape, on_device: bool):
     return values
 
 
+class _CallableMonitor:
+    """What ``ode.monitor`` of the Dolfin solvers is.  The dataclass field of that name holds the TELEMETRY monitor (the reference's
+    interface: ``DolfinODESolver(..., monitor=...)``, ``ode.monitor.track_time(...)``) and stays that: every attribute read or set
+    here is that object's (``telemetry``).  Called -- ``ode.monitor(names, t, out=None)`` -- it is the solver's
+    ``monitor_values``: the model's monitored values on the device."""
+
+    def __init__(self, telemetry, call):
+        object.__setattr__(self, "telemetry", telemetry)
+        object.__setattr__(self, "_call", call)
+
+    def __getattr__(self, name):
+        return getattr(object.__getattribute__(self, "telemetry"), name)
+
+    def __setattr__(self, name, value):
+        setattr(self.telemetry, name, value)
+
+    def __call__(self, names, t, out=None):
+        return self._call(names, t, out=out)
+
+
 class _DeviceODE:
     """(S, N) state array in HBM advanced by a built-in model kernel."""
 
@@ -237,6 +257,22 @@ class _DeviceODE:
             self._ppn_args = self._per_node_or_classes(self._ppn, p.shape[0])
         return self._ppn_args
 
+    def monitor_rows(self, names, t, out_ptr, out_ld) -> None:
+        """The monitor kernel of a generated model on the resident states, with the parameters as they are now and by the route the
+        next step would take them (uniform vector, classes; per-node rows are read whole -- a generated model has no sparse-row
+        instance).  The caller has brought the potential row up to date.  Does not wait."""
+        hp, _, ppn, pld = (None, 0, None, 0) if self.explicit_classes else self._param_args()
+        args = dict(host_params=None, per_node=None, classes=None)
+        if self.classes is not None:
+            args["classes"] = self.classes
+        elif ppn is not None:
+            args["per_node"] = (ppn, pld)
+        elif hp is not None:
+            args["host_params"] = self._keep  # (the vector _param_args handed out as `hp`)
+        else:
+            raise ValueError(f"{self.model.name}: monitored values need the parameters")
+        self.model.monitor_on_device(self.ctx, names, self.states.ptr, self.n, self.states.ld, t, out_ptr, out_ld, **args)
+
     def step(self, t0, dt, v_index=0, v_copy=None, pending_ops=None, v_row=None):
         """``pending_ops``: diffusion operators whose last solve deferred its update of ``v_row`` (row v_index of
         these states): the kernel adds it while loading the potential (beat_ode_step_pending)."""
@@ -368,6 +404,7 @@ class DolfinODESolver(BaseDolfinODESolver):
             self._ode = ODESystemSolver(fun=self.fun, states=self._values, parameters=self.parameters,
                                         missing_variables=self.missing_variables, monitor=self.monitor)
         self._initialize_metadata()
+        self.monitor = _CallableMonitor(self.monitor, self.monitor_values)
 
     # ---- alias bookkeeping (see grid.Function) ------------------------------------------------
     def _sync_v(self):
@@ -438,6 +475,40 @@ class DolfinODESolver(BaseDolfinODESolver):
         else:
             self._ode.step(t0=t0, dt=dt)
 
+    def monitor_values(self, names, t: float, out: list[grid.Function] | None = None) -> list[grid.Function]:
+        """``ode.monitor(names, t, out=None)`` (see _CallableMonitor: ``monitor`` is also the telemetry field).  The model's monitored values ``names`` (a gotranx module's ``monitor_values``: currents, fluxes, rates, ``d<state>_dt``
+        -- ``fun.monitor_names``) at every node, at time ``t``, as functions on ``v_ode``'s space: evaluated on the device from
+        the resident states and the parameters as they are now; no state leaves the device.  ``out``: functions to write into
+        instead of new ones.  Returns without waiting for the kernel.  For models made by ``beat.models.from_ode``."""
+        if not self.on_device or not hasattr(self.fun, "monitor_on_device"):
+            raise NotImplementedError("monitor() evaluates the named intermediates of a model made by beat.models.from_ode: a hand-written "
+                                      "kernel or a host callable keeps none; use from_ode on the model's .ode file")
+        if self.missing_variables is not None:
+            raise NotImplementedError("monitor() does not take missing_variables")
+        V = self.v_ode.function_space
+        if V.mesh.comm.size > 1:
+            raise NotImplementedError("monitor() is not available on a decomposed mesh")
+        from ._device import StateArray
+
+        names = [names] if isinstance(names, str) else list(names)
+        if out is not None and len(out) != len(names):
+            raise ValueError(f"{len(names)} names, {len(out)} functions")
+        # the potential row must be complete: a step leaves its solve open and its last update to the next ionic launch
+        # (what to_dolfin / values do before they read the row: finish the solve, apply the update)
+        self._sync_v()
+        self._dev.parameters = self.parameters
+        mesh = V.mesh
+        rows = StateArray(self.v_ode._ctx, len(names), self.num_points, mesh.plane if V.is_p1 else 0)
+        self._dev.monitor_rows(names, t, rows.ptr, rows.ld)
+        if out is None:  # each new function owns its row of the kernel's output
+            out = [grid.Function(V, name=nm, field=rows.row_field(j)) for j, nm in enumerate(names)]
+        else:
+            for j, f in enumerate(out):
+                f.writable_field().copy_from(rows.row_field(j))
+        for f in out:
+            f._touch()
+        return out
+
     @property
     def full_values(self):
         return self.values
@@ -500,6 +571,8 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         self._initialize_full_values()
         self._aliases: list[grid.Function] = []
         self._pending_ops = None
+        telemetry = self.monitor  # (the per-marker solvers below take the telemetry monitor itself)
+        self.monitor = _CallableMonitor(telemetry, self.monitor_values)
         self._marked = self.on_device and self._one_launch_possible()
         if self._marked:
             self._setup_one_launch(marker_arr)
@@ -513,14 +586,14 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
             values = _initial_values(self.init_states[marker], self.shape(marker), self.on_device)
             if self.on_device:
                 dev = _DeviceODE(ctx, self.fun[marker], self.num_states[marker], n_m, 0, self.parameters[marker],
-                                 self.monitor)
+                                 telemetry)
                 dev.set_initial(values)
                 self._odes[marker] = dev
                 self._idx_dev[marker] = ctx.from_numpy(np.nonzero(where)[0].astype(np.int64))
             else:
                 self._values[marker] = values
                 self._odes[marker] = ODESystemSolver(fun=self.fun[marker], states=values,
-                                                     parameters=self.parameters[marker], monitor=self.monitor)
+                                                     parameters=self.parameters[marker], monitor=telemetry)
         self._initialize_metadata()
 
     # ---- one launch for all markers (the markers share one device model: cell types, parameter regions) ----------------
@@ -600,7 +673,7 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
             if node_idx.size == 0 or node_idx.max() >= 2**31:
                 raise ValueError("the node map holds 32-bit indices")
             n_c = int(node_idx.size)
-            self._dev = _DeviceODE(ctx, model, S, n_c, 0, None, self.monitor)
+            self._dev = _DeviceODE(ctx, model, S, n_c, 0, None, self.monitor.telemetry)
             self._v_row = ctx.field(n, mesh.plane)  # the potential's home: a field of the PDE grid
             self._v_row.copy_from(self.v_ode.field)  # nodes outside every marker keep the potential they have
             self._real_pos = ctx.from_numpy(real_pos.astype(np.int64))       # entries of the array that are nodes ...
@@ -608,7 +681,7 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
             self._node_idx = self._real_nodes
             self._dev.node_map = (ctx.from_numpy(node_idx.astype(np.int32)), self._v_row)
         else:
-            self._dev = _DeviceODE(ctx, model, S, n, mesh.plane, None, self.monitor)
+            self._dev = _DeviceODE(ctx, model, S, n, mesh.plane, None, self.monitor.telemetry)
             self._v_row = self._dev.states.row_field(vi)
             self._v_row.copy_from(self.v_ode.field)
             self._node_idx = None
@@ -776,6 +849,9 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
                         ode.step(t0, dt)
                     else:
                         ode.step(t0=t0, dt=dt)
+
+    def monitor_values(self, names, t: float, out=None):
+        raise NotImplementedError("monitor() is not available for DolfinMultiODESolver: use DolfinODESolver with one beat.models.from_ode model")
 
     def assign_all_states(self, functions: list[grid.Function]) -> None:
         num_states = self.num_states[self._marker_values[0]]

@@ -225,12 +225,15 @@ bool run_hipcc(const JitState& s, const std::string& src, const std::string& out
 }
 
 // the kernel's symbol in a code object (an offload bundle or a bare ELF): the NUL-terminated string that starts with _Z, names
-// ode_step_kernel (or ode_run_kernel: a translation unit instantiates ONE kernel) and carries no suffix (.kd, .private_seg_size ...
+// ode_step_kernel (or ode_run_kernel, or ode_monitor_kernel: a translation unit instantiates ONE kernel) and carries no suffix (.kd, .private_seg_size ...
 // are the descriptor and its metadata)
 std::string kernel_symbol(const std::string& blob, const char* stem);
 std::string kernel_symbol(const std::string& blob) {
-  const std::string s = kernel_symbol(blob, "ode_step_kernel");
-  return s.empty() ? kernel_symbol(blob, "ode_run_kernel") : s;
+  for (const char* stem : {"ode_step_kernel", "ode_run_kernel", "ode_monitor_kernel"}) {
+    const std::string s = kernel_symbol(blob, stem);
+    if (!s.empty()) return s;
+  }
+  return "";
 }
 std::string kernel_symbol(const std::string& blob, const char* stem) {
   size_t pos = 0;
@@ -608,6 +611,181 @@ int beat_custom_run(beat_ctx* ctx, int model_id, double* states, int64_t n, int6
   double drv = 0.0;
   const unsigned grid = (unsigned)((n + BEAT_BLOCK - 1) / BEAT_BLOCK);
   void* args[] = {&states, &n, &ld, prm.data(), &drv, &ppn, &pld, &t0, &dt, &nsteps, &nbeats, &save_freq, &tr, &trace};
+  BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+  return BEAT_OK;
+}
+
+// ---- monitored values of a registered model (beat.models.from_ode: monitor_values) ----------------------------------------------------
+// A selection of the file's assignments, given as the source of a struct Mon (NS, NP, NM, eval: what the generator writes for
+// csrc/beat_ode_kernel.h's ode_monitor_kernel), kept beside the model it belongs to and compiled at first use like the model's own kernels.
+namespace {
+struct CustomMonitor {
+  int model_id;
+  std::string name, source;
+  int nm;
+};
+std::vector<CustomMonitor>& monitors() {
+  static std::vector<CustomMonitor> v;
+  return v;
+}
+std::string monitor_instantiation(const std::string& name, bool per_node, bool marked) {
+  return "template __global__ void ode_monitor_kernel<" + name + ", " + (per_node ? "true" : "false") + ", " + (marked ? "true" : "false") +
+         ">(\n    const double*, int64_t, int64_t, ParamPack<" + name + "::NP>, const double*, int64_t, MarkedArgs, int, double, double*, int64_t);";
+}
+
+// A variant instance (per-node rows, classes) against the selection's PLAIN instance, once per instance and process, on the caller's
+// first nodes: the variant is given what makes it compute the plain values (every node the parameters of node 0 / class 0) --
+// same arithmetic, same values.  Why: custom_cross_check above.  The plain instance itself is held against the NumPy evaluation
+// of the same expressions by the caller (beat/models/ode_file.py).  A variant that fails is refused: the call fails.
+int monitor_cross_check(beat_ctx* ctx, const CustomMonitor& mon, const CustomModel& unit, hipFunction_t f, const std::string& what,
+                        bool per_node, bool marked, const double* states, int64_t n, int64_t ld, const double* ppn, int64_t pld,
+                        const double* class_table, double t) {
+  if (const char* e = std::getenv("BEAT_JIT_SELF_CHECK"))
+    if (e[0] == '0') return BEAT_OK;
+  const std::string key = mon.name + "/" + what + "@" + std::to_string(ctx->device);
+  {
+    std::lock_guard<std::mutex> lock(customs_mutex());
+    if (custom_checked().count(key)) return BEAT_OK;
+  }
+  hipFunction_t f0 = custom_instance(ctx, unit, "mon_n0m0", monitor_instantiation(mon.name, false, false));
+  if (f0 == nullptr) return BEAT_EINVAL;
+  int64_t nc = std::min<int64_t>(n, 1024);
+  if (nc < 1) return BEAT_OK;
+  const size_t np = (size_t)unit.np, nm = (size_t)mon.nm;
+  std::vector<double> p0(np, 1.0);  // the parameters of node 0 / class 0
+  if (per_node) {
+    BEAT_HIP_CHECK(hipMemcpy2DAsync(p0.data(), sizeof(double), ppn, sizeof(double) * (size_t)pld, sizeof(double), np, hipMemcpyDeviceToHost,
+                                    ctx->stream));
+  } else {
+    BEAT_HIP_CHECK(hipMemcpyAsync(p0.data(), class_table, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  const size_t doubles = 2 * nm * (size_t)nc + np * (size_t)nc + (np + 1) + ((size_t)nc + 7) / 8;
+  double* scratch = nullptr;
+  BEAT_HIP_CHECK(hipMalloc(&scratch, sizeof(double) * doubles));
+  struct Free {
+    double* p;
+    ~Free() { (void)hipFree(p); }
+  } guard{scratch};
+  double* oa = scratch;
+  double* ob = oa + nm * (size_t)nc;
+  double* rows = ob + nm * (size_t)nc;
+  double* table = rows + np * (size_t)nc;
+  unsigned char* marks = (unsigned char*)(table + np + 1);
+  std::vector<double> hrows(np * (size_t)nc), htab(np + 1, 0.0);
+  for (size_t k = 0; k < np; ++k) {
+    htab[k] = p0[k];
+    for (int64_t i = 0; i < nc; ++i) hrows[k * nc + i] = p0[k];
+  }
+  BEAT_HIP_CHECK(hipMemcpyAsync(rows, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice, ctx->stream));
+  BEAT_HIP_CHECK(hipMemcpyAsync(table, htab.data(), sizeof(double) * htab.size(), hipMemcpyHostToDevice, ctx->stream));
+  BEAT_HIP_CHECK(hipMemsetAsync(marks, 0, (size_t)nc, ctx->stream));
+  MarkedArgs mk0{nullptr, nullptr, 0, nullptr, nullptr};
+  MarkedArgs mkv = marked ? MarkedArgs{marks, table, unit.np + 1, nullptr, nullptr} : mk0;
+  const double* ppn_v = per_node ? rows : nullptr;
+  const double* ppn_0 = nullptr;
+  int64_t pld_v = per_node ? nc : 0, pld_0 = 0, ldo = nc;
+  int ncls_v = marked ? 1 : 0, ncls_0 = 0;
+  const unsigned grid = (unsigned)((nc + BEAT_BLOCK - 1) / BEAT_BLOCK);
+  {
+    void* args[] = {&states, &nc, &ld, p0.data(), &ppn_v, &pld_v, &mkv, &ncls_v, &t, &oa, &ldo};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+  }
+  {
+    void* args[] = {&states, &nc, &ld, p0.data(), &ppn_0, &pld_0, &mk0, &ncls_0, &t, &ob, &ldo};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f0, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+  }
+  std::vector<double> h(2 * nm * (size_t)nc);
+  BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), scratch, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  const double* a = h.data();
+  const double* b = h.data() + nm * (size_t)nc;
+  for (size_t k = 0; k < nm; ++k) {
+    double scale = 0.0;
+    for (int64_t i = 0; i < nc; ++i) {
+      const double v = std::fabs(b[k * nc + i]);
+      if (v == v && v > scale && v < 1e300) scale = v;
+    }
+    for (int64_t i = 0; i < nc; ++i) {
+      const double x = a[k * nc + i], y = b[k * nc + i];
+      if (x != x && y != y) continue;  // both NaN (a caller's garbage in, the same garbage out)
+      if (!(std::fabs(x - y) <= 1e-10 * std::fabs(y) + 1e-13 * scale)) {
+        beat_set_error("instance %s of monitor %s differs from the monitor's plain instance (row %d, node %lld: %.17g against %.17g): "
+                       "miscompiled (heavily spilled) kernel; try other BEAT_JIT_EXTRA_FLAGS", what.c_str(), mon.name.c_str(), (int)k, (long long)i, x, y);
+        return BEAT_EINVAL;
+      }
+    }
+  }
+  std::lock_guard<std::mutex> lock(customs_mutex());
+  custom_checked().insert(key);
+  return BEAT_OK;
+}
+}  // namespace
+
+extern "C" int beat_ode_monitor_register(int model_id, const char* name, const char* source, int num_outputs, int* monitor_id_out) {
+  BEAT_REQUIRE(name != nullptr && source != nullptr && monitor_id_out != nullptr, "null argument");
+  BEAT_REQUIRE(num_outputs >= 1 && num_outputs <= BEAT_MAX_MONITORS, "1..%d monitored values per launch, got %d", BEAT_MAX_MONITORS, num_outputs);
+  BEAT_REQUIRE(beat_custom_model_info(model_id, nullptr, nullptr, nullptr) == BEAT_OK,
+               "monitored values belong to a model registered as source (beat_ode_model_register), not to model id %d", model_id);
+  for (const char* c = name; *c; ++c)
+    BEAT_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_', "monitor name: [A-Za-z0-9_]+");
+  BEAT_REQUIRE(std::string(source).find(std::string("struct ") + name) != std::string::npos, "the source does not define struct %s", name);
+  BEAT_REQUIRE(beat_jit_enabled(), "monitored values need run-time compilation, which is not available here (beat_ode_jit_stats)");
+  std::lock_guard<std::mutex> lock(customs_mutex());
+  std::vector<CustomMonitor>& v = monitors();
+  for (size_t k = 0; k < v.size(); ++k)
+    if (v[k].model_id == model_id && v[k].name == name && v[k].source == source) {
+      *monitor_id_out = (int)k;
+      return BEAT_OK;
+    }
+  v.push_back(CustomMonitor{model_id, name, source, num_outputs});
+  *monitor_id_out = (int)v.size() - 1;
+  return BEAT_OK;
+}
+
+extern "C" int beat_ode_monitor(beat_ctx* ctx, int monitor_id, const double* dev_states, int64_t n, int64_t ld, const double* host_params,
+                                int num_params, const double* dev_params_per_node, int64_t params_ld, const double* dev_class_table,
+                                int num_classes, const unsigned char* dev_markers, double t, double* dev_out, int64_t out_ld) {
+  BEAT_REQUIRE(ctx != nullptr && dev_states != nullptr && dev_out != nullptr, "null argument");
+  BEAT_REQUIRE(n >= 0 && ld >= n, "bad shape n=%lld ld=%lld", (long long)n, (long long)ld);
+  BEAT_REQUIRE(out_ld >= n, "out_ld %lld < n %lld", (long long)out_ld, (long long)n);
+  BEAT_REQUIRE((n + BEAT_BLOCK - 1) / BEAT_BLOCK < (int64_t)0x7fffffff, "n too large");
+  CustomMonitor mon;
+  {
+    std::lock_guard<std::mutex> lock(customs_mutex());
+    BEAT_REQUIRE(monitor_id >= 0 && monitor_id < (int)monitors().size(), "unknown monitor id %d", monitor_id);
+    mon = monitors()[monitor_id];
+  }
+  CustomModel m;
+  if (int rc = custom_model(mon.model_id, m)) return rc;
+  const bool marked = dev_markers != nullptr, per_node = dev_params_per_node != nullptr;
+  BEAT_REQUIRE(!(marked && per_node) && marked == (dev_class_table != nullptr), "parameter classes come with markers and a table, not with per-node rows");
+  BEAT_REQUIRE(!marked || (num_classes >= 1 && num_classes <= BEAT_MAX_CLASSES), "1..%d parameter classes, got %d", BEAT_MAX_CLASSES, num_classes);
+  BEAT_REQUIRE(marked || ((host_params != nullptr || per_node) && num_params == m.np),
+               "model %s expects %d parameters (a host vector, per-node rows or classes), got %d", m.name.c_str(), m.np, num_params);
+  BEAT_REQUIRE(!per_node || params_ld >= n, "params_ld %lld < n %lld", (long long)params_ld, (long long)n);
+  {  // the pass reads the states and writes `out`: the two must not overlap
+    const double* s0 = dev_states;
+    const double* s1 = dev_states + ((int64_t)(m.ns - 1) * ld + n);
+    const double* o0 = dev_out;
+    const double* o1 = dev_out + ((int64_t)(mon.nm - 1) * out_ld + n);
+    BEAT_REQUIRE(n == 0 || o1 <= s0 || s1 <= o0, "the output rows overlap the state array");
+  }
+  if (n == 0) return BEAT_OK;
+  const CustomModel unit{mon.name, mon.source, m.ns, m.np, m.v_index};  // the translation unit: the monitor's struct alone
+  const std::string what = std::string("mon_n") + (per_node ? "1" : "0") + "m" + (marked ? "1" : "0");
+  hipFunction_t f = custom_instance(ctx, unit, what, monitor_instantiation(mon.name, per_node, marked));
+  if (f == nullptr) return BEAT_EINVAL;
+  if (per_node || marked)
+    if (int rc = monitor_cross_check(ctx, mon, unit, f, what, per_node, marked, dev_states, n, ld, dev_params_per_node, params_ld, dev_class_table, t))
+      return rc;
+  std::vector<double> prm(m.np, 1.0);
+  if (host_params != nullptr && !marked && !per_node) prm.assign(host_params, host_params + m.np);
+  int stride = m.np + 1;  // beat_ode_class_table_doubles of a registered model
+  MarkedArgs mk{dev_markers, dev_class_table, stride, nullptr, nullptr};
+  int ncls = marked ? num_classes : 0;
+  const unsigned grid = (unsigned)((n + BEAT_BLOCK - 1) / BEAT_BLOCK);
+  void* args[] = {&dev_states, &n, &ld, prm.data(), &dev_params_per_node, &params_ld, &mk, &ncls, &t, &dev_out, &out_ld};
   BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   return BEAT_OK;
 }

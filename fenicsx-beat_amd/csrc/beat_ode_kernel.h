@@ -530,3 +530,77 @@ __global__ __launch_bounds__(BEAT_BLOCK, 1) void ode_run_kernel(
   }
 }
 
+// Monitored values of a generated model (beat.models.from_ode: monitor_values, what a gotranx module's monitor_values(t, states,
+// parameters) gives): a READ-ONLY pass over the state array that evaluates a selection of the file's assignments -- currents, fluxes,
+// gate rates, d<state>_dt -- at every node and writes them to NM output rows, out + m out_ld + i.  Mon is the struct the generator
+// writes for the selection (NS, NP, NM, eval); it loads only the state rows the selection uses: 8 (rows used + NM) B/node.
+// One node per thread; rows addressed as in the step (uniform row base + the lane's 32-bit byte offset) and read / written with
+// the step's non-temporal accesses.  Parameters as the step of a registered model takes them: the uniform vector in the
+// kernel-argument segment, all per-node rows, or a class byte per node and a table (stride mk.stride doubles per class, the
+// parameters first); a node whose byte names no class (255, or anything >= num_classes: no table entry is read for it) gets NaN
+// in every row.
+struct MonitorIn {
+  const double* __restrict__ base;  // the tile's first node in row 0 (uniform)
+  int64_t ld;
+  mutable unsigned i;  // BYTE offset of the lane's node within the tile (see NodeIO)
+  __device__ __forceinline__ double load(int k) const { return beat_row_load(beat_at(beat_row(base, k, ld), i)); }
+};
+struct MonitorOut {
+  double* __restrict__ base;  // the tile's first node in output row 0 (uniform)
+  int64_t ld;
+  mutable unsigned i;
+  __device__ __forceinline__ void store(int m, double x) const { beat_row_store(beat_at(beat_row(base, m, ld), i), x); }
+};
+constexpr int BEAT_MAX_MONITOR_ROWS = 32;  // = BEAT_MAX_MONITORS of include/beat_hip.h
+
+template <class Mon, bool PER_NODE, bool MARKED>
+__global__ __launch_bounds__(BEAT_BLOCK) void ode_monitor_kernel(
+    const double* __restrict__ states, int64_t n, int64_t ld, ParamPack<Mon::NP> prm, const double* __restrict__ ppn, int64_t pld,
+    MarkedArgs mk, int num_classes, double t, double* __restrict__ out, int64_t out_ld) {
+  static_assert(Mon::NM >= 1 && Mon::NM <= BEAT_MAX_MONITOR_ROWS, "1..32 monitored values per launch");
+  __shared__ double etab[BEAT_EXP_TAB];
+  __shared__ LogEntry ltab[128];
+  static_assert(BEAT_EXP_TAB == BEAT_BLOCK, "one table entry per thread");
+  // (every thread of the block fills its table entry and meets the barrier -- the lanes past the last node too: the bounds
+  // check comes after both, as in ode_step_kernel)
+  etab[threadIdx.x] = beat_exp_tab_entry<FastMath::INT_SCALE>(kExp2Tab[threadIdx.x], (int)threadIdx.x);
+  if (threadIdx.x < 128) ltab[threadIdx.x] = kLogTab[threadIdx.x];
+  __syncthreads();
+  const FastMath fm{etab, ltab};
+  const int64_t tile0 = (int64_t)blockIdx.x * BEAT_BLOCK;  // the tile's first node: uniform
+  const int64_t i = tile0 + threadIdx.x;
+  if (i >= n) return;
+  const unsigned lane_off = threadIdx.x * 8u;
+  const MonitorIn io{states + tile0, ld, lane_off};
+  const MonitorOut o{out + tile0, out_ld, lane_off};
+  if constexpr (MARKED) {
+    const int m_lane = mk.markers[i];
+    if (m_lane >= num_classes) {
+#pragma unroll
+      for (int m = 0; m < Mon::NM; ++m) o.store(m, __builtin_nan(""));
+    }
+    // a wavefront whose nodes share a class reads its set with scalar loads; one on a class boundary evaluates once per class
+    // present, lanes masked (as the step's class kernel)
+    unsigned long long todo = __ballot(m_lane < num_classes);
+    while (todo) {
+      const int c = __builtin_amdgcn_readlane(m_lane, __ffsll((long long)todo) - 1);  // wave-uniform
+      typedef const __attribute__((address_space(4))) char* TabPtr;
+      TabPtr tb = (TabPtr)(uintptr_t)(mk.table + (int64_t)c * mk.stride);  // (the table is not written here)
+      asm volatile("" : "+s"(tb));
+      const double* p_c = (const double*)tb;
+      if (m_lane == c) Mon::eval(io, p_c, fm, t, o);
+      todo &= ~__ballot(m_lane == c);
+    }
+  } else if constexpr (PER_NODE) {
+    double pl[Mon::NP];  // (the rows the selection does not use are never loaded: their values are dead)
+#pragma unroll
+    for (int k = 0; k < Mon::NP; ++k) {
+      unsigned off = lane_off;
+      pl[k] = *beat_at(beat_row(ppn + tile0, k, pld), off);
+    }
+    Mon::eval(io, (const double*)pl, fm, t, o);
+  } else {
+    Mon::eval(io, prm.p, fm, t, o);
+  }
+}
+

@@ -169,6 +169,26 @@ int beat_ode_run(beat_ctx* ctx, int model_id, double* dev_states, int64_t n, int
                  int64_t params_ld, double t0, double dt, int64_t nsteps, int nbeats, int save_freq,
                  const int* host_track_idx, int ntrack, double* dev_trace);
 
+/* Monitored values of a model registered as source: a gotranx-generated module's  monitor_values(t, states, parameters)  and
+ * monitor_index(name)  (what users plot I_Na or I_CaL from, check a model against its paper with and hand an active tension to a
+ * mechanics code), evaluated at every node from the RESIDENT state array instead of on a host copy of it.
+ * beat_ode_monitor_register stands for the generated module's monitor function itself: `source` defines a C++ struct `name` with the
+ * interface csrc/beat_ode_kernel.h's ode_monitor_kernel expects (NS, NP, NM = num_outputs <= BEAT_MAX_MONITORS, eval -- what
+ * beat.models.from_ode writes for a selection of the file's assignments), kept beside the registered model `model_id` and compiled
+ * by hipcc at first use like that model's kernels.  The same model, name and source give the same id. */
+#define BEAT_MAX_MONITORS 32
+int beat_ode_monitor_register(int model_id, const char* name, const char* source, int num_outputs, int* monitor_id_out);
+/* values = monitor_values(t, states, parameters)  at n nodes: row m of the selection goes to dev_out + m*out_ld + i (out_ld >= n;
+ * what lies between n and out_ld is not touched).  dev_states (num_states, ld) is only read; dev_out must not overlap it.
+ * Parameters as beat_ode_step / beat_ode_step_classes take them for a registered model: host_params (num_params), or
+ * dev_params_per_node (num_params, params_ld), or dev_class_table (beat_ode_class_table_fill, num_classes entries) with a byte per
+ * node in dev_markers -- a node whose byte names no class (255) gets NaN in every row.  Enqueued on the context's stream; does not
+ * synchronise.  The first launch of an instance compiles it; the per-node and class instances are then held once against the plain
+ * one (BEAT_JIT_SELF_CHECK=0: not), and one that differs fails the call. */
+int beat_ode_monitor(beat_ctx* ctx, int monitor_id, const double* dev_states, int64_t n, int64_t ld, const double* host_params,
+                     int num_params, const double* dev_params_per_node, int64_t params_ld, const double* dev_class_table,
+                     int num_classes, const unsigned char* dev_markers, double t, double* dev_out, int64_t out_ld);
+
 /* row/field transfers: v_ode.x.array[:] = values[v_index] etc. (odesolver.py:164-170,
  * utils.py:52-54, monodomain_model.py:59-60) */
 int beat_copy(beat_ctx* ctx, double* dev_dst, const double* dev_src, int64_t n);
