@@ -168,6 +168,54 @@ def _dependency_order(assignments):
     return out
 
 
+def _on_gpu() -> bool:
+    """Is there a GPU to run a kernel on?  (Without one -- or without torch -- the handle evaluates with NumPy.)"""
+    try:
+        import torch
+
+        return torch.cuda.is_available()
+    except Exception:  # noqa: BLE001
+        return False
+
+
+class _Body:
+    """The body of a generated function as it is being written (the step's, a monitor selection's): the printer, the file's
+    states, parameters and time as y_k / p_k / t, the common subexpressions ``repl`` in those symbols, the ``lines`` so far and the
+    symbols they use."""
+
+    def __init__(self, model, repl):
+        import sympy
+
+        self.pr, self.uses_mod = model._printer()
+        y, p = model._sym["y"], model._sym["p"]
+        self.ns, self.np = len(y), len(p)
+        self.sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
+        self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
+        self.sub[model._sym["t"]] = sympy.Symbol("t")
+        self.temp = {lhs: e.xreplace(self.sub) for lhs, e in repl}
+        self.lines = []
+        self.emit, self.emitted = model._emitter(self.temp, self.pr, self.lines)
+        self.used = set()
+
+    def expr(self, e):
+        """``e`` in the body's symbols: the temporaries it needs are emitted, its symbols noted as used."""
+        import sympy
+
+        e = sympy.sympify(e).xreplace(self.sub)
+        self.emit(e)
+        self.used |= e.free_symbols
+        return e
+
+    def loads(self, every_state: bool):
+        """The load lines of the states (all of them, or the used ones) and of the used parameters, once the body is written."""
+        import sympy
+
+        for e in self.emitted:
+            self.used |= self.temp[e].free_symbols
+        return ([f"    const double y_{k} = io.load({k});" for k in range(self.ns) if every_state or sympy.Symbol(f"y_{k}") in self.used],
+                [f"    const double p_{k} = p[{k}];" for k in range(self.np) if sympy.Symbol(f"p_{k}") in self.used])
+
+
 class OdeFileModel(DeviceModel):
     """A :class:`DeviceModel` generated from an ``.ode`` file (see the module docstring)."""
 
@@ -346,38 +394,24 @@ class OdeFileModel(DeviceModel):
     def _cxx(self, stem: str) -> str:
         import os
 
-        import sympy
-
         exp_name = "fexp" if self.fast_exp else "exp"
-        pr, uses_mod = self._printer()
-        y, p = self._sym["y"], self._sym["p"]
-        sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
-        sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-        sub[self._sym["t"]] = sympy.Symbol("t")
-        used = set()
-        ns_, np_ = len(y), len(p)
-        vi = self.state_index(self.v_name) if self.v_name else 0
         # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
         # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
         # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
         # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
         # per lane that way.)
-        temp = {lhs: e.xreplace(sub) for lhs, e in self._sym["repl"]}
-        lines = []
-        emit, emitted = self._emitter(temp, pr, lines)
-
+        body = _Body(self, self._sym["repl"])
+        pr, lines, ns_, np_ = body.pr, body.lines, body.ns, body.np
+        vi = self.state_index(self.v_name) if self.v_name else 0
         order = list(range(ns_))
         if os.environ.get("BEAT_ODE_V_LAST", "1") == "1" and self.v_name:  # the potential's equation sums every current: last, when the currents exist
             order = [k for k in order if k != vi] + [vi]
         if os.environ.get("BEAT_ODE_EMIT") == "global":  # every temporary first, in the elimination's order (tests: the heavily spilled form)
-            for lhs in temp:
-                emit(lhs)
+            for lhs in body.temp:
+                body.emit(lhs)
             order = list(range(ns_))
         for k in order:
-            fk, jk = self._sym["f"][k].xreplace(sub), self._sym["J"][k].xreplace(sub)
-            emit(fk)
-            emit(jk)
-            used |= fk.free_symbols | jk.free_symbols
+            fk, jk = body.expr(self._sym["f"][k]), body.expr(self._sym["J"][k])
             if self._grl[k]:
                 if os.environ.get("BEAT_ODE_BRANCHES") == "1":  # (the former output: see _print_Piecewise)
                     lines.append(f"    {{ const double f = {pr.doprint(fk)}; const double J = {pr.doprint(jk)};\n"
@@ -387,12 +421,8 @@ class OdeFileModel(DeviceModel):
                              f"      io.store({k}, y_{k} + beat_sel(fabs(J) > 1e-8, f / J * ({exp_name}(J * dt) - 1.0), f * dt)); }}")
             else:
                 lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
-        for e in emitted:
-            used |= temp[e].free_symbols
-        body = []
-        loads = [f"    const double y_{k} = io.load({k});" for k in range(ns_)]
-        pl = [f"    const double p_{k} = p[{k}];" for k in range(np_) if sympy.Symbol(f"p_{k}") in used]
-        digest = hashlib.sha1(("\n".join(lines + body) + self.scheme).encode()).hexdigest()[:12]
+        loads, pl = body.loads(every_state=True)
+        digest = hashlib.sha1(("\n".join(lines) + self.scheme).encode()).hexdigest()[:12]
         self.cxx_name = f"Ode_{stem}_{digest}"
         return (f"// generated by beat.models.from_ode from {self.path.name} ({self.scheme}): {ns_} states, {np_} parameters\n"
                 f"struct {self.cxx_name} {{\n"
@@ -403,8 +433,8 @@ class OdeFileModel(DeviceModel):
                 "  template <class P> __host__ __device__ static Derived derive(const P&) { return Derived{0.0}; }\n"
                 "  template <class IO, class P>\n"
                 "  __device__ static __forceinline__ void step(const IO& io, const P& p, const Derived&, const FastMath& fm, double t, double dt) {\n"
-                + self._cxx_helpers(uses_mod)
-                + "\n".join(loads + pl + lines + body) + "\n  }\n};\n")
+                + self._cxx_helpers(body.uses_mod)
+                + "\n".join(loads + pl + lines) + "\n  }\n};\n")
 
     def _monitor_cxx(self, names):
         """(struct name, source) of ``Mon_<stem>_<digest>`` for csrc/beat_ode_kernel.h's ode_monitor_kernel: the assignments ``names``
@@ -414,33 +444,20 @@ class OdeFileModel(DeviceModel):
         loaded."""
         import sympy
 
-        pr, uses_mod = self._printer()
-        y, p = self._sym["y"], self._sym["p"]
-        sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
-        sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-        sub[self._sym["t"]] = sympy.Symbol("t")
         repl, red = sympy.cse([self._mon_expr[nm] for nm in names], symbols=sympy.numbered_symbols("x_"), optimizations="basic")
-        temp = {lhs: e.xreplace(sub) for lhs, e in repl}
-        lines = []
-        emit, emitted = self._emitter(temp, pr, lines)
-        used = set()
+        body = _Body(self, repl)
+        lines = body.lines
         for j, e in enumerate(red):
-            ej = sympy.sympify(e).xreplace(sub)
-            emit(ej)
-            used |= ej.free_symbols
-            lines.append(f"    out.store({j}, {pr.doprint(ej)});  // {names[j]}")
-        for e in emitted:
-            used |= temp[e].free_symbols
-        loads = [f"    const double y_{k} = io.load({k});" for k in range(len(y)) if sympy.Symbol(f"y_{k}") in used]
-        pl = [f"    const double p_{k} = p[{k}];" for k in range(len(p)) if sympy.Symbol(f"p_{k}") in used]
+            lines.append(f"    out.store({j}, {body.pr.doprint(body.expr(e))});  // {names[j]}")
+        loads, pl = body.loads(every_state=False)
         digest = hashlib.sha1("\n".join(loads + pl + lines).encode()).hexdigest()[:12]
         name = f"Mon_{self._stem}_{digest}"
-        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {len(y)} states read\n"
+        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {body.ns} states read\n"
                       f"struct {name} {{\n"
-                      f"  static constexpr int NS = {len(y)}, NP = {max(len(p), 1)}, NM = {len(names)};\n"
+                      f"  static constexpr int NS = {body.ns}, NP = {max(body.np, 1)}, NM = {len(names)};\n"
                       "  template <class IO, class P, class OUT>\n"
                       "  __device__ static __forceinline__ void eval(const IO& io, const P& p, const FastMath& fm, double t, const OUT& out) {\n"
-                      + self._cxx_helpers(uses_mod)
+                      + self._cxx_helpers(body.uses_mod)
                       + "\n".join(loads + pl + lines) + "\n  }\n};\n")
 
     def monitor_sources(self, names=None):
@@ -592,38 +609,56 @@ class OdeFileModel(DeviceModel):
         y[:, 0] = self.init_state_values()
         return y
 
-    def _self_check(self) -> None:
-        """The model's PLAIN kernel instance (uniform parameters, no pending update) against the NumPy evaluation of the same
-        expressions on 2048 sample states (to 1e-6 of each value), once per process: a big generated kernel is heavily spilled, and such a kernel has been
-        seen miscompiled (round 1; reproduced in round 5, tools/diag_spill.py) -- wrong values on part of the nodes, silently.
-        The other instances (per-node rows, pending update, classes) are held against this one by the library at their first
-        launch (csrc/beat_ode_jit.hip: custom_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both."""
+    @staticmethod
+    def step_error(dev, ref, y):
+        """|dev - ref| / max(|ref|, |y|) (relative to the state before or after the step, whichever is larger: y + dt f may
+        cancel) over the finite reference values; inf where ``dev`` is not finite there."""
+        ok = np.isfinite(ref)
+        with np.errstate(all="ignore"):  # (inf - inf where both sides overflow: masked by `ok`)
+            err = np.abs(dev - ref) / np.maximum(np.maximum(np.abs(ref), np.abs(y)), 1e-12)
+        return np.where(ok, np.where(np.isfinite(dev), err, np.inf), 0.0)
+
+    def _check_against_numpy(self, what, rows, device, host, error):
+        """The frame of the two self checks: ``device(y, t, p, dt)`` against ``host(y, t, p, dt)`` on the 2048 states of
+        ``_sample_states`` at two times, the instance refused (RuntimeError) where ``error(dev, ref, y)`` exceeds 1e-6 -- a sample
+        far from the model's physiological range may sit where exp(J dt) - 1 cancels, and the two exp()s differ in the last bit
+        (3e-8 seen); a miscompiled kernel is wrong by O(1) on thousands of values.  Returns the largest error seen, or None
+        where BEAT_JIT_SELF_CHECK=0 skips the check."""
         import os
 
-        if os.environ.get("BEAT_JIT_SELF_CHECK", "1") == "0" or getattr(self, "_verified", False):
-            return
+        if os.environ.get("BEAT_JIT_SELF_CHECK", "1") == "0":
+            return None
         y = self._sample_states(2048)
         p = self.init_parameter_values()
         worst = 0.0
         for t, dt in ((0.0, 0.01), (0.37, 0.05)):
-            dev = DeviceModel.__call__(self, states=y, t=t, parameters=p, dt=dt)
+            dev = device(y, t, p, dt)
             with np.errstate(all="ignore"):
-                ref = self.numpy_step(y, t, p, dt)
-            ok = np.isfinite(ref)
-            with np.errstate(all="ignore"):  # (inf - inf where both sides overflow: masked by `ok`)
-                err = np.abs(dev - ref)[ok] / np.maximum(np.maximum(np.abs(ref), np.abs(y)), 1e-12)[ok]
-            # (1e-6 of the value: a sample far from the model's physiological range may sit where exp(J dt) - 1 cancels, and the two
-            # exp()s differ in the last bit -- 3e-8 seen; a miscompiled kernel is wrong by O(1) on thousands of values)
-            if not np.isfinite(dev[ok]).all() or (err.size and err.max() > 1e-6):
-                bad = np.argwhere(~(np.abs(np.where(ok, dev - ref, 0.0)) <= 1e-6 * np.maximum(np.maximum(np.abs(ref), np.abs(y)), 1e-12)))
-                k, i = (int(bad[0][0]), int(bad[0][1])) if len(bad) else (0, 0)
+                ref = host(y, t, p, dt)
+            err = error(dev, ref, y)
+            if err.max() > 1e-6:
+                k, i = np.unravel_index(int(np.argmax(err)), err.shape)
                 raise RuntimeError(
-                    f"{self.name}: the compiled kernel differs from the NumPy evaluation of the same expressions (state {self.state_names[k]}, "
-                    f"sample {i}: {dev[k, i]!r} against {ref[k, i]!r}; {len(bad)} of {ok.sum()} values) -- a miscompiled (heavily spilled) kernel; "
-                    "other compiler flags (BEAT_JIT_EXTRA_FLAGS) may help, BEAT_JIT_SELF_CHECK=0 skips this check")
-            worst = max(worst, float(err.max()) if err.size else 0.0)
-        self._verified = True
-        self.self_check_error = worst
+                    f"{self.name}: the compiled {what} differs from the NumPy evaluation of the same expressions ({rows[k]}, sample {i}: "
+                    f"{dev[k, i]!r} against {ref[k, i]!r}; {int((err > 1e-6).sum())} of {err.size} values) -- a miscompiled (heavily spilled) "
+                    "kernel; other compiler flags (BEAT_JIT_EXTRA_FLAGS) may help, BEAT_JIT_SELF_CHECK=0 skips this check")
+            worst = max(worst, float(err.max()))
+        return worst
+
+    def _self_check(self) -> None:
+        """The model's PLAIN kernel instance (uniform parameters, no pending update) against the NumPy evaluation of the same
+        expressions (``_check_against_numpy``, to 1e-6 of each value), once per process: a big generated kernel is heavily spilled,
+        and such a kernel has been seen miscompiled (round 1; reproduced in round 5, tools/diag_spill.py) -- wrong values on part of
+        the nodes, silently.  The other instances (per-node rows, pending update, classes) are held against this one by the library
+        at their first launch (csrc/beat_ode_jit.hip: custom_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both."""
+        if getattr(self, "_verified", False):
+            return
+        worst = self._check_against_numpy(
+            "kernel", [f"state {s}" for s in self.state_names],
+            lambda y, t, p, dt: DeviceModel.__call__(self, states=y, t=t, parameters=p, dt=dt), self.numpy_step, self.step_error)
+        if worst is not None:
+            self.self_check_error = worst
+            self._verified = True
 
     # ---- monitored values --------------------------------------------------------------------------------
     def _monitor_launches(self, names):
@@ -698,39 +733,19 @@ class OdeFileModel(DeviceModel):
         return err
 
     def _monitor_self_check(self, mid: int, names) -> None:
-        """A selection's PLAIN kernel instance (uniform parameters) against ``numpy_monitor`` on the 2048 states of
-        ``_sample_states``, to 1e-6 of each value (of its row's scale where the value is smaller), at its first use in a process:
-        the reason is ``_self_check``'s.  The per-node and class instances are held against this one by the library at their first
-        launch (csrc/beat_ode_jit.hip: monitor_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both; a failing instance raises."""
-        import os
-
-        if os.environ.get("BEAT_JIT_SELF_CHECK", "1") == "0":
-            return
-        y = self._sample_states(2048)
-        p = self.init_parameter_values()
-        for t in (0.0, 0.37):
-            dev = self._monitor_staged(mid, len(names), y, t, p)
-            ref = self.numpy_monitor(y, t, p, list(names))
-            err = self.monitor_error(dev, ref)
-            if err.max() > 1e-6:
-                k, i = np.unravel_index(int(np.argmax(err)), err.shape)
-                raise RuntimeError(
-                    f"{self.name}: the compiled monitor kernel differs from the NumPy evaluation of the same expressions ({names[k]}, sample {i}: "
-                    f"{dev[k, i]!r} against {ref[k, i]!r}; {int((err > 1e-6).sum())} of {err.size} values) -- a miscompiled (heavily spilled) "
-                    "kernel; other compiler flags (BEAT_JIT_EXTRA_FLAGS) may help, BEAT_JIT_SELF_CHECK=0 skips this check")
+        """A selection's PLAIN kernel instance (uniform parameters) against ``numpy_monitor`` (``_check_against_numpy``), to 1e-6 of
+        each value (of its row's scale where the value is smaller), at its first use in a process: the reason is ``_self_check``'s.
+        The per-node and class instances are held against this one by the library at their first launch (csrc/beat_ode_jit.hip:
+        monitor_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both; a failing instance raises."""
+        self._check_against_numpy("monitor kernel", names, lambda y, t, p, dt: self._monitor_staged(mid, len(names), y, t, p),
+                                  lambda y, t, p, dt: self.numpy_monitor(y, t, p, list(names)), lambda dev, ref, y: self.monitor_error(dev, ref))
 
     def monitor_values(self, t, states, parameters, names=None):
         """gotranx's ``monitor_values(t, states, parameters)``: the values of the file's assignments ``names`` (None: all, in the
         order of ``monitor_names``; ``monitor_index(name)`` gives a row) for (S,) or (S, N) states and (P,) or (P, N) parameters,
         as (M,) or (M, N).  With a GPU the arrays are staged through the device and the monitor kernel runs; without one this is
         ``numpy_monitor``, as ``__call__`` is ``numpy_step``."""
-        try:
-            import torch
-
-            on_gpu = torch.cuda.is_available()
-        except Exception:  # noqa: BLE001
-            on_gpu = False
-        if not on_gpu:
+        if not _on_gpu():
             return self.numpy_monitor(states, t, parameters, names)
         names = self._monitor_selection(names)
         y = np.asarray(states, dtype=np.float64)
@@ -744,13 +759,7 @@ class OdeFileModel(DeviceModel):
     def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
         if dt is None:
             raise TypeError("dt is required")
-        try:
-            import torch
-
-            on_gpu = torch.cuda.is_available()
-        except Exception:  # noqa: BLE001
-            on_gpu = False
-        if on_gpu:
+        if _on_gpu():
             self.register()
             return super().__call__(states=states, t=t, parameters=parameters, dt=dt, **kwargs)
         return self.numpy_step(states, t, parameters, dt)

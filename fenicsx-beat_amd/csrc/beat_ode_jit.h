@@ -11,8 +11,10 @@
 // fails -- beat_ode_jit_launch returns BEAT_JIT_UNAVAILABLE and the caller launches the run-time-index kernel: a HIP kernel
 // either way, never a host path.
 #pragma once
+#include "beat_jit_check.h"
 #include "beat_ode_kernel.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -110,6 +112,55 @@ void beat_jit_derived_mask(const double* p, const SparseRows& sp, unsigned long 
   }
 }
 
+// Device scratch of a check: freed when its owner goes out of scope
+struct BeatJitScratch {
+  double* p = nullptr;
+  BeatJitScratch() = default;
+  BeatJitScratch(const BeatJitScratch&) = delete;
+  BeatJitScratch& operator=(const BeatJitScratch&) = delete;
+  ~BeatJitScratch() { (void)hipFree(p); }
+  int alloc(size_t doubles) {
+    BEAT_HIP_CHECK(hipMalloc(&p, sizeof(double) * doubles));
+    return BEAT_OK;
+  }
+};
+
+// What every check of an instance runs on: two result blocks a | b of rows x nc doubles (nc: the caller's first nodes, 1024 at
+// the most) at the head of one allocation -- a for the instance under test, b for the reference instance -- and `extra` doubles
+// behind them for the caller's own inputs.  The caller launches the two instances; compare() copies both blocks back and holds a
+// against b (beat_jit_check.h).
+struct BeatJitPair {
+  BeatJitScratch mem;
+  double *a = nullptr, *b = nullptr, *extra = nullptr;
+  size_t rows = 0;
+  int64_t nc = 0;
+  int alloc(size_t rows_, int64_t n, size_t extra_doubles = 0) {
+    rows = rows_;
+    nc = std::min<int64_t>(n, 1024);
+    if (int rc = mem.alloc(2 * rows * (size_t)nc + extra_doubles)) return rc;
+    a = mem.p;
+    b = a + rows * (size_t)nc;
+    extra = b + rows * (size_t)nc;
+    return BEAT_OK;
+  }
+  unsigned grid() const { return (unsigned)((nc + BEAT_BLOCK - 1) / BEAT_BLOCK); }
+  // both blocks start as the first nc nodes of the caller's state rows (a step works in place)
+  int copy_states(beat_ctx* ctx, const double* states, int64_t ld) {
+    for (size_t k = 0; k < rows; ++k)
+      for (double* dst : {a, b})
+        BEAT_HIP_CHECK(hipMemcpyAsync(dst + k * nc, states + (int64_t)k * ld, sizeof(double) * nc, hipMemcpyDeviceToDevice, ctx->stream));
+    return BEAT_OK;
+  }
+  // synchronises; *agree = false: *bad is the first value of a that differs from b's
+  int compare(beat_ctx* ctx, double rtol, double atol, bool* agree, BeatJitMismatch* bad) {
+    std::vector<double> h(2 * rows * (size_t)nc);
+    BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), a, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *agree = beat_jit_rows_agree(h.data(), h.data() + rows * (size_t)nc, rows, (size_t)nc, rtol, atol, bad);
+    return BEAT_OK;
+  }
+};
+
 // One step of the first nodes on two scratch copies: the instance `f` and the run-time-index kernel; BEAT_OK when they agree to
 // 1e-9 of each value (+ 1e-12 of its row's scale: the two differ in where the derived constants are rounded, 1e-12 measured),
 // BEAT_JIT_UNAVAILABLE (and the instance rejected) when they do not.  Synchronises; runs once per instance and process.
@@ -117,28 +168,17 @@ template <class Model>
 int beat_jit_self_check(beat_ctx* ctx, hipFunction_t f, const std::string& key, const double* states, int64_t n, int64_t ld,
                         ParamPack<Model::NP> prm, typename Model::Derived drv, const double* ppn, int64_t pld, double t, double dt,
                         int v_index, SparseRows sp) {
-  if (const char* e = std::getenv("BEAT_JIT_SELF_CHECK"))
-    if (e[0] == '0') return BEAT_OK;
+  if (beat_jit_checks_off()) return BEAT_OK;
   const bool many = sp.count > BEAT_MAX_SPARSE_ROWS_RT;  // more rows than the run-time-index kernel takes: checked against the all-rows kernel
-  int64_t nc = std::min<int64_t>(n, 1024);
-  double* scratch = nullptr;
-  const size_t bytes = sizeof(double) * 2 * Model::NS * (size_t)nc;
-  BEAT_HIP_CHECK(hipMalloc(&scratch, bytes));
-  struct Free {
-    double* p;
-    ~Free() { (void)hipFree(p); }
-  } guard{scratch};
-  double* sa = scratch;
-  double* sb = scratch + (size_t)Model::NS * nc;
-  for (int k = 0; k < Model::NS; ++k) {
-    BEAT_HIP_CHECK(hipMemcpyAsync(sa + (size_t)k * nc, states + (int64_t)k * ld, sizeof(double) * nc, hipMemcpyDeviceToDevice, ctx->stream));
-    BEAT_HIP_CHECK(hipMemcpyAsync(sb + (size_t)k * nc, states + (int64_t)k * ld, sizeof(double) * nc, hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  BeatJitPair pair;
+  if (int rc = pair.alloc(Model::NS, n)) return rc;
+  if (int rc = pair.copy_states(ctx, states, ld)) return rc;
+  double *sa = pair.a, *sb = pair.b;
+  int64_t nc = pair.nc, ldc = nc;
   PendingV none{nullptr, 0, nullptr, 0, {}};
   MarkedArgs mk{nullptr, nullptr, 0, nullptr, nullptr};
   double* vc = nullptr;
-  int64_t ldc = nc;
-  const unsigned grid = (unsigned)((nc + BEAT_BLOCK - 1) / BEAT_BLOCK);
+  const unsigned grid = pair.grid();
   void* args[] = {&sa, &nc, &ldc, &prm, &drv, &ppn, &pld, &t, &dt, &v_index, &vc, &none, &mk, &sp};
   BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   if (!many) {
@@ -154,14 +194,10 @@ int beat_jit_self_check(beat_ctx* ctx, hipFunction_t f, const std::string& key, 
       for (int64_t i = 0; i < nc; ++i) full[(size_t)k * nc + i] = prm.p[k];
     for (int j = 0; j < sp.count; ++j)
       for (int64_t i = 0; i < nc; ++i) full[(size_t)sp.idx[j] * nc + i] = rows[(size_t)j * nc + i];
-    double* dfull = nullptr;
-    BEAT_HIP_CHECK(hipMalloc(&dfull, sizeof(double) * full.size()));
-    struct Free2 {
-      double* p;
-      ~Free2() { (void)hipFree(p); }
-    } g2{dfull};
-    BEAT_HIP_CHECK(hipMemcpyAsync(dfull, full.data(), sizeof(double) * full.size(), hipMemcpyHostToDevice, ctx->stream));
-    const double* cfull = dfull;
+    BeatJitScratch dfull;
+    if (int rc = dfull.alloc(full.size())) return rc;
+    BEAT_HIP_CHECK(hipMemcpyAsync(dfull.p, full.data(), sizeof(double) * full.size(), hipMemcpyHostToDevice, ctx->stream));
+    const double* cfull = dfull.p;
     SparseRows none_sp{{0}, 0};
     BEAT_KERNEL((ode_step_kernel<Model, true, false, false, false>), dim3(grid), dim3(BEAT_BLOCK), 0, ctx->stream, sb, nc, ldc, prm, drv, cfull,
                 ldc, t, dt, v_index, vc, none, mk, none_sp);
@@ -169,28 +205,15 @@ int beat_jit_self_check(beat_ctx* ctx, hipFunction_t f, const std::string& key, 
     BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (dfull is freed when this block ends)
   }
   BEAT_LAUNCH_CHECK();
-  std::vector<double> h((size_t)2 * Model::NS * nc);
-  BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  const double* a = h.data();
-  const double* b = h.data() + (size_t)Model::NS * nc;
-  for (int k = 0; k < Model::NS; ++k) {
-    double scale = 0.0;
-    for (int64_t i = 0; i < nc; ++i) {
-      const double v = std::fabs(b[(size_t)k * nc + i]);
-      if (v == v && v > scale && v < 1e300) scale = v;
-    }
-    for (int64_t i = 0; i < nc; ++i) {
-      const double x = a[(size_t)k * nc + i], y = b[(size_t)k * nc + i];
-      if (x != x && y != y) continue;  // both NaN (a caller's garbage in, the same garbage out)
-      if (!(std::fabs(x - y) <= 1e-9 * std::fabs(y) + 1e-12 * scale)) {
-        char msg[256];
-        std::snprintf(msg, sizeof msg, "self-check against the run-time-index kernel failed (state %d, node %lld: %.17g against %.17g)", k,
-                      (long long)i, x, y);
-        beat_jit_reject(ctx, key, msg);
-        return BEAT_JIT_UNAVAILABLE;
-      }
-    }
+  bool agree = false;
+  BeatJitMismatch bad;
+  if (int rc = pair.compare(ctx, 1e-9, 1e-12, &agree, &bad)) return rc;
+  if (!agree) {
+    char msg[256];
+    std::snprintf(msg, sizeof msg, "self-check against the run-time-index kernel failed (state %d, node %lld: %.17g against %.17g)", (int)bad.row,
+                  (long long)bad.node, bad.x, bad.y);
+    beat_jit_reject(ctx, key, msg);
+    return BEAT_JIT_UNAVAILABLE;
   }
   return BEAT_OK;
 }

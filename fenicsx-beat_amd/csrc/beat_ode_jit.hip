@@ -227,26 +227,20 @@ bool run_hipcc(const JitState& s, const std::string& src, const std::string& out
 // the kernel's symbol in a code object (an offload bundle or a bare ELF): the NUL-terminated string that starts with _Z, names
 // ode_step_kernel (or ode_run_kernel, or ode_monitor_kernel: a translation unit instantiates ONE kernel) and carries no suffix (.kd, .private_seg_size ...
 // are the descriptor and its metadata)
-std::string kernel_symbol(const std::string& blob, const char* stem);
 std::string kernel_symbol(const std::string& blob) {
   for (const char* stem : {"ode_step_kernel", "ode_run_kernel", "ode_monitor_kernel"}) {
-    const std::string s = kernel_symbol(blob, stem);
-    if (!s.empty()) return s;
-  }
-  return "";
-}
-std::string kernel_symbol(const std::string& blob, const char* stem) {
-  size_t pos = 0;
-  while ((pos = blob.find(stem, pos)) != std::string::npos) {
-    size_t b = pos;
-    while (b > 0 && blob[b - 1] != '\0' && (pos - b) < 8) --b;
-    size_t e = pos;
-    while (e < blob.size() && blob[e] != '\0') ++e;
-    const std::string name = blob.substr(b, e - b);
-    if (name.size() > 2 && name[0] == '_' && name[1] == 'Z' && name.find('.') == std::string::npos &&
-        std::all_of(name.begin(), name.end(), [](unsigned char c) { return c > 32 && c < 127; }))
-      return name;
-    pos = e;
+    size_t pos = 0;
+    while ((pos = blob.find(stem, pos)) != std::string::npos) {
+      size_t b = pos;
+      while (b > 0 && blob[b - 1] != '\0' && (pos - b) < 8) --b;
+      size_t e = pos;
+      while (e < blob.size() && blob[e] != '\0') ++e;
+      const std::string name = blob.substr(b, e - b);
+      if (name.size() > 2 && name[0] == '_' && name[1] == 'Z' && name.find('.') == std::string::npos &&
+          std::all_of(name.begin(), name.end(), [](unsigned char c) { return c > 32 && c < 127; }))
+        return name;
+      pos = e;
+    }
   }
   return "";
 }
@@ -373,25 +367,31 @@ std::mutex& customs_mutex() {
   static std::mutex m;
   return m;
 }
+// what both registrations ask of a unit (`what`: model / monitor): a name [A-Za-z0-9_]+ and a source that defines struct <name>
+int check_unit(const char* what, const char* name, const char* source) {
+  for (const char* c = name; *c; ++c)
+    BEAT_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_', "%s name: [A-Za-z0-9_]+", what);
+  BEAT_REQUIRE(std::string(source).find(std::string("struct ") + name) != std::string::npos, "the source does not define struct %s", name);
+  return BEAT_OK;
+}
+// the index of the entry `same` accepts; `item` is appended when there is none
+template <class T, class Same>
+int find_or_append(std::vector<T>& v, T item, Same same) {
+  std::lock_guard<std::mutex> lock(customs_mutex());
+  auto it = std::find_if(v.begin(), v.end(), same);
+  if (it == v.end()) it = v.insert(v.end(), std::move(item));
+  return (int)(it - v.begin());
+}
 }  // namespace
 
 extern "C" int beat_ode_model_register(const char* name, const char* source, int num_states, int num_params, int v_index, int* model_id_out) {
   BEAT_REQUIRE(name != nullptr && source != nullptr && model_id_out != nullptr, "null argument");
   BEAT_REQUIRE(num_states >= 1 && num_states <= 512 && num_params >= 1 && num_params <= 1024, "bad state / parameter count");
   BEAT_REQUIRE(v_index >= 0 && v_index < num_states, "v_index %d out of range", v_index);
-  for (const char* c = name; *c; ++c)
-    BEAT_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_', "model name: [A-Za-z0-9_]+");
-  BEAT_REQUIRE(std::string(source).find(std::string("struct ") + name) != std::string::npos, "the source does not define struct %s", name);
+  if (int rc = check_unit("model", name, source)) return rc;
   BEAT_REQUIRE(beat_jit_enabled(), "a model given as source needs run-time compilation, which is not available here (beat_ode_jit_stats)");
-  std::lock_guard<std::mutex> lock(customs_mutex());
-  std::vector<CustomModel>& v = customs();
-  for (size_t k = 0; k < v.size(); ++k)
-    if (v[k].name == name && v[k].source == source) {
-      *model_id_out = BEAT_MODEL_CUSTOM_BASE + (int)k;
-      return BEAT_OK;
-    }
-  v.push_back(CustomModel{name, source, num_states, num_params, v_index});
-  *model_id_out = BEAT_MODEL_CUSTOM_BASE + (int)v.size() - 1;
+  *model_id_out = BEAT_MODEL_CUSTOM_BASE + find_or_append(customs(), CustomModel{name, source, num_states, num_params, v_index},
+                                                          [&](const CustomModel& c) { return c.name == name && c.source == source; });
   return BEAT_OK;
 }
 
@@ -431,17 +431,60 @@ hipFunction_t custom_instance(beat_ctx* ctx, const CustomModel& m, const std::st
     beat_set_error("the kernel of model %s could not be compiled (see the log in the cache directory; BEAT_JIT_VERBOSE=1)", m.name.c_str());
   return f;
 }
-}  // namespace
 
-namespace {
+// checked once per (name, instance, device) and process
 std::set<std::string>& custom_checked() {
   static std::set<std::string> v;
   return v;
 }
+bool custom_check_passed(const std::string& key, bool record = false) {
+  std::lock_guard<std::mutex> lock(customs_mutex());
+  if (record) custom_checked().insert(key);
+  return custom_checked().count(key) != 0;
+}
+
+// What makes a variant instance of a registered model compute what the plain instance computes: every node the parameters p0 of
+// node 0 / class 0 -- the caller's host vector, row 0 of its per-node rows or class 0 of its table -- as per-node rows, as a class
+// table (np + 1 doubles per class) and as marker bytes that are all 0, behind the two result blocks of one allocation.  The marker
+// bytes take (nc + 7) / 8 doubles: a byte per node for every nc.
+struct UniformVariant {
+  BeatJitPair pair;
+  std::vector<double> p0, hrows, htab;  // (the host sides of rows and table: alive until the copies to the device have run)
+  double *rows = nullptr, *table = nullptr;
+  unsigned char* marks = nullptr;
+  int build(beat_ctx* ctx, int num_params, size_t result_rows, int64_t n, const double* host_params, const double* ppn, int64_t pld,
+            const double* class_table) {
+    const size_t np = (size_t)num_params;
+    p0.assign(np, 1.0);
+    if (host_params != nullptr)
+      p0.assign(host_params, host_params + np);
+    else if (ppn != nullptr)
+      BEAT_HIP_CHECK(hipMemcpy2DAsync(p0.data(), sizeof(double), ppn, sizeof(double) * (size_t)pld, sizeof(double), np, hipMemcpyDeviceToHost,
+                                      ctx->stream));
+    else if (class_table != nullptr)
+      BEAT_HIP_CHECK(hipMemcpyAsync(p0.data(), class_table, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
+    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const size_t nc = (size_t)std::min<int64_t>(n, 1024);
+    if (int rc = pair.alloc(result_rows, n, np * nc + (np + 1) + (nc + 7) / 8)) return rc;
+    rows = pair.extra;
+    table = rows + np * nc;
+    marks = (unsigned char*)(table + np + 1);
+    hrows.resize(np * nc);
+    htab.assign(np + 1, 0.0);
+    for (size_t k = 0; k < np; ++k) {
+      htab[k] = p0[k];
+      std::fill_n(hrows.begin() + k * nc, nc, p0[k]);
+    }
+    BEAT_HIP_CHECK(hipMemcpyAsync(rows, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice, ctx->stream));
+    BEAT_HIP_CHECK(hipMemcpyAsync(table, htab.data(), sizeof(double) * htab.size(), hipMemcpyHostToDevice, ctx->stream));
+    BEAT_HIP_CHECK(hipMemsetAsync(marks, 0, nc, ctx->stream));
+    return BEAT_OK;
+  }
+};
 
 // A variant instance of a registered model (per-node rows, pending update, classes) against the model's PLAIN instance, once per
 // instance and process: one step of the caller's first nodes on two scratch copies, the variant given what makes it compute the
-// plain step (every node the parameters of node 0 / class 0, nothing pending) -- same arithmetic, same values.  Why: the kernel of
+// plain step (UniformVariant, nothing pending) -- same arithmetic, same values.  Why: the kernel of
 // a big generated model is heavily spilled (the reference's ToR-ORd files: ~400 SGPRs and ~500 VGPRs), and with ROCm 7.2 one of two
 // instances of such a kernel has been seen to reload registers under another lane mask than it spilled them under: wrong values on
 // the nodes that took the other arm of a branch, in ONE instance, the other one right (tools/diag_spill.py,
@@ -451,100 +494,41 @@ std::set<std::string>& custom_checked() {
 int custom_cross_check(beat_ctx* ctx, const CustomModel& m, hipFunction_t f, const std::string& what, bool per_node, bool marked,
                        const double* states, int64_t n, int64_t ld, const double* host_params, const double* ppn, int64_t pld,
                        const MarkedArgs& mk_in, double t, double dt, int v_index) {
-  if (const char* e = std::getenv("BEAT_JIT_SELF_CHECK"))
-    if (e[0] == '0') return BEAT_OK;
+  if (beat_jit_checks_off()) return BEAT_OK;
   const std::string key = m.name + "/" + what + "@" + std::to_string(ctx->device);
-  {
-    std::lock_guard<std::mutex> lock(customs_mutex());
-    if (custom_checked().count(key)) return BEAT_OK;
-  }
+  if (custom_check_passed(key)) return BEAT_OK;
   hipFunction_t f0 = custom_instance(ctx, m, "step_n0p0m0",
       "template __global__ void ode_step_kernel<" + m.name + ", false, false, false>(\n    double*, int64_t, int64_t, ParamPack<" + m.name +
       "::NP>, typename " + m.name + "::Derived, const double*, int64_t, double, double, int, double*, PendingV, MarkedArgs, SparseRows);");
   if (f0 == nullptr) return BEAT_EINVAL;
-  int64_t nc = std::min<int64_t>(n, 1024);
-  if (nc < 1) return BEAT_OK;
-  // the parameters of node 0 / class 0
-  std::vector<double> p0(m.np, 1.0);
-  if (host_params != nullptr) {
-    p0.assign(host_params, host_params + m.np);
-  } else if (per_node) {
-    BEAT_HIP_CHECK(hipMemcpy2DAsync(p0.data(), sizeof(double), ppn, sizeof(double) * (size_t)pld, sizeof(double), (size_t)m.np,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  } else if (marked) {
-    BEAT_HIP_CHECK(hipMemcpyAsync(p0.data(), mk_in.table, sizeof(double) * (size_t)m.np, hipMemcpyDeviceToHost, ctx->stream));
-    BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  }
-  const size_t ns = (size_t)m.ns, np = (size_t)m.np;
-  const size_t doubles = 2 * ns * (size_t)nc + np * (size_t)nc + (np + 1) + ((size_t)nc + 7) / 8;
-  double* scratch = nullptr;
-  BEAT_HIP_CHECK(hipMalloc(&scratch, sizeof(double) * doubles));
-  struct Free {
-    double* p;
-    ~Free() { (void)hipFree(p); }
-  } guard{scratch};
-  double* sa = scratch;
-  double* sb = sa + ns * (size_t)nc;
-  double* rows = sb + ns * (size_t)nc;
-  double* table = rows + np * (size_t)nc;
-  unsigned char* marks = (unsigned char*)(table + np + 1);
-  for (size_t k = 0; k < ns; ++k) {
-    BEAT_HIP_CHECK(hipMemcpyAsync(sa + k * nc, states + (int64_t)k * ld, sizeof(double) * nc, hipMemcpyDeviceToDevice, ctx->stream));
-    BEAT_HIP_CHECK(hipMemcpyAsync(sb + k * nc, states + (int64_t)k * ld, sizeof(double) * nc, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  std::vector<double> hrows(np * (size_t)nc), htab(np + 1, 0.0);
-  for (size_t k = 0; k < np; ++k) {
-    htab[k] = p0[k];
-    for (int64_t i = 0; i < nc; ++i) hrows[k * nc + i] = p0[k];
-  }
-  BEAT_HIP_CHECK(hipMemcpyAsync(rows, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice, ctx->stream));
-  BEAT_HIP_CHECK(hipMemcpyAsync(table, htab.data(), sizeof(double) * htab.size(), hipMemcpyHostToDevice, ctx->stream));
-  BEAT_HIP_CHECK(hipMemsetAsync(marks, 0, (size_t)nc, ctx->stream));
+  if (n < 1) return BEAT_OK;
+  UniformVariant u;
+  if (int rc = u.build(ctx, m.np, (size_t)m.ns, n, host_params, per_node ? ppn : nullptr, pld, marked ? mk_in.table : nullptr)) return rc;
+  if (int rc = u.pair.copy_states(ctx, states, ld)) return rc;
   PendingV none{nullptr, 0, nullptr, 0, {}, nullptr, 0};
   MarkedArgs mk0{nullptr, nullptr, 0, nullptr, nullptr};
-  MarkedArgs mkv = marked ? MarkedArgs{marks, table, m.np + 1, nullptr, nullptr} : mk0;
+  MarkedArgs mkv = marked ? MarkedArgs{u.marks, u.table, m.np + 1, nullptr, nullptr} : mk0;
   SparseRows sp{{0}, 0};
-  double drv = 0.0;
-  double* vc = nullptr;
-  int64_t ldc = nc;
-  const double* ppn_v = per_node ? rows : nullptr;
+  double drv = 0.0, *vc = nullptr, *sa = u.pair.a, *sb = u.pair.b;
+  int64_t nc = u.pair.nc, ldc = nc;
+  const double* ppn_v = per_node ? u.rows : nullptr;
   const double* ppn_0 = nullptr;
   int64_t pld_v = per_node ? nc : 0, pld_0 = 0;
-  const unsigned grid = (unsigned)((nc + BEAT_BLOCK - 1) / BEAT_BLOCK);
   {
-    void* args[] = {&sa, &nc, &ldc, p0.data(), &drv, &ppn_v, &pld_v, &t, &dt, &v_index, &vc, &none, &mkv, &sp};
-    BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+    void* args[] = {&sa, &nc, &ldc, u.p0.data(), &drv, &ppn_v, &pld_v, &t, &dt, &v_index, &vc, &none, &mkv, &sp};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f, u.pair.grid(), 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   }
   {
-    void* args[] = {&sb, &nc, &ldc, p0.data(), &drv, &ppn_0, &pld_0, &t, &dt, &v_index, &vc, &none, &mk0, &sp};
-    BEAT_HIP_CHECK(hipModuleLaunchKernel(f0, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+    void* args[] = {&sb, &nc, &ldc, u.p0.data(), &drv, &ppn_0, &pld_0, &t, &dt, &v_index, &vc, &none, &mk0, &sp};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f0, u.pair.grid(), 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   }
-  std::vector<double> h(2 * ns * (size_t)nc);
-  BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), scratch, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  const double* a = h.data();
-  const double* b = h.data() + ns * (size_t)nc;
-  for (size_t k = 0; k < ns; ++k) {
-    double scale = 0.0;
-    for (int64_t i = 0; i < nc; ++i) {
-      const double v = std::fabs(b[k * nc + i]);
-      if (v == v && v > scale && v < 1e300) scale = v;
-    }
-    for (int64_t i = 0; i < nc; ++i) {
-      const double x = a[k * nc + i], y = b[k * nc + i];
-      if (x != x && y != y) continue;  // both NaN (a caller's garbage in, the same garbage out)
-      if (!(std::fabs(x - y) <= 1e-10 * std::fabs(y) + 1e-13 * scale)) {
-        char msg[320];
-        std::snprintf(msg, sizeof msg, "instance %s of model %s differs from the model's plain instance (state %d, node %lld: %.17g against %.17g): "
-                      "miscompiled (heavily spilled) kernel; try other BEAT_JIT_EXTRA_FLAGS", what.c_str(), m.name.c_str(), (int)k, (long long)i, x, y);
-        beat_set_error("%s", msg);
-        return BEAT_EINVAL;
-      }
-    }
-  }
-  std::lock_guard<std::mutex> lock(customs_mutex());
-  custom_checked().insert(key);
+  bool agree = false;
+  BeatJitMismatch bad;
+  if (int rc = u.pair.compare(ctx, 1e-10, 1e-13, &agree, &bad)) return rc;
+  BEAT_REQUIRE(agree, "instance %s of model %s differs from the model's plain instance (state %d, node %lld: %.17g against %.17g): "
+               "miscompiled (heavily spilled) kernel; try other BEAT_JIT_EXTRA_FLAGS", what.c_str(), m.name.c_str(), (int)bad.row,
+               (long long)bad.node, bad.x, bad.y);
+  custom_check_passed(key, true);
   return BEAT_OK;
 }
 }  // namespace
@@ -634,90 +618,42 @@ std::string monitor_instantiation(const std::string& name, bool per_node, bool m
 }
 
 // A variant instance (per-node rows, classes) against the selection's PLAIN instance, once per instance and process, on the caller's
-// first nodes: the variant is given what makes it compute the plain values (every node the parameters of node 0 / class 0) --
-// same arithmetic, same values.  Why: custom_cross_check above.  The plain instance itself is held against the NumPy evaluation
-// of the same expressions by the caller (beat/models/ode_file.py).  A variant that fails is refused: the call fails.
+// first nodes: the variant is given what makes it compute the plain values (UniformVariant) -- same arithmetic, same values.  Why:
+// custom_cross_check above.  The plain instance itself is held against the NumPy evaluation of the same expressions by the caller
+// (beat/models/ode_file.py).  A variant that fails is refused: the call fails.
 int monitor_cross_check(beat_ctx* ctx, const CustomMonitor& mon, const CustomModel& unit, hipFunction_t f, const std::string& what,
                         bool per_node, bool marked, const double* states, int64_t n, int64_t ld, const double* ppn, int64_t pld,
                         const double* class_table, double t) {
-  if (const char* e = std::getenv("BEAT_JIT_SELF_CHECK"))
-    if (e[0] == '0') return BEAT_OK;
+  if (beat_jit_checks_off()) return BEAT_OK;
   const std::string key = mon.name + "/" + what + "@" + std::to_string(ctx->device);
-  {
-    std::lock_guard<std::mutex> lock(customs_mutex());
-    if (custom_checked().count(key)) return BEAT_OK;
-  }
+  if (custom_check_passed(key)) return BEAT_OK;
   hipFunction_t f0 = custom_instance(ctx, unit, "mon_n0m0", monitor_instantiation(mon.name, false, false));
   if (f0 == nullptr) return BEAT_EINVAL;
-  int64_t nc = std::min<int64_t>(n, 1024);
-  if (nc < 1) return BEAT_OK;
-  const size_t np = (size_t)unit.np, nm = (size_t)mon.nm;
-  std::vector<double> p0(np, 1.0);  // the parameters of node 0 / class 0
-  if (per_node) {
-    BEAT_HIP_CHECK(hipMemcpy2DAsync(p0.data(), sizeof(double), ppn, sizeof(double) * (size_t)pld, sizeof(double), np, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-  } else {
-    BEAT_HIP_CHECK(hipMemcpyAsync(p0.data(), class_table, sizeof(double) * np, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  const size_t doubles = 2 * nm * (size_t)nc + np * (size_t)nc + (np + 1) + ((size_t)nc + 7) / 8;
-  double* scratch = nullptr;
-  BEAT_HIP_CHECK(hipMalloc(&scratch, sizeof(double) * doubles));
-  struct Free {
-    double* p;
-    ~Free() { (void)hipFree(p); }
-  } guard{scratch};
-  double* oa = scratch;
-  double* ob = oa + nm * (size_t)nc;
-  double* rows = ob + nm * (size_t)nc;
-  double* table = rows + np * (size_t)nc;
-  unsigned char* marks = (unsigned char*)(table + np + 1);
-  std::vector<double> hrows(np * (size_t)nc), htab(np + 1, 0.0);
-  for (size_t k = 0; k < np; ++k) {
-    htab[k] = p0[k];
-    for (int64_t i = 0; i < nc; ++i) hrows[k * nc + i] = p0[k];
-  }
-  BEAT_HIP_CHECK(hipMemcpyAsync(rows, hrows.data(), sizeof(double) * hrows.size(), hipMemcpyHostToDevice, ctx->stream));
-  BEAT_HIP_CHECK(hipMemcpyAsync(table, htab.data(), sizeof(double) * htab.size(), hipMemcpyHostToDevice, ctx->stream));
-  BEAT_HIP_CHECK(hipMemsetAsync(marks, 0, (size_t)nc, ctx->stream));
+  if (n < 1) return BEAT_OK;
+  UniformVariant u;
+  if (int rc = u.build(ctx, unit.np, (size_t)mon.nm, n, nullptr, per_node ? ppn : nullptr, pld, class_table)) return rc;
   MarkedArgs mk0{nullptr, nullptr, 0, nullptr, nullptr};
-  MarkedArgs mkv = marked ? MarkedArgs{marks, table, unit.np + 1, nullptr, nullptr} : mk0;
-  const double* ppn_v = per_node ? rows : nullptr;
+  MarkedArgs mkv = marked ? MarkedArgs{u.marks, u.table, unit.np + 1, nullptr, nullptr} : mk0;
+  const double* ppn_v = per_node ? u.rows : nullptr;
   const double* ppn_0 = nullptr;
-  int64_t pld_v = per_node ? nc : 0, pld_0 = 0, ldo = nc;
+  double *oa = u.pair.a, *ob = u.pair.b;
+  int64_t nc = u.pair.nc, pld_v = per_node ? nc : 0, pld_0 = 0, ldo = nc;
   int ncls_v = marked ? 1 : 0, ncls_0 = 0;
-  const unsigned grid = (unsigned)((nc + BEAT_BLOCK - 1) / BEAT_BLOCK);
   {
-    void* args[] = {&states, &nc, &ld, p0.data(), &ppn_v, &pld_v, &mkv, &ncls_v, &t, &oa, &ldo};
-    BEAT_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+    void* args[] = {&states, &nc, &ld, u.p0.data(), &ppn_v, &pld_v, &mkv, &ncls_v, &t, &oa, &ldo};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f, u.pair.grid(), 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   }
   {
-    void* args[] = {&states, &nc, &ld, p0.data(), &ppn_0, &pld_0, &mk0, &ncls_0, &t, &ob, &ldo};
-    BEAT_HIP_CHECK(hipModuleLaunchKernel(f0, grid, 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
+    void* args[] = {&states, &nc, &ld, u.p0.data(), &ppn_0, &pld_0, &mk0, &ncls_0, &t, &ob, &ldo};
+    BEAT_HIP_CHECK(hipModuleLaunchKernel(f0, u.pair.grid(), 1, 1, BEAT_BLOCK, 1, 1, 0, ctx->stream, args, nullptr));
   }
-  std::vector<double> h(2 * nm * (size_t)nc);
-  BEAT_HIP_CHECK(hipMemcpyAsync(h.data(), scratch, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
-  BEAT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  const double* a = h.data();
-  const double* b = h.data() + nm * (size_t)nc;
-  for (size_t k = 0; k < nm; ++k) {
-    double scale = 0.0;
-    for (int64_t i = 0; i < nc; ++i) {
-      const double v = std::fabs(b[k * nc + i]);
-      if (v == v && v > scale && v < 1e300) scale = v;
-    }
-    for (int64_t i = 0; i < nc; ++i) {
-      const double x = a[k * nc + i], y = b[k * nc + i];
-      if (x != x && y != y) continue;  // both NaN (a caller's garbage in, the same garbage out)
-      if (!(std::fabs(x - y) <= 1e-10 * std::fabs(y) + 1e-13 * scale)) {
-        beat_set_error("instance %s of monitor %s differs from the monitor's plain instance (row %d, node %lld: %.17g against %.17g): "
-                       "miscompiled (heavily spilled) kernel; try other BEAT_JIT_EXTRA_FLAGS", what.c_str(), mon.name.c_str(), (int)k, (long long)i, x, y);
-        return BEAT_EINVAL;
-      }
-    }
-  }
-  std::lock_guard<std::mutex> lock(customs_mutex());
-  custom_checked().insert(key);
+  bool agree = false;
+  BeatJitMismatch bad;
+  if (int rc = u.pair.compare(ctx, 1e-10, 1e-13, &agree, &bad)) return rc;
+  BEAT_REQUIRE(agree, "instance %s of monitor %s differs from the monitor's plain instance (row %d, node %lld: %.17g against %.17g): "
+               "miscompiled (heavily spilled) kernel; try other BEAT_JIT_EXTRA_FLAGS", what.c_str(), mon.name.c_str(), (int)bad.row,
+               (long long)bad.node, bad.x, bad.y);
+  custom_check_passed(key, true);
   return BEAT_OK;
 }
 }  // namespace
@@ -727,19 +663,11 @@ extern "C" int beat_ode_monitor_register(int model_id, const char* name, const c
   BEAT_REQUIRE(num_outputs >= 1 && num_outputs <= BEAT_MAX_MONITORS, "1..%d monitored values per launch, got %d", BEAT_MAX_MONITORS, num_outputs);
   BEAT_REQUIRE(beat_custom_model_info(model_id, nullptr, nullptr, nullptr) == BEAT_OK,
                "monitored values belong to a model registered as source (beat_ode_model_register), not to model id %d", model_id);
-  for (const char* c = name; *c; ++c)
-    BEAT_REQUIRE((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_', "monitor name: [A-Za-z0-9_]+");
-  BEAT_REQUIRE(std::string(source).find(std::string("struct ") + name) != std::string::npos, "the source does not define struct %s", name);
+  if (int rc = check_unit("monitor", name, source)) return rc;
   BEAT_REQUIRE(beat_jit_enabled(), "monitored values need run-time compilation, which is not available here (beat_ode_jit_stats)");
-  std::lock_guard<std::mutex> lock(customs_mutex());
-  std::vector<CustomMonitor>& v = monitors();
-  for (size_t k = 0; k < v.size(); ++k)
-    if (v[k].model_id == model_id && v[k].name == name && v[k].source == source) {
-      *monitor_id_out = (int)k;
-      return BEAT_OK;
-    }
-  v.push_back(CustomMonitor{model_id, name, source, num_outputs});
-  *monitor_id_out = (int)v.size() - 1;
+  *monitor_id_out = find_or_append(monitors(), CustomMonitor{model_id, name, source, num_outputs}, [&](const CustomMonitor& c) {
+    return c.model_id == model_id && c.name == name && c.source == source;
+  });
   return BEAT_OK;
 }
 

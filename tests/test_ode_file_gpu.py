@@ -328,6 +328,70 @@ def test_self_checks_catch_a_miscompiled_generated_kernel(hip_ctx, monkeypatch):
             model.register()
 
 
+MONITOR_BOUND = 1e-11  # what tests/test_monitor_gpu.py holds a monitored value to, relative to its row's scale
+
+
+@pytest.mark.parametrize("n", [1, 9, 1025])
+def test_first_launches_of_the_variant_instances_at_the_edges_of_the_check(hip_ctx, n):
+    """The library holds a variant instance against the plain one at its FIRST launch, on min(n, 1024) nodes and with scratch it
+    lays out itself: two result blocks, per-node rows, a class table and a marker byte per node behind it.  Its edges: one node; 9
+    (marker bytes that do not fill a double); 1025 (more nodes than the check takes, a second block).  A model name of its own per
+    n, so that each case IS the first launch of its four variant instances -- per-node step, class step, per-node monitor, class
+    monitor: none may be refused, each gives the NumPy evaluation's values, and the monitors leave the state array as it was."""
+    import ctypes as C
+
+    import beat
+    from beat._device import StateArray
+    from beat.models import from_ode
+    from beat.odesolver import _DeviceODE
+
+    model = from_ode(SMALL, name=f"small_first_launch_{n}")
+    names = list(model.monitor_names)
+    y = _states(model, n, 21)
+    t, dt = 1.0, 0.02  # (inside the stimulus window)
+    sets = [model.init_parameter_values(stim_amplitude=30.0), model.init_parameter_values(stim_amplitude=12.0, g_in=7.0, v_pump=0.03)]
+    marks = (np.arange(n) % 2).astype(np.uint8)
+    p_class = np.stack([sets[m] for m in marks], axis=1)
+    p_node = np.repeat(sets[0][:, None], n, axis=1)
+    p_node[model.parameter_index("g_in")] *= np.linspace(0.5, 1.5, n)
+
+    def step_error(dev, ref, y0):
+        assert dev.shape == ref.shape and np.isfinite(dev).all()
+        return (np.abs(dev - ref) / np.maximum(np.maximum(np.abs(ref), np.abs(y0)), 1e-12)).max()
+
+    def monitor_error(dev, ref):
+        assert dev.shape == ref.shape and np.isfinite(ref).all() and np.isfinite(dev).all()
+        return (np.abs(dev - ref) / np.maximum(np.maximum(np.abs(ref), np.abs(ref).max(axis=1, keepdims=True)), 1e-300)).max()
+
+    err = step_error(model(states=y, t=t, parameters=p_node, dt=dt), model.numpy_step(y, t, p_node, dt), y)
+    print(f"n={n}: per-node step {err:.3e}")
+    assert err < 1e-11
+    ode = _DeviceODE(hip_ctx, model, model.num_states, n, 0, None, beat.telemetry.NullMonitor())
+    ode.set_initial(y)
+    ode.explicit_classes = True
+    ode.set_classes(hip_ctx.from_numpy(marks), sets)
+    ode.step(t, dt, v_index=model.state_index("V"))
+    y1 = ode.states.numpy()
+    err = step_error(y1, model.numpy_step(y, t, p_class, dt), y)
+    print(f"n={n}: class step {err:.3e}")
+    assert err < 1e-11
+    # the monitors on the resident array, every byte of which (padding included) must stay what it is
+    before = ode.states.buf.cpu().numpy().tobytes()
+    out = StateArray(hip_ctx, len(names), n)
+    rows = hip_ctx.from_numpy(np.ascontiguousarray(p_node))
+    model.monitor_on_device(hip_ctx, names, ode.states.ptr, n, ode.states.ld, t, out.ptr, out.ld, per_node=(C.c_void_p(rows.data_ptr()), n))
+    hip_ctx.synchronize()
+    err = monitor_error(out.numpy(), model.numpy_monitor(y1, t, p_node))
+    print(f"n={n}: per-node monitor {err:.3e}")
+    assert err <= MONITOR_BOUND
+    ode.monitor_rows(names, t, out.ptr, out.ld)
+    hip_ctx.synchronize()
+    err = monitor_error(out.numpy(), model.numpy_monitor(y1, t, p_class))
+    print(f"n={n}: class monitor {err:.3e}")
+    assert err <= MONITOR_BOUND
+    assert ode.states.buf.cpu().numpy().tobytes() == before
+
+
 def test_registration_hands_out_no_id_until_the_self_check_has_passed(hip_ctx, monkeypatch):
     """``register()`` used to set the id before ``_self_check()`` ran, so a second call after a failed check returned
     the id of a kernel known to be wrong.  With a check made to fail once: no id, the check runs again at the next call, and only
