@@ -18,11 +18,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Any
 
 import numpy as np
 
 from . import _hip
+from ._deferred import DeferredUpdate
 
 
 @dataclass
@@ -127,6 +129,20 @@ def spectrum_bounds(A_tab: np.ndarray, ratio: float = 5.0) -> tuple[float, float
     return lmax / ratio, lmax
 
 
+def _owned(name):
+    """Attribute of ``HipOps`` that is its DeferredUpdate's (the names bench.py, the tools and the tests read and assign)."""
+    return property(lambda self: getattr(self.deferred, name), lambda self, value: setattr(self.deferred, name, value))
+
+
+def _solve_record(call):
+    """(record, ring_base, count) of one solve: ``call(info, pend)`` is the C call that fills the record and the pair of what the
+    solve leaves pending.  A solve that did not converge is reported, not raised."""
+    info = _hip.KspInfo()
+    pend = (C.c_int * 2)()
+    _hip.check(call(C.byref(info), pend), allow_not_converged=True)
+    return KspResult(info.iterations, info.residual_norm, info.converged_reason, info.rhs_norm), int(pend[0]), int(pend[1])
+
+
 class HipOps:
     """The product compute backend: every method is one C-ABI call into libbeat_hip.so."""
 
@@ -186,13 +202,14 @@ class HipOps:
                      for j in range(nfields - 3)]
         self.p = self.ring[0]
         self.st = ctx.zeros(_hip.ST_SIZE)
-        self.pending = None            # (field, ring_base, count) of a deferred potential update
-        self.st_ptr_for_flush = None   # scalar state the pending update belongs to (None: the handle's own)
-        # a solve that is enqueued and not yet looked at (solve_begin): the field it works on; its record arrives with solve_finish,
-        # which `on_finish` (the PDE model: its .ksp, its status) and `ksp_log` (a list, when a caller wants every record) receive
-        self.open_x = None
-        self.on_finish = None
-        self.ksp_log = None
+        # who completes the potential: what a solve left pending, the solve left open (see _deferred.py)
+        lib, ring = self.lib, self.ring[0].ptr  # (the calls hold no reference to this object)
+        self.deferred = DeferredUpdate(SimpleNamespace(
+            x_flush=lambda st, x, base: _hip.check(lib.beat_pde_x_flush(handle, C.c_void_p(st), x.ptr, ring, fld, base, 0)),
+            x_flush_events=lambda st, x, base, maps, t0, t1: _hip.check(
+                lib.beat_pde_x_flush_events(handle, C.c_void_p(st), x.ptr, ring, fld, base, maps, t0, t1)),
+            solve_end=lambda: _solve_record(lambda info, pend: lib.beat_pde_solve_end(handle, info, pend)),
+            guess_pending=lambda: bool(lib.beat_pde_guess_pending(handle))), (handle, ring, fld), len(self.ring))
         self.pc_degree = 1
         self._coeffs = (1.0, 0.5, 0.0)
         self.guess_order = 0  # x0 = v_ unless asked for (set_guess_order; BaseModel asks for "auto" by default)
@@ -253,6 +270,9 @@ class HipOps:
             T.ctypes.data_as(C.c_void_p), Me.ctypes.data_as(C.c_void_p), ptr(m_dev),
             None if m_const is None else m_const.ctypes.data_as(C.c_void_p), ptr(a_dev), ptr(mass), ptr(stiff), n))
         return cls(ctx, shape_local, lo_phys, hi_phys, mass, stiff, per_node=True)
+
+    pending, st_ptr_for_flush, open_x = _owned("pending"), _owned("st_ptr"), _owned("open_x")
+    flushes, on_finish, ksp_log = _owned("flushes"), _owned("on_finish"), _owned("ksp_log")
 
     # -- field helpers ----------------------------------------------------------------------
     def new_field(self):
@@ -364,12 +384,11 @@ class HipOps:
         """With ``defer_flush`` the last partially filled cycle of search directions is left unapplied and recorded
         in ``self.pending`` = (field, ring_base, count): the next ionic kernel adds it (beat_ode_step_pending) or
         ``flush_pending`` does."""
-        self.flush_pending()
-        self.st_ptr_for_flush = None  # a pending update of this solve belongs to the handle's own scalar state
+        self.deferred.new_solve()
         ptrs, amps, k = self._stim_args(stim_w, stim_amp)
-        return self._result(lambda info, pend: self.lib.beat_pde_solve_ex(
+        return self.deferred.solved(x, *_solve_record(lambda info, pend: self.lib.beat_pde_solve_ex(
             self.handle, v_prev.ptr, ptrs, amps, k, x.ptr, C.c_void_p(self.work.data_ptr()), rtol, atol, max_it, int(defer_flush),
-            info, pend), x)
+            info, pend)))
 
     # -- the solve in two halves (beat_pde_solve_begin / _end): see include/beat_hip.h ------------------------------------
     def can_open(self) -> bool:
@@ -379,8 +398,7 @@ class HipOps:
         """Enqueue the solve and return without waiting.  Until ``solve_finish`` -- which everything that needs the result or
         the field calls: ``flush_pending``, the model's ``ksp``, the next ionic step -- the device works and the host is free.
         ``comm``: the slab-decomposed solve (beat_pde_solve_dist_begin), its exchanges and all-reduces enqueued with it."""
-        self.flush_pending()
-        self.st_ptr_for_flush = None
+        self.deferred.new_solve()
         ptrs, amps, k = self._stim_args(stim_w, stim_amp)
         if comm is not None:
             _hip.check(self.lib.beat_pde_solve_dist_begin(self.handle, comm.handle, v_prev.ptr, ptrs, amps, k, x.ptr,
@@ -388,49 +406,20 @@ class HipOps:
         else:
             _hip.check(self.lib.beat_pde_solve_begin(self.handle, v_prev.ptr, ptrs, amps, k, x.ptr, C.c_void_p(self.work.data_ptr()),
                                                      rtol, atol, max_it))
-        self.open_x = x
-
-    def _result(self, call, x, notify: bool = False) -> KspResult:
-        """One solve's record: ``call(info, pend)`` is the C call that fills it and the pair of what it leaves pending, which goes to
-        ``self.pending`` when ``x`` (the field solved for) is given.  A solve that did not converge is reported, not raised.
-        ``notify``: ``on_finish`` receives the record too."""
-        info = _hip.KspInfo()
-        pend = (C.c_int * 2)()
-        _hip.check(call(C.byref(info), pend), allow_not_converged=True)
-        if x is not None and (pend[1] > 0 or self.lib.beat_pde_guess_pending(self.handle)):  # (the guess increment alone may be due)
-            self.pending = (x, int(pend[0]), int(pend[1]))
-        res = KspResult(info.iterations, info.residual_norm, info.converged_reason, info.rhs_norm)
-        if self.ksp_log is not None:
-            self.ksp_log.append(res)
-        if notify and self.on_finish is not None:
-            self.on_finish(res)
-        return res
+        self.deferred.opened(x)
 
     def solve_finish(self):
-        """Wait for the open solve (more iterations are enqueued if it needs them), take its record; what it leaves pending
-        goes to ``self.pending`` as after ``solve_single(defer_flush=True)``.  None when no solve is open."""
-        if self.open_x is None:
-            return None
-        x, self.open_x = self.open_x, None
-        return self._result(lambda info, pend: self.lib.beat_pde_solve_end(self.handle, info, pend), x, notify=True)
-
-    def finished_behind(self):
-        """The open solve was finished inside the ionic call that was enqueued behind it (beat_ode_step_* with pending = -1):
-        collect its record; nothing is pending."""
-        self.open_x = None
-        self.pending = None
-        # (no solve open: the last record)
-        return self._result(lambda info, pend: self.lib.beat_pde_solve_end(self.handle, info, pend), None, notify=True)
+        """Wait for the open solve (more iterations are enqueued if it needs them) and take its record; None when no solve is open."""
+        return self.deferred.finish()
 
     def solve_dist(self, comm: "LibComm", v_prev, stim_w, stim_amp, x, rtol, atol, max_it, defer_flush: bool = False) -> KspResult:
         """The slab-decomposed solve as ONE C call (beat_pde_solve_dist): halo exchange and all-reduces are issued
         by the library on ``comm``; same deferred-update contract as solve_single."""
-        self.flush_pending()
-        self.st_ptr_for_flush = None
+        self.deferred.new_solve()
         ptrs, amps, k = self._stim_args(stim_w, stim_amp)
-        return self._result(lambda info, pend: self.lib.beat_pde_solve_dist(
+        return self.deferred.solved(x, *_solve_record(lambda info, pend: self.lib.beat_pde_solve_dist(
             self.handle, comm.handle, v_prev.ptr, ptrs, amps, k, x.ptr, C.c_void_p(self.work.data_ptr()), rtol, atol, max_it,
-            int(defer_flush), info, pend), x)
+            int(defer_flush), info, pend)))
 
     def set_guess_order(self, order: int) -> None:
         """0: every solve starts from x0 = v_; m = 1..4: from v_ plus the degree-(m-1) extrapolation in time of the last
@@ -479,29 +468,7 @@ class HipOps:
 
     def flush_pending(self) -> None:
         """Apply a deferred update of the potential (no-op when nothing is pending).  A solve that is still open is finished first."""
-        if self.open_x is not None:
-            self.solve_finish()
-        if self.pending is not None:
-            x, ring_base, _ = self.pending
-            self.pending = None
-            self.flushes = getattr(self, "flushes", 0) + 1  # separate passes taken (the fused step should take none)
-            _hip.check(self.lib.beat_pde_x_flush(self.handle, C.c_void_p(self.st_ptr_for_flush), x.ptr, self.ring[0].ptr,
-                                                 self.fld, ring_base, 0))
-
-    def flush_pending_events(self, field, maps, t0: float, t1: float) -> bool:
-        """``flush_pending`` and the event maps' pass over ``field`` in one (beat_pde_x_flush_events; ``maps``: a reference to a
-        ``_hip.EventMaps``), if it is ``field`` whose update is pending.  False: nothing of that field is pending (an open solve has
-        been finished), the caller observes the field as it is."""
-        if self.open_x is not None:
-            self.solve_finish()
-        if self.pending is None or self.pending[0].ptr.value != field.ptr.value:
-            return False
-        x, ring_base, _ = self.pending
-        _hip.check(self.lib.beat_pde_x_flush_events(self.handle, C.c_void_p(self.st_ptr_for_flush), x.ptr, self.ring[0].ptr,
-                                                    self.fld, ring_base, maps, t0, t1))
-        self.pending = None
-        self.flushes = getattr(self, "flushes", 0) + 1
-        return True
+        self.deferred.flush()
 
     def apply(self, which, x, y):
         _hip.check(self.lib.beat_pde_apply(self.handle, which, x.ptr, y.ptr))
@@ -892,8 +859,6 @@ class DiffusionSolver:
         ``BEAT_STAGE_DRIVEN=1``) keeps the iteration in Python, stage by stage over ``torch.distributed``: that is
         the orchestration the CPU tests run with oracle-backed ``ops`` on gloo, and the only route for the
         polynomial preconditioner."""
-        import os
-
         self.ops = ops
         self.slab = slab
         self.group = group
@@ -980,16 +945,16 @@ class DiffusionSolver:
         """x <- solution of A x = B v_prev + dt*sum amp_k w_k, started from x0 = v_prev.  ``defer_flush``: see
         HipOps.solve_single (backends without that support simply apply the update)."""
         ops = self.ops
-        can_defer = defer_flush and hasattr(ops, "flush_pending")
-        if hasattr(ops, "flush_pending"):
-            ops.flush_pending()
+        can_defer = defer_flush and hasattr(ops, "deferred")  # (the oracle-backed ops of the CPU tests have none, and their
+        # solve_single takes no defer_flush)
         if self.dist is None and self.libcomm is None:
             if can_defer:
-                ops.st_ptr_for_flush = None
                 return ops.solve_single(v_prev, stim_w, stim_amp, x, rtol, atol, max_it, defer_flush=True)
             return ops.solve_single(v_prev, stim_w, stim_amp, x, rtol, atol, max_it)
         if self.libcomm is not None and ops.pc_num_passes == 0:
             return ops.solve_dist(self.libcomm, v_prev, stim_w, stim_amp, x, rtol, atol, max_it, defer_flush=bool(can_defer))
+        if hasattr(ops, "deferred"):
+            ops.deferred.new_solve()
         self.exchange_halo(v_prev)
         ops.rhs(v_prev, stim_w, stim_amp, x)
         self._allreduce(ops.st[0:3])
@@ -1033,8 +998,7 @@ class DiffusionSolver:
             nupd = int(st[_hip.ST_NUPD])
             if nupd % K:
                 if can_defer:
-                    ops.pending = (x, (nupd // K) * K, nupd % K)
-                    ops.st_ptr_for_flush = ops.st.data_ptr()
+                    ops.deferred.leave(x, (nupd // K) * K, nupd % K, st_ptr=ops.st.data_ptr())
                 else:
                     ops.x_flush(x, (nupd // K) * K, False)
         its = int(st[_hip.ST_ITERS])

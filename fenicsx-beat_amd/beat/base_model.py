@@ -170,9 +170,7 @@ class BaseModel:
     def ksp(self):
         """KSP-like record of the last solve (what telemetry.py:67-76 reads from PETSc's KSP).  A solve the fused step left
         open is finished here."""
-        ops = getattr(self, "_ops", None)
-        if ops is not None and getattr(ops, "open_x", None) is not None:
-            ops.solve_finish()
+        self._finish_open_solve()
         return self._ksp
 
     @ksp.setter
@@ -183,14 +181,15 @@ class BaseModel:
     def status(self) -> Status:
         """``Status.NOT_CONVERGING`` once a linear solve has run out of iterations (base_model.py:23-30).  Like ``ksp``, reading it
         finishes a solve the fused step left open: the record of the LAST step is in it too."""
-        ops = getattr(self, "_ops", None)
-        if ops is not None and getattr(ops, "open_x", None) is not None:
-            ops.solve_finish()
+        self._finish_open_solve()
         return self._status
 
     @status.setter
     def status(self, value: Status) -> None:
         self._status = value
+
+    def _finish_open_solve(self) -> None:
+        """Hook of ``ksp`` and ``status``: a model whose step may leave its solve open finishes it here."""
 
     @abc.abstractmethod
     def _setup_state_space(self) -> None: ...
@@ -252,29 +251,33 @@ class BaseModel:
         (base_model.py:188-194)."""
         self._ops.set_timestep(float(self.C_m), float(self.parameters["theta"]), float(self._timestep))
 
+    # -- the prologue of a PDE step: the time, the operators if dt changed, the active stimuli (MonodomainModel.step_in_place, the
+    # fused routes' step, tracks ``pde_update_matrices`` only)
+    def _set_timestep(self, dt) -> None:
+        if not abs(dt - float(self._timestep)) < 1.0e-12:
+            self._timestep.value = dt
+            with self.monitor.track_time("pde_update_matrices"):
+                self._update_matrices()
+
+    def _active_stimuli(self):
+        """(weight fields, amplitudes) of the stimuli that are on at ``self.time``."""
+        stim_w, stim_amp = [], []
+        for s in self._stimuli:
+            a = s.amplitude()
+            if a != 0.0 and s.field is not None:
+                stim_w.append(s.field)
+                stim_amp.append(a)
+        return stim_w, stim_amp
+
     def step(self, interval):
         t0, t1 = interval
         dt = t1 - t0
-        theta = self.parameters["theta"]
-        t = t0 + theta * dt
-
         with self.monitor.track_time("pde_total_step"):
             with self.monitor.track_time("pde_set_time"):
-                self.time.value = t
-
-            timestep_unchanged = abs(dt - float(self._timestep)) < 1.0e-12
-            if not timestep_unchanged:
-                self._timestep.value = dt
-                with self.monitor.track_time("pde_update_matrices"):
-                    self._update_matrices()
-
+                self.time.value = t0 + self.parameters["theta"] * dt
+            self._set_timestep(dt)
             with self.monitor.track_time("pde_update_rhs"):
-                stim_w, stim_amp = [], []
-                for s in self._stimuli:
-                    a = s.amplitude()
-                    if a != 0.0 and s.field is not None:
-                        stim_w.append(s.field)
-                        stim_amp.append(a)
+                stim_w, stim_amp = self._active_stimuli()
 
             with self.monitor.track_time("pde_linear_solve"):
                 self._solve_linear(stim_w, stim_amp)

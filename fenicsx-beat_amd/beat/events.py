@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _hip
+from ._deferred import DeferredUpdate
 from .grid import Function
 
 # public name -> field of beat_event_maps
@@ -106,12 +107,12 @@ class EventRecorder:
 
     def observe(self, t0, t1) -> None:
         """The step (t0, t1) has just been made: update the maps from ``f``.  One launch.  Where ``f`` is the potential whose solve is still
-        open, that solve is finished first: the host waits for it and reads its record (``flush_pending_events``)."""
+        open, that solve is finished first: the host waits for it and reads its record (``DeferredUpdate.flush_events``)."""
         f = self._f
         args = C.byref(self._args)
         # f aliases the potential row whose update the diffusion operator still owes (the fused split step): this pass applies it
-        ops = getattr(f._alias_sync, "__self__", None) if f._alias is not None else None
-        if ops is not None and hasattr(ops, "flush_pending_events") and ops.flush_pending_events(f._alias, args, float(t0), float(t1)):
+        owner = f._alias_sync if f._alias is not None else None
+        if isinstance(owner, DeferredUpdate) and owner.flush_events(f._alias, args, float(t0), float(t1)):
             self.fused_passes += 1
         else:
             _hip.check(self._ctx.lib.beat_field_events(self._ctx.handle, f.field.ptr, self._n, args, float(t0), float(t1)))

@@ -9,10 +9,12 @@ meshes use per-node stencil rows."""
 from __future__ import annotations
 
 import logging
+import os
 
 from . import grid
 from ._engine import DiffusionSolver, build_ops, conductivity_array
 from .base_model import BaseModel
+from .telemetry import NullMonitor
 
 logger = logging.getLogger(__name__)
 
@@ -60,12 +62,8 @@ class MonodomainModel(BaseModel):
         sees the same all-reduced scalars on the device, so every rank's launch behind the solve does the same); nobody who
         wants the KSP record step by step (a monitor; PETSc's ``ksp_error_if_not_converged``, whose exception belongs to the
         failing step); BEAT_LAZY_KSP=0 switches it off, BEAT_LAZY_KSP_DIST=0 on decomposed grids only."""
-        import os
-
-        from .telemetry import NullMonitor
-
         d, ops = self._diffusion, self._ops
-        if os.environ.get("BEAT_LAZY_KSP", "1") == "0" or not hasattr(ops, "can_open"):
+        if os.environ.get("BEAT_LAZY_KSP", "1") == "0":
             return False
         if type(self.monitor) is not NullMonitor:
             return False
@@ -84,14 +82,31 @@ class MonodomainModel(BaseModel):
         read when somebody asks, or when the next step has put its ionic kernel behind the solve -- finishes it."""
         rtol, atol, max_it = self._solver_tolerances()
         if lazy and defer_flush:
-            ops = self._ops
-            ops.on_finish = self._solve_finished
-            ops.solve_begin(field, stim_w, stim_amp, field, rtol, atol, max_it, comm=self._diffusion.libcomm)
+            self._ops.on_finish = self._solve_finished
+            self._ops.solve_begin(field, stim_w, stim_amp, field, rtol, atol, max_it, comm=self._diffusion.libcomm)
             return None
         self.ksp = self._diffusion.solve(field, stim_w, stim_amp, field, rtol=rtol, atol=atol, max_it=max_it,
                                          defer_flush=defer_flush)
         self._check_converged()
         return self.ksp
+
+    def step_in_place(self, field, t0, t1, deferred: bool = False) -> None:
+        """The PDE step of the fused routes, v_ and the unknown sharing ``field``.  ``deferred``: the last update of the potential
+        may stay pending, and -- with nobody asking for the KSP record step by step -- the solve is left open: the next step's
+        ionic launch goes into the queue behind it before the host waits, and the device never idles in between."""
+        with self.monitor.track_time("pde_total_step"):
+            self.time.value = t0 + self.parameters["theta"] * (t1 - t0)
+            self._set_timestep(t1 - t0)
+            stim_w, stim_amp = self._active_stimuli()
+            lazy = deferred and self.can_solve_lazily()
+            with self.monitor.track_time("pde_linear_solve"):
+                self.solve_in_place(field, stim_w, stim_amp, defer_flush=deferred, lazy=lazy)
+            if not lazy:
+                self.monitor.record_ksp(self.ksp)
+        self.monitor.advance_step(t0, t1)
+
+    def _finish_open_solve(self) -> None:
+        self._ops.solve_finish()
 
     def _solve_finished(self, res) -> None:
         self._ksp = res

@@ -9,14 +9,19 @@ copies per step (steps 2-4, 6, 7 of the reference sequence), none of the traffic
 
 from __future__ import annotations
 
+import ctypes as C
 import logging
 import os
+import time
 from dataclasses import dataclass, field
 from typing import Protocol
 
 import numpy as np
 
+from . import _hip
+from ._engine import KspResult
 from .monodomain_model import MonodomainModel
+from .odesolver import DolfinMultiODESolver, DolfinODESolver
 from .telemetry import BaseMonitor, NullMonitor
 
 logger = logging.getLogger(__name__)
@@ -85,22 +90,17 @@ class MonodomainSplittingSolver:
     def _can_batch(self, recorder) -> bool:
         from .ecg import LeadRecorder
         from .events import EventRecorder
-        from .odesolver import DolfinODESolver
 
         if isinstance(recorder, (EventRecorder, LeadRecorder)):
             return False  # event maps and lead traces inside the library's step loops: not built
         if not (isinstance(self.ode, DolfinODESolver) and self._can_fuse() and np.isclose(self.theta, 1.0)):
             return False
         ode, pde = self.ode, self.pde
-        ops = getattr(pde, "_ops", None)
-        if ops is None or not hasattr(ops, "small_active"):
-            return False
-        if not ops.small_active():
+        if not pde._ops.small_active():
             # a grid of any size on one rank: the step loop inside the library (beat_split_steps_big); no probe rows there
             # (the potential is complete only after the next ionic launch or a flush)
-            diff = getattr(pde, "_diffusion", None)
-            one_rank = diff is not None and getattr(diff, "dist", None) is None and getattr(diff, "libcomm", None) is None
-            if not (one_rank and recorder is None and hasattr(ops, "work") and os.environ.get("BEAT_BATCH_BIG", "1") != "0"):
+            if not (pde._diffusion.dist is None and pde._diffusion.libcomm is None and recorder is None
+                    and os.environ.get("BEAT_BATCH_BIG", "1") != "0"):
                 return False
         if not all(type(m) is NullMonitor for m in (self.monitor, pde.monitor, getattr(ode._dev, "monitor", NullMonitor()))):
             return False  # someone wants per-step timings / KSP records
@@ -112,11 +112,6 @@ class MonodomainSplittingSolver:
         return ode._dev._param_args()[0] is not None  # uniform parameters (one host vector)
 
     def _batched_steps(self, steps, recorder) -> None:
-        import ctypes as C
-
-        from . import _hip
-        from ._engine import KspResult
-
         ode, pde = self.ode, self.pde
         ops, dev, row = pde._ops, ode._dev, ode._v_row
         dt = steps[0][1] - steps[0][0]
@@ -124,22 +119,12 @@ class MonodomainSplittingSolver:
         # of the library's loop applies it, as step() would have (pending_in) -- a call of solve() per output interval does not pay
         # a pass over the potential per call (2 ms at 512^3).  Anything else that is pending (another row, another time step, the
         # one-launch path) is flushed.
-        carry = 0
-        if getattr(ops, "open_x", None) is not None:
-            ops.solve_finish()
-        same_dt = abs(dt - float(pde._timestep)) < 1.0e-12
-        pend = getattr(ops, "pending", None)
-        if (same_dt and pend is not None and not ops.small_active() and pend[0].ptr.value == row.ptr.value
-                and ode._pending_ops is ops and os.environ.get("BEAT_BATCH_CARRY", "1") != "0"):
-            carry = int(pend[2])
-            ops.pending = None  # (the guess increment, if one is due, is known to the operator)
-        else:
-            ops.flush_pending()
-        self._last_carry = carry
-        if not same_dt:
-            pde._timestep.value = dt
-            pde._update_matrices()
-        theta_pde = pde.parameters["theta"]
+        ops.solve_finish()
+        take = (abs(dt - float(pde._timestep)) < 1.0e-12 and ops.pending is not None and not ops.small_active()
+                and ode._pending_ops is ops and os.environ.get("BEAT_BATCH_CARRY", "1") != "0")
+        # (a claim for no row flushes; the guess increment, if one is due, is known to the operator)
+        self._last_carry = carry = ops.deferred.claim(row if take else None)[3]
+        pde._set_timestep(dt)
         stims = [s for s in pde._stimuli if s.field is not None]
         rtol, atol, max_it = pde._solver_tolerances()
         hp, npar, _, _ = dev._param_args()
@@ -155,15 +140,7 @@ class MonodomainSplittingSolver:
                 ptr, nb = recorder._reserve(nb)
                 probe = (recorder._idx.ctypes.data_as(C.c_void_p), recorder._wts.ctypes.data_as(C.c_void_p), recorder.npts,
                          C.c_void_p(ptr))
-            chunk = steps[done : done + nb]
-            t_start = np.ascontiguousarray([a for a, _ in chunk], dtype=np.float64)
-            dts = np.ascontiguousarray([self.theta * (b - a) for a, b in chunk], dtype=np.float64)
-            amps = np.zeros((nb, max(1, len(stims))))
-            for k, (a, _) in enumerate(chunk):  # the stimulus expressions are evaluated at t0 + theta dt, as step() does
-                pde.time.value = a + theta_pde * (chunk[k][1] - a)
-                for j, s in enumerate(stims):
-                    amps[k, j] = s.amplitude()
-            infos = (_hip.KspInfo * nb)()
+            t_start, dts, amps, infos = self._batch_inputs(steps[done : done + nb], stims)
             rc = dev.ctx.lib.beat_split_steps(
                 dev.ctx.handle, dev.model.model_id, dev.states.ptr, dev.n, dev.states.ld, hp, npar, int(ode.v_index), ops.handle,
                 nb, t_start.ctypes.data_as(C.c_void_p), dts.ctypes.data_as(C.c_void_p), w_ptrs, amps.ctypes.data_as(C.c_void_p), len(stims),
@@ -176,21 +153,26 @@ class MonodomainSplittingSolver:
             pde.ksp = KspResult(last.iterations, last.residual_norm, last.converged_reason, last.rhs_norm)
             pde._check_converged()
             done += nb
-        ode._pending_ops = ops
-        for f in (pde.state, pde.v_, ode.v_ode):
-            f.alias_to(row, sync=ops.flush_pending)
-        ode._aliases = [pde.state, pde.v_, ode.v_ode]
+        ode._alias_v(ops, pde.state, pde.v_, ode.v_ode)
+
+    def _batch_inputs(self, chunk, stims):
+        """(start times, ionic step lengths, (steps, stimuli) amplitudes, KSP records to fill) of the steps ``chunk`` for the
+        library's loops; the stimulus expressions are evaluated at t0 + theta dt, as step() does."""
+        pde, theta_pde = self.pde, self.pde.parameters["theta"]
+        t_start = np.ascontiguousarray([a for a, _ in chunk], dtype=np.float64)
+        dts = np.ascontiguousarray([self.theta * (b - a) for a, b in chunk], dtype=np.float64)
+        amps = np.zeros((len(chunk), max(1, len(stims))))
+        for k, (a, b) in enumerate(chunk):
+            pde.time.value = a + theta_pde * (b - a)
+            for j, s in enumerate(stims):
+                amps[k, j] = s.amplitude()
+        return t_start, dts, amps, (_hip.KspInfo * len(chunk))()
 
     def _batched_steps_big(self, steps, stims, w_ptrs, hp, npar, tol, pending_in: int = 0) -> None:
         """The steps of a grid too big for the one-launch solve, run by the library's own loop (beat_split_steps_big): per step the
         ionic launch that applies what the previous solve deferred and the solve in place on the potential row -- what
         ``_fused_step`` does, without Python between the steps.  ``self.batch_ode_ms`` (a list, if the caller sets one) collects
         the duration of every ionic launch."""
-        import ctypes as C
-
-        from . import _hip
-        from ._engine import KspResult
-
         ode, pde = self.ode, self.pde
         ops, dev, row = pde._ops, ode._dev, ode._v_row
         theta_pde = pde.parameters["theta"]
@@ -201,34 +183,23 @@ class MonodomainSplittingSolver:
         done = 0
         # a call into the library cannot be interrupted: its length is kept near one second of steps (the first call makes 16 and
         # times them; 14 ms per step at 512^3, ten times that at 1024^3), and it returns early at a solve that ran out of iterations
-        import time as _time
-
         cap = min(16, _hip.MAX_BATCH)
         try:
             while done < len(steps):
                 nb = min(len(steps) - done, cap)
                 chunk = steps[done : done + nb]
-                t_start = np.ascontiguousarray([a for a, _ in chunk], dtype=np.float64)
-                dts = np.ascontiguousarray([self.theta * (b - a) for a, b in chunk], dtype=np.float64)
-                amps = np.zeros((nb, max(1, len(stims))))
-                for k, (a, b) in enumerate(chunk):  # the stimulus expressions are evaluated at t0 + theta dt, as step() does
-                    pde.time.value = a + theta_pde * (b - a)
-                    for j, s in enumerate(stims):
-                        amps[k, j] = s.amplitude()
-                infos = (_hip.KspInfo * nb)()
+                t_start, dts, amps, infos = self._batch_inputs(chunk, stims)
                 pend = (C.c_int * 3)()
                 ode_ms = (C.c_float * nb)() if times is not None else None
-                ops.st_ptr_for_flush = None
-                tic = _time.perf_counter()
+                tic = time.perf_counter()
                 rc = dev.ctx.lib.beat_split_steps_big(
                     dev.ctx.handle, dev.model.model_id, dev.states.ptr, dev.n, dev.states.ld, hp, npar, int(ode.v_index), ops.handle,
                     C.c_void_p(ops.work.data_ptr()), nb, t_start.ctypes.data_as(C.c_void_p), dts.ctypes.data_as(C.c_void_p), w_ptrs,
                     amps.ctypes.data_as(C.c_void_p), len(stims), rtol, atol, max_it, pending_in, infos, pend, ode_ms)
                 ran = int(pend[2])  # steps done: all of them, or up to and including a solve that did not converge
-                per_step = (_time.perf_counter() - tic) / max(1, ran)
+                per_step = (time.perf_counter() - tic) / max(1, ran)
                 cap = int(min(_hip.MAX_BATCH, max(1, 1.0 / max(per_step, 1e-6))))
-                pending_in = int(pend[1])
-                ops.pending = (row, int(pend[0]), int(pend[1])) if (pend[1] > 0 or dev.ctx.lib.beat_pde_guess_pending(ops.handle)) else None
+                ops.deferred.leave(row, pend[0], pend[1])
                 if times is not None:
                     times.extend(float(v) for v in ode_ms[:ran])
                 if ran > 0:
@@ -243,17 +214,12 @@ class MonodomainSplittingSolver:
                 if ran == 0:
                     raise _hip.BeatHipError("beat_split_steps_big made no progress")
                 if done < len(steps):
-                    ops.pending = None  # the next batch's first ionic launch applies it (pending_in)
+                    pending_in = ops.deferred.claim(row)[3]  # the next batch's first ionic launch applies it
         finally:  # (also when ksp_error_if_not_converged raised: the row, its aliases and what is pending stay consistent)
-            ode._pending_ops = ops
-            for f in (pde.state, pde.v_, ode.v_ode):
-                f.alias_to(row, sync=ops.flush_pending)
-            ode._aliases = [pde.state, pde.v_, ode.v_ode]
+            ode._alias_v(ops, pde.state, pde.v_, ode.v_ode)
 
     # ---------------------------------------------------------------------------------------
     def _can_fuse(self) -> bool:
-        from .odesolver import DolfinMultiODESolver, DolfinODESolver
-
         ode, pde = self.ode, self.pde
         if isinstance(ode, DolfinMultiODESolver):
             # markers that share one device model live in one state array advanced by one launch: the single-model route
@@ -289,42 +255,18 @@ class MonodomainSplittingSolver:
                 # a deferred x += sum alpha_j p_j of the previous solve is applied by this kernel
                 ode._dev.step(t0, self.theta * dt, v_index=v_index, pending_ops=ode._pending_ops, v_row=row)
             with mon.track_time("pde_step"):
-                theta_pde = pde.parameters["theta"]
-                with pde.monitor.track_time("pde_total_step"):
-                    pde.time.value = t0 + theta_pde * dt
-                    if not abs(dt - float(pde._timestep)) < 1.0e-12:
-                        pde._timestep.value = dt
-                        with pde.monitor.track_time("pde_update_matrices"):
-                            pde._update_matrices()
-                    stim_w, stim_amp = [], []
-                    for s in pde._stimuli:
-                        a = s.amplitude()
-                        if a != 0.0 and s.field is not None:
-                            stim_w.append(s.field)
-                            stim_amp.append(a)
-                    # (with nobody asking for the KSP record step by step the solve is left open: the next step's ionic launch
-                    # goes into the queue behind it before the host waits, and the device never idles in between)
-                    lazy = pde.can_solve_lazily()
-                    with pde.monitor.track_time("pde_linear_solve"):
-                        pde.solve_in_place(row, stim_w, stim_amp, defer_flush=True, lazy=lazy)
-                    ode._pending_ops = pde._ops
-                    if not lazy:
-                        pde.monitor.record_ksp(pde.ksp)
-                pde.monitor.advance_step(t0, t1)
+                pde.step_in_place(row, t0, t1, deferred=True)
+                ode._pending_ops = pde._ops  # (a first step's corrective launch below needs it before _alias_v sets it)
             if not np.isclose(self.theta, 1.0):
                 # corrective ionic step of length (1 - theta) dt from t0 + theta dt (monodomain_solver.py:98-113)
                 with mon.track_time("corrective_ode_step"):
                     ode._dev.step(t0 + self.theta * dt, (1.0 - self.theta) * dt, v_index=v_index,
                                   pending_ops=ode._pending_ops, v_row=row)
             with mon.track_time("pde_assign_previous_after"):
-                for f in (pde.state, pde.v_, ode.v_ode):
-                    f.alias_to(row, sync=pde._ops.flush_pending)
-                ode._aliases = [pde.state, pde.v_, ode.v_ode]
+                ode._alias_v(pde._ops, pde.state, pde.v_, ode.v_ode)
         mon.advance_step(t0, t1)
 
     def _can_fuse_multi(self) -> bool:
-        from .odesolver import DolfinMultiODESolver
-
         ode, pde = self.ode, self.pde
         return (
             self.fused
@@ -349,23 +291,7 @@ class MonodomainSplittingSolver:
             with mon.track_time("ode_to_dolfin"):
                 ode.scatter_v(x)
             with mon.track_time("pde_step"):
-                theta_pde = pde.parameters["theta"]
-                with pde.monitor.track_time("pde_total_step"):
-                    pde.time.value = t0 + theta_pde * dt
-                    if not abs(dt - float(pde._timestep)) < 1.0e-12:
-                        pde._timestep.value = dt
-                        with pde.monitor.track_time("pde_update_matrices"):
-                            pde._update_matrices()
-                    stim_w, stim_amp = [], []
-                    for s in pde._stimuli:
-                        a = s.amplitude()
-                        if a != 0.0 and s.field is not None:
-                            stim_w.append(s.field)
-                            stim_amp.append(a)
-                    with pde.monitor.track_time("pde_linear_solve"):
-                        pde.solve_in_place(x, stim_w, stim_amp)
-                    pde.monitor.record_ksp(pde.ksp)
-                pde.monitor.advance_step(t0, t1)
+                pde.step_in_place(x, t0, t1)
             with mon.track_time("ode_from_dolfin"):
                 ode.gather_v(x)
             if not np.isclose(self.theta, 1.0):

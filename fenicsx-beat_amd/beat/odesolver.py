@@ -285,28 +285,13 @@ class _DeviceODE:
             # go back to the per-node kernel, which mirrors any row (what the reference's v_index means, odesolver.py:135-146)
             use_classes = False
             hp, npar, ppn, pld = self._per_node_args
-        pend = None
-        behind = False  # enqueue this launch BEHIND a solve that is still open (pending = -1: beat_ode_step_pending)
         model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
-        if pending_ops is not None and getattr(pending_ops, "open_x", None) is not None:
-            long_ring = len(pending_ops.ring) > 6  # (only the class kernel takes more than six pending directions)
-            if (v_row is not None and int(v_index) == model_v and pending_ops.open_x.ptr.value == v_row.ptr.value
-                    and (self.node_map is None or self.node_map[1].ptr.value == v_row.ptr.value)
-                    and (use_classes or not long_ring)):
-                behind = True
-                pend = (v_row, 0, -1)
-            else:
-                pending_ops.solve_finish()
-        if not behind and pending_ops is not None and pending_ops.pending is not None:
-            if (v_row is not None and int(v_index) == model_v
-                    and pending_ops.pending[0].ptr.value == v_row.ptr.value
-                    and (self.node_map is None or self.node_map[1].ptr.value == v_row.ptr.value)):
-                pend = pending_ops.pending
-                pending_ops.pending = None
-            else:
-                pending_ops.flush_pending()
-        # (operator, ring, field stride, count) of what the launch applies, as the pending-update entry points take them
-        pend_args = (None, None, 0, 0) if pend is None else (pending_ops.handle, pending_ops.ring[0].ptr, pending_ops.fld, int(pend[2]))
+        # (operator, ring, field stride, count) of what the launch applies, as the pending-update entry points take them; count -1:
+        # the launch is enqueued BEHIND a solve that is still open (beat_ode_step_pending)
+        pend_args = (None, None, 0, 0) if pending_ops is None else pending_ops.deferred.claim(
+            v_row, int(v_index) == model_v, None if self.node_map is None else self.node_map[1], use_classes)
+        pend = None if pend_args[0] is None else pend_args
+        behind = pend_args[3] < 0
         with self.monitor.track_time("ode_total_step"):
             with self.monitor.track_time("ode_function_call"):
                 if use_classes:
@@ -337,7 +322,7 @@ class _DeviceODE:
                                                    None if v_copy is None else v_copy.ptr)
                     )
             if behind:  # the call has finished the solve it was enqueued behind: take its record
-                pending_ops.finished_behind()
+                pending_ops.deferred.finished_behind()
             with self.monitor.track_time("ode_state_update"):
                 pass  # updated in place by the kernel
 
@@ -346,6 +331,30 @@ class BaseDolfinODESolver(abc.ABC):
     v_ode: grid.Function
     v_pde: grid.Function
     _metadata: dict[str, Any] | None = None
+    _pending_ops = None  # diffusion operators that may hold a deferred update of the V row (fused step)
+    _aliases: tuple = ()  # functions that alias the V row (see grid.Function)
+
+    def _sync_v(self):
+        """Bring the V row up to date if the last fused diffusion solve left its final update to the next ionic
+        kernel (deferred-x PCG): everything that reads or overwrites the row outside that kernel calls this."""
+        if self._pending_ops is not None:
+            self._pending_ops.flush_pending()
+
+    def _release_aliases(self):
+        """The V row is about to change outside the fused step: give every function that merely
+        aliases it its own copy of the current values first."""
+        self._sync_v()
+        for f in self._aliases:
+            if f._alias is self._v_row:
+                f.materialize()
+        self._aliases = ()
+
+    def _alias_v(self, ops, *functions) -> None:
+        """``functions`` (the potential's: pde.state, pde.v_, v_ode) become aliases of the V row, which ``ops`` completes."""
+        self._pending_ops = ops
+        for f in functions:
+            f.alias_to(self._v_row, sync=ops.deferred)
+        self._aliases = functions
 
     def _initialize_metadata(self):
         if self.v_ode.ufl_element().family_name == "Quadrature":
@@ -387,8 +396,6 @@ class DolfinODESolver(BaseDolfinODESolver):
     monitor: BaseMonitor = field(default_factory=NullMonitor)
 
     def __post_init__(self):
-        self._aliases: list[grid.Function] = []
-        self._pending_ops = None  # diffusion operators that may hold a deferred update of the V row (fused step)
         self.on_device = isinstance(self.fun, DeviceModel)
         values = _initial_values(self.init_states, self.shape, self.on_device)
         if self.on_device:
@@ -405,22 +412,6 @@ class DolfinODESolver(BaseDolfinODESolver):
                                         missing_variables=self.missing_variables, monitor=self.monitor)
         self._initialize_metadata()
         self.monitor = _CallableMonitor(self.monitor, self.monitor_values)
-
-    # ---- alias bookkeeping (see grid.Function) ------------------------------------------------
-    def _sync_v(self):
-        """Bring the V row up to date if the last fused diffusion solve left its final update to the next ionic
-        kernel (deferred-x PCG): everything that reads or overwrites the row outside that kernel calls this."""
-        if self._pending_ops is not None:
-            self._pending_ops.flush_pending()
-
-    def _release_aliases(self):
-        """The V row is about to change outside the fused step: give every function that merely
-        aliases it its own copy of the current values first."""
-        self._sync_v()
-        for f in self._aliases:
-            if f._alias is self._v_row:
-                f.materialize()
-        self._aliases = []
 
     # ---- reference interface --------------------------------------------------------------------
     def to_dolfin(self) -> None:
@@ -569,8 +560,6 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
                 if hasattr(f, "register"):
                     f.register()
         self._initialize_full_values()
-        self._aliases: list[grid.Function] = []
-        self._pending_ops = None
         telemetry = self.monitor  # (the per-marker solvers below take the telemetry monitor itself)
         self.monitor = _CallableMonitor(telemetry, self.monitor_values)
         self._marked = self.on_device and self._one_launch_possible()
@@ -709,22 +698,11 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         self._dev.set_classes(self._cls_dev, [self.parameters[m] for m in ms])
         self._odes = {}
 
-    def _sync_v(self):
-        if self._pending_ops is not None:
-            self._pending_ops.flush_pending()
-
     def _refresh_compact_v(self) -> None:
         """Compact layout: the potential row of the state array mirrors the field only as of the last ionic launch."""
         if self._marked and self._node_idx is not None:
             self._sync_v()
             self._dev.states.rows[self._vi].index_copy_(0, self._real_pos, self._v_row.data.index_select(0, self._real_nodes))
-
-    def _release_aliases(self):
-        self._sync_v()
-        for f in self._aliases:
-            if f._alias is self._v_row:
-                f.materialize()
-        self._aliases = []
 
     def _fused_prepare(self) -> int:
         """Called by the fused split step before the ionic launch: refresh the class table if a parameter set was

@@ -792,11 +792,101 @@ def test_deferred_potential_update_is_bit_identical():
             # every step) are not reads of the potential and must not cost a flush pass
             assert s.pde.state.x.array.size == s.ode.num_points == len(s.pde.v_.x.array)
             assert s.pde.state.x.array.shape == (s.ode.num_points,)
-            assert getattr(ops, "flushes", 0) == 0 and (ops.pending is not None or ops.open_x is not None)
+            assert ops.flushes == 0 and (ops.pending is not None or ops.open_x is not None)
         runs[peek] = s.ode.values.copy()
         assert ops.pending is None
         np.testing.assert_array_equal(np.asarray(s.pde.v_.x.array), runs[peek][17])
     np.testing.assert_array_equal(runs[False], runs[True])
+
+
+@pytest.mark.parametrize("lazy", ["open", "pending"])
+@pytest.mark.parametrize("why", ["another field", "not the model's potential row", "a node map into another field"])
+def test_an_update_the_ionic_launch_may_not_claim_is_flushed_bit_identically(why, lazy, monkeypatch):
+    """The three ways the claim of a deferred update (beat._deferred.DeferredUpdate.claim) can fail, each behind a solve that is
+    still open and with the update pending (BEAT_LAZY_KSP=0): the ionic launch must leave the update alone -- the open solve is
+    finished, the update applied in a pass of its own -- and 4 steps on a 17 x 9 x 7 box end on the bits of the same run with
+    the update flushed after every solve.  "another field": two splitting solvers on ONE diffusion model take turns, so each
+    finds the other's solve; "not the model's potential row": the PDE is coupled to another row of the states than TP06's V;
+    "a node map into another field": a compact state array whose potential is at home in a field of its own.
+
+    Why these: counted over the whole GPU suite, the claim met only an idle owner, a matching open solve (ring of six; ring of
+    twelve with and without the class kernel) and a matching pending update -- no test reached a refusal for any of the three
+    reasons, in either state.  No public route refuses today: the fused step always solves on the launch's own row.  So each case
+    builds the nearest configuration that does.  Two solvers on one model meet each other's solve from the third step on (the
+    second solver's first step has no operator yet and its solve flushes through the start of a solve); the node map is pointed at
+    a field made here, through the private ``_dev.node_map``, which no public route does.  What they hold: a launch that took an
+    update it must refuse would add one row's directions to another row or home, and the bits would differ from the flushed run;
+    ``flushes`` tells a refused claim (a pass of its own) from a taken one (none)."""
+    import beat
+    from beat import grid as g
+    from beat._engine import HipOps
+    from beat.models import tp06
+
+    monkeypatch.setattr(HipOps, "default_small", False)  # (1071 nodes: the one-launch solve would leave nothing to defer)
+    monkeypatch.setenv("BEAT_LAZY_KSP", "1" if lazy == "open" else "0")
+    monkeypatch.setenv("BEAT_MULTI_COMPACT", "1")
+    row_v = tp06.state_index("V")
+
+    def run(flush):
+        mesh = g.create_box(g.COMM_WORLD, [np.zeros(3), np.array([4.0, 2.0, 1.5])], [16, 8, 6])
+        time = g.Constant(mesh, 0.0)
+        cells = g.locate_entities(mesh, 3, lambda x: x[0] <= 1.0 + 1e-10)
+        tags = g.meshtags(mesh, 3, cells, np.full(len(cells), 1, dtype=np.int32))
+        chi = beat.conductivities.default_conductivities("Niederer")["chi"]
+        I_s = beat.stimulation.define_stimulus(mesh=mesh, chi=chi, time=time, subdomain_data=tags, marker=1, mesh_unit="mm",
+                                               amplitude=50_000.0, duration=1.0)
+        pde = beat.MonodomainModel(time=time, mesh=mesh, M=np.diag([9.5e-4, 1.3e-4, 1.3e-4]), I_s=I_s, C_m=0.01, dx=I_s.dZ)
+        V = g.functionspace(mesh, ("P", 1))
+        assert pde.state.x.array.size == 17 * 9 * 7 and not pde._ops.small_active()
+
+        def single(v_index):
+            ode = beat.odesolver.DolfinODESolver(
+                v_ode=g.Function(V), v_pde=pde.state, fun=tp06.generalized_rush_larsen, init_states=tp06.init_state_values(),
+                parameters=tp06.init_parameter_values(stim_amplitude=0.0), num_states=19, v_index=v_index)
+            return beat.MonodomainSplittingSolver(pde=pde, ode=ode)
+
+        if why == "another field":
+            solvers = [single(row_v), single(row_v)]
+        elif why == "not the model's potential row":
+            solvers = [single((row_v + 1) % 19)]
+        else:
+            markers = g.Function(V)
+            markers.x.array[:] = np.where(mesh.node_coordinates(pad3=True)[:, 0] < 2.0, 0.0, 1.0)
+            v_ode = g.Function(V)
+            v_ode.x.array[:] = -80.0
+            ode = beat.odesolver.DolfinMultiODESolver(
+                v_ode=v_ode, v_pde=pde.state, markers=markers, num_states={0: 19, 1: 19}, v_index={0: row_v, 1: row_v},
+                fun={k: tp06.generalized_rush_larsen for k in (0, 1)}, init_states={k: tp06.init_state_values() for k in (0, 1)},
+                parameters={0: tp06.init_parameter_values(stim_amplitude=0.0), 1: tp06.init_parameter_values(stim_amplitude=0.0, g_Ks=0.098)})
+            assert ode._marked and ode._node_idx is not None
+            home = pde._ctx.field(ode._v_row.n, mesh.plane)  # the potential the cells see lives here ...
+            home.copy_from(ode._v_row)
+            ode._dev.node_map = (ode._dev.node_map[0], home)  # ... while the diffusion solve works on ode._v_row
+            solvers = [beat.MonodomainSplittingSolver(pde=pde, ode=ode)]
+        assert all(s._can_fuse() for s in solvers)
+        ops, left = pde._ops, 0
+        for i in range(4):
+            solvers[i % len(solvers)].step((i * 0.05, (i + 1) * 0.05))
+            left += int(ops.open_x is not None if lazy == "open" else ops.pending is not None)
+            if flush:
+                ops.flush_pending()
+        # the steps left their solves open / updates pending (a solve that ends on a full ring cycle with no guess increment due
+        # leaves nothing): the state the claims under test meet
+        assert left == 4 if lazy == "open" else left >= 2
+        if not flush:  # ... and no launch took one: passes of their own applied them (the last step's may still be owed)
+            assert 1 <= ops.flushes <= 3
+        out = [np.asarray(pde.state.x.array).copy()]
+        for s in solvers:
+            ode = s.ode
+            out.append(np.asarray(ode._v_row.numpy()).copy())
+            out.append(np.asarray(ode._dev.states.numpy()).copy())
+        assert ops.pending is None and ops.open_x is None
+        return out
+
+    a, b = run(False), run(True)
+    assert np.abs(a[0] - a[0][0]).max() > 0.0  # (the stimulus acts: the potential is no constant)
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
 
 
 @pytest.mark.parametrize("theta", [1.0, 0.5])
@@ -848,7 +938,7 @@ def test_fused_multi_celltype_step_equals_reference_sequence(theta, monkeypatch)
                 params[1][tp06.parameter_index("g_Kr")] *= 0.5
             solver.step((i * 0.05, (i + 1) * 0.05))
         if one_launch and fused:
-            assert getattr(pde._ops, "flushes", 0) == 0  # no separate pass ever applied the potential's update
+            assert pde._ops.flushes == 0  # no separate pass ever applied the potential's update
         v = np.asarray(pde.state.x.array).copy()
         np.testing.assert_array_equal(v, np.asarray(pde.v_.x.array))
         np.testing.assert_array_equal(v, np.asarray(ode.v_ode.x.array))
