@@ -838,7 +838,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = halo_wait(comm))) return rc;
       if ((rc = beat_rr_udot_part(pde, st, r_cur, 1))) return rc;
       if ((rc = allreduce_sum(comm, st + PQ, 3))) return rc;
-      if ((rc = beat_rr_merged_next(pde, st, slot))) return rc;
+      if ((rc = beat_pcg_launch_step(pde, ScalarStep::with_slot(STEP_MERGED, st, pde->d_alphas + slot)))) return rc;
       if ((rc = beat_rr_prupd(pde, st, r_cur, p_old, p_cur, r_new))) return rc;
       if ((rc = halo_start(comm, r_new, n, plane))) return rc;
       if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
@@ -855,7 +855,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = halo_start(comm, r_new, n, plane))) return rc;  // travels behind the reductions and the next part 0
       if ((rc = allreduce_sum(comm, st + RZN, 2))) return rc;
       if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
-      if ((rc = beat_rr_next(pde, st))) return rc;
+      if ((rc = beat_pcg_launch_step(pde, ScalarStep::roll(st)))) return rc;
       continue;
     }
     if (vpdot) {
@@ -870,7 +870,7 @@ int beat_dist_enqueue_iterations(beat_pde* pde, int count) {
       if ((rc = halo_start(comm, r, n, plane))) return rc;
       if ((rc = allreduce_sum(comm, st + RZN, 2))) return rc;
       if ((rc = beat_flush_if_ring_full(pde, i))) return rc;
-      if ((rc = beat_rr_next(pde, st))) return rc;  // the scalar roll (beta, iteration count, latch)
+      if ((rc = beat_pcg_launch_step(pde, ScalarStep::roll(st)))) return rc;  // the scalar roll (beta, iteration count, latch)
       continue;
     }
     if ((rc = halo_start(comm, p_cur, n, plane))) return rc;                  // ghost planes of p travel ...

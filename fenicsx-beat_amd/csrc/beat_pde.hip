@@ -17,10 +17,11 @@
 // (ds_read_b64, conflict-free: lanes read consecutive doubles); a thread computes 4 rows, unrolled by 2, so the
 // compiler shares the in-plane reads.  Algorithmic HBM traffic: 8 B read + 8 B written per node per operator
 // application; the tile halo and the chunk's two extra planes are re-reads that the XCD-local L2 mostly absorbs
-// (measured: reads 1.09x algorithmic; tiles are dealt to XCDs in contiguous runs, see tile_of_block()).
+// (measured: reads 1.09x algorithmic; tiles are dealt to XCDs in contiguous runs, see xcd_block()).
 // PMC picture of the SpMV at 512^3 (0.56 ms): LDS-limited to 4 workgroups per CU (37 KB each), no bank
 // conflicts, LDS pipe 37 % busy, waves parked on s_waitcnt / barriers 64 % of their lifetime -- latency bound.
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -83,20 +84,6 @@ struct StencilArgs {
 // PC: one Horner pass of the polynomial preconditioner z = sum_j c_j (D^-1 A)^j D^-1 r:
 //     out = c_r D^-1 r + D^-1 A in,   in = c_in D^-1 r on the first pass, the previous output afterwards;
 //     the last pass also reduces r.z.
-
-__device__ __forceinline__ int axis_type(int i, int n, int lo_phys, int hi_phys) {
-  if (n == 1 && lo_phys && hi_phys) return 1;  // collapsed axis: no coupling along it
-  if (i == 0 && lo_phys) return 0;
-  if (i == n - 1 && hi_phys) return 2;
-  return 1;
-}
-
-// Blocks are dealt round-robin to the 8 XCDs; give each XCD a contiguous run of tiles so that
-// tiles sharing a halo share an L2.  Pure performance heuristic (placement is not relied upon).
-__device__ __forceinline__ int tile_of_block(int b, int total) {
-  const int per = (total + 7) >> 3;
-  return (b & 7) * per + (b >> 3);
-}
 
 // Per-thread staging descriptors, computed once per tile: which elements of the (TY+2)x(TX+2)
 // staged plane this thread moves, their offset inside an xy-plane (-1: outside the box or idle),
@@ -252,7 +239,7 @@ __global__ __launch_bounds__(BEAT_BLOCK) void stencil_kernel(Geom g, StencilArgs
   if (MODE == MODE_SPMV_DOT || MODE == MODE_PC) {
     if (a.st[STOP] != 0.0) return;  // convergence latch: nothing left to do in this solve
   }
-  const int t = tile_of_block(blockIdx.x, g.total);
+  const int t = xcd_block(blockIdx.x, g.total);
   if (t >= g.total) return;
   const int tile_x = t % g.tiles_x;
   const int tile_y = (t / g.tiles_x) % g.tiles_y;
@@ -308,69 +295,9 @@ __global__ __launch_bounds__(BEAT_BLOCK) void stencil_kernel(Geom g, StencilArgs
   }
 }
 
-// The scalar steps of the PCG (each also a kernel of its own below; the reduction runs them behind its sums, see reduce_partials_kernel)
-__device__ __forceinline__ void beat_pcg_roll(double* st) {
-  st[BETA] = st[RZN] / st[RZ];
-  st[RZ] = st[RZN];
-  st[RR] = st[RRN];
-  st[ITERS] += 1.0;
-  const double tr = st[RTOL] * st[RTOL] * st[BB];
-  if (st[RR] <= st[TOL2]) {
-    st[STOP] = 1.0;
-    st[REASON] = st[RR] <= tr ? 2.0 : 3.0;
-  } else if (st[ITERS] >= st[MAXIT]) {
-    st[STOP] = 1.0;
-    st[REASON] = -3.0;
-  }
-}
-__device__ __forceinline__ void beat_pcg_begin(double* st, double rtol, double atol, double max_it) {
-  const double bb = st[BB], rr = st[RR];
-  const double tr = rtol * rtol * bb, ta = atol * atol;
-  const double tol2 = tr > ta ? tr : ta;
-  st[TOL2] = tol2;
-  st[ITERS] = 0.0;
-  st[NUPD] = 0.0;
-  st[RTOL] = rtol;
-  st[ATOL] = atol;
-  st[MAXIT] = max_it;
-  st[BETA] = 0.0;
-  st[RR0] = rr;
-  const bool done = rr <= tol2;
-  st[STOP] = done ? 1.0 : 0.0;
-  st[REASON] = done ? (rr <= tr ? 2.0 : 3.0) : 0.0;
-}
-// The predicted stop behind PDOT (beat_rr_pdot with a ring slot), with st[PQS..QQ] = p.q, r.q, q.q just summed (q = A p_i, r = r_i):
-//   r_{i+1} . r_{i+1} = RR - 2 alpha (r.q) + alpha^2 (q.q)   in exact arithmetic, alpha = RZ / PQ.
-// The prediction rho feeds no iterate: it only gates the stop.  E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds |rho - what the residual
-// update's reduction would compute| (c: beat_rr_predict_bound).  When rho + E settles the stopping test and its reason (and rho is
-// accurate enough for the recorded residual norm) the solve is latched exactly as the update, its count and the roll would have left
-// it -- same alpha bits in the ring slot, same ITERS, NUPD, STOP, REASON, RR = max(rho, 0) -- and the update's launches are the no-ops
-// latched launches are.  Otherwise nothing changes but PQ: the update and the roll run and decide, max_it included.
-__device__ __forceinline__ void beat_pcg_predict(double* st, double* alpha_slot, double c) {
-  st[PQ] = st[PQS];
-  const double alpha = st[RZ] / st[PQ];  // (the residual update's expression)
-  const double rr = st[RR], rq = st[RQ], qq = st[QQ];
-  const double rho = fma(alpha, fma(alpha, qq, -2.0 * rq), rr);
-  const double m = sqrt(rr) + fabs(alpha) * sqrt(qq);
-  const double e = c * m * m;
-  const double tr = st[RTOL] * st[RTOL] * st[BB];
-  // (a recorded norm within ~1e-6 of the explicit one: E <= 2^-20 rho; the comparisons are false for a NaN anywhere)
-  if (!(rho + e <= st[TOL2]) || !(e <= 0x1p-20 * rho)) return;
-  double reason;
-  if (rho + e <= tr) reason = 2.0;
-  else if (rho - e > tr) reason = 3.0;
-  else return;
-  *alpha_slot = alpha;
-  st[RR] = rho > 0.0 ? rho : 0.0;
-  st[ITERS] += 1.0;
-  st[NUPD] += 1.0;
-  st[REASON] = reason;
-  st[STOP] = 1.0;
-}
 // Sum `count` block partials of `nsum` quantities in a fixed order and store them at out[0..nsum); then, in the same launch (round 5:
-// one launch instead of two; the same arithmetic in the same order as the kernels it replaces), the scalar step `then` (ScalarStep::Kind)
-// on the state `roll_st` the sums were just written into: 0 = none, 1 = the iteration's roll (pcg_next_kernel: beta, iteration count,
-// latch), 2 = the start of a solve (pcg_begin_kernel) with rtol / atol / max_it, 3 = the predicted stop (pcg_predict_kernel).
+// one launch instead of two; the same arithmetic in the same order as the kernels it replaces), the scalar step `then` (a PcgStep of
+// beat_pcg_scalar.h, run by beat_pcg_step) on the state `roll_st` the sums were just written into.
 __global__ __launch_bounds__(BEAT_BLOCK) void reduce_partials_kernel(const double* __restrict__ partials, int count, int nsum, double* out,
                                                                      const double* st, double* counter, int then, double* roll_st,
                                                                      double rtol, double atol, double max_it, double* alpha_slot,
@@ -384,23 +311,13 @@ __global__ __launch_bounds__(BEAT_BLOCK) void reduce_partials_kernel(const doubl
     s = beat_block_sum(s, red);
     if (threadIdx.x == 0) out[k] = s;
   }
-  if (then != 0 && threadIdx.x == 0) {  // (the thread that wrote the sums: its own stores are ahead of these loads)
-    if (then == 1) beat_pcg_roll(roll_st);
-    else if (then == 3) beat_pcg_predict(roll_st, alpha_slot, bound_c);
-    else beat_pcg_begin(roll_st, rtol, atol, max_it);
-  }
+  // (the thread that wrote the sums: its own stores are ahead of these loads)
+  if (then != STEP_NONE && threadIdx.x == 0) beat_pcg_step(then, roll_st, rtol, atol, max_it, alpha_slot, bound_c);
 }
 
-__global__ void pcg_predict_kernel(double* st, double* alpha_slot, double c) {
-  if (st[STOP] != 0.0) return;
-  beat_pcg_predict(st, alpha_slot, c);
-}
-
-__global__ void pcg_begin_kernel(double* st, double rtol, double atol, double max_it) { beat_pcg_begin(st, rtol, atol, max_it); }
-
-__global__ void pcg_next_kernel(double* st) {
-  if (st[STOP] != 0.0) return;
-  beat_pcg_roll(st);
+// one scalar step in a launch of its own (beat_pcg_launch_step)
+__global__ void pcg_step_kernel(int kind, double* st, double rtol, double atol, double max_it, double* alpha_slot, double bound_c) {
+  beat_pcg_step(kind, st, rtol, atol, max_it, alpha_slot, bound_c);
 }
 
 // x += alpha p ; r -= alpha q ; partial sums of r.z (z = D^-1 r) and r.r.  Row-per-wave so the node
@@ -804,14 +721,16 @@ int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, cons
   }();
   hipStream_t s = pde->ctx->stream;
   BEAT_KERNEL(reduce_partials_kernel, dim3(1), dim3(BEAT_BLOCK), 0, s, (const double*)pde->ctx->d_partials, count, nsum, out, st, step.counter,
-              fuse ? (int)step.kind : 0, step.st, step.rtol, step.atol, (double)step.max_it, step.alpha_slot, step.bound_c);
+              fuse ? (int)step.kind : (int)STEP_NONE, step.st, step.rtol, step.atol, (double)step.max_it, step.alpha_slot, step.bound_c);
   BEAT_LAUNCH_CHECK();
-  if (step.kind != ScalarStep::NONE && !fuse) {
-    if (step.kind == ScalarStep::ROLL) BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, s, step.st);
-    else if (step.kind == ScalarStep::PREDICT) BEAT_KERNEL(pcg_predict_kernel, dim3(1), dim3(1), 0, s, step.st, step.alpha_slot, step.bound_c);
-    else BEAT_KERNEL(pcg_begin_kernel, dim3(1), dim3(1), 0, s, step.st, step.rtol, step.atol, (double)step.max_it);
-    BEAT_LAUNCH_CHECK();
-  }
+  return fuse ? BEAT_OK : beat_pcg_launch_step(pde, step);
+}
+
+int beat_pcg_launch_step(beat_pde* pde, const ScalarStep& step) {
+  if (step.kind == STEP_NONE) return BEAT_OK;
+  BEAT_KERNEL(pcg_step_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, (int)step.kind, step.st, step.rtol, step.atol, (double)step.max_it,
+              step.alpha_slot, step.bound_c);
+  BEAT_LAUNCH_CHECK();
   return BEAT_OK;
 }
 
@@ -859,10 +778,8 @@ extern "C" int beat_pde_rhs(beat_pde* pde, const double* dev_v_prev, const doubl
 
 extern "C" int beat_pde_cg_begin(beat_pde* pde, double* dev_st, double rtol, double atol, int max_it) {
   BEAT_REQUIRE(pde != nullptr && dev_st, "null argument");
-  BEAT_KERNEL(pcg_begin_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st, rtol, atol,
-                     (double)max_it);
-  BEAT_LAUNCH_CHECK();
-  return BEAT_OK;
+  const PcgStart start{rtol, atol, max_it};
+  return beat_pcg_launch_step(pde, ScalarStep::begin(dev_st, &start));
 }
 
 extern "C" int beat_pde_spmv_dot(beat_pde* pde, const double* dev_p, double* dev_q, double* dev_st) {
@@ -948,8 +865,7 @@ extern "C" int beat_pde_pc_pass(beat_pde* pde, int j, const double* dev_r, doubl
 // p = z + beta p after the scalar roll (polynomial-preconditioned variant of beat_pde_cg_next)
 extern "C" int beat_pde_cg_next_z(beat_pde* pde, double* dev_st, const double* dev_z, double* dev_p) {
   BEAT_REQUIRE(pde != nullptr && dev_st && dev_z && dev_p, "null argument");
-  BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st);
-  BEAT_LAUNCH_CHECK();
+  if (int rc = beat_pcg_launch_step(pde, ScalarStep::roll(dev_st))) return rc;
   const unsigned grid = (unsigned)std::min<int64_t>(2048, (pde->n + BEAT_BLOCK - 1) / BEAT_BLOCK);
   BEAT_KERNEL(cg_pupdate_z_kernel, dim3(grid), dim3(BEAT_BLOCK), 0, pde->ctx->stream, pde->n,
                      (const double*)dev_st, dev_z, dev_p);
@@ -969,8 +885,7 @@ extern "C" int beat_pde_cg_first_z(beat_pde* pde, double* dev_st, const double* 
 
 extern "C" int beat_pde_cg_next(beat_pde* pde, double* dev_st, const double* dev_r, double* dev_p) {
   BEAT_REQUIRE(pde != nullptr && dev_st && dev_r && dev_p, "null argument");
-  BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st);
-  BEAT_LAUNCH_CHECK();
+  if (int rc = beat_pcg_launch_step(pde, ScalarStep::roll(dev_st))) return rc;
   BEAT_LAUNCH_VEC(pde, cg_pupdate_kernel, dim3(pde->vec_grid), dim3(BEAT_BLOCK), 0, pde->ctx->stream, pde->g,
                      (const double*)dev_st, dev_r, dev_p, pde->dinv_arg(), pde->h_dinv[13]);
   BEAT_LAUNCH_CHECK();
@@ -1018,8 +933,7 @@ extern "C" int beat_pde_cg_next_oop(beat_pde* pde, double* dev_st, const double*
                                     double* dev_p_next) {
   BEAT_REQUIRE(pde != nullptr && dev_st && dev_r && dev_p_cur && dev_p_next, "null argument");
   BEAT_REQUIRE(dev_p_cur != dev_p_next, "the p-update is out of place");
-  BEAT_KERNEL(pcg_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st);
-  BEAT_LAUNCH_CHECK();
+  if (int rc = beat_pcg_launch_step(pde, ScalarStep::roll(dev_st))) return rc;
   if (pde->var) return beat_var_pupdate_oop(pde, dev_st, dev_r, dev_p_cur, dev_p_next);
   BEAT_LAUNCH_VEC(pde, cg_pupdate_oop_kernel, dim3(pde->vec_grid), dim3(BEAT_BLOCK), 0, pde->ctx->stream, pde->g,
                      (const double*)dev_st, dev_r, dev_p_cur, dev_p_next, pde->dinv_arg(), pde->h_dinv[13]);

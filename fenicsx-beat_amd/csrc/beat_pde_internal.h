@@ -3,6 +3,7 @@
 //   beat_pde_var.hip  per-node-coefficient operators, device-side row assembly, Dirichlet elimination
 #pragma once
 #include "beat_common.h"
+#include "beat_pcg_scalar.h"
 #include "beat_slab_parts.h"
 
 #include <algorithm>
@@ -11,12 +12,7 @@
 
 namespace beat_pde_detail {
 
-// slots of the PCG scalar state `st` (device, caller-owned, >= 16 doubles)
-enum St { BB = 0, RZ, RR, PQ, RZN, RRN, TOL2, BETA, STOP, ITERS, REASON, RTOL, ATOL, MAXIT, NUPD, RR0, ALPHA, PQS, RQ, QQ };  // RR0: r.r of the initial guess
-// ALPHA: the step length of the single-reduction iteration (beat_rr_merged_next); PQS, RQ, QQ: p.Ap, r.Ap and Ap.Ap of the pass that
-// predicts the stop (beat_rr_pdot with a ring slot; PQS is copied to PQ).  Device side only: the host reads the first 16 entries.
-// The operator's own scalar state (beat_pde::d_st) has BEAT_ST_DOUBLES entries.
-constexpr int BEAT_ST_DOUBLES = 32;
+// (the slots of the PCG scalar state `st` and BEAT_ST_DOUBLES: beat_pcg_scalar.h)
 constexpr int PRING = 6;  // search directions kept by the deferred-x PCG before x must be brought up to date (default ring)
 // Per-node-row operators on a single slab keep PRING_MAX directions (beat_pde::ring): their solves take 9 - 12 iterations at the
 // reference's dt (profiles/r05_shell_guess.md), and with a ring of 6 every one of them paid an in-loop flush -- x and the guess's
@@ -158,32 +154,40 @@ inline int beat_pde_first_chunk(const beat_pde* pde) {
   return pde->last_iters >= 0 ? std::max(1, pde->last_iters + extra) : 8;
 }
 
-// What a solve starts with (pcg_begin_kernel's step).  A right-hand side that is given one runs the start in the launch that sums its
+// What a solve starts with (beat_pcg_begin's arguments).  A right-hand side that is given one runs the start in the launch that sums its
 // partials; nullptr: the caller starts the solve itself (a decomposed solve: the all-reduce sits between the sums and the start)
 struct PcgStart {
   double rtol, atol;
   int max_it;
 };
 
-// The scalar step that follows a reduction's sums, in the same launch (BEAT_PCG_FUSE=0: in a launch of its own behind it)
+// One scalar step of the PCG (beat_pcg_step in beat_pcg_scalar.h) on the state `st`: behind a reduction's sums, in the same launch
+// (BEAT_PCG_FUSE=0: in a launch of its own behind it), or in a launch of its own (beat_pcg_launch_step: the stage API, and a decomposed
+// solve between its all-reduce and the next pass)
 struct ScalarStep {
-  enum Kind { NONE = 0, ROLL, BEGIN, PREDICT };  // (the values of reduce_partials_kernel's `then`)
-  Kind kind = NONE;
-  double* st = nullptr;       // the scalar state the step works on: the one the sums were just written into
-  double* counter = nullptr;  // any kind: counts the executed residual update (st + NUPD) when the reduction is not latched
-  double rtol = 0.0, atol = 0.0;  // BEGIN: the start of a solve
+  beat_pde_detail::PcgStep kind = beat_pde_detail::STEP_NONE;
+  double* st = nullptr;       // the scalar state the step works on (behind a reduction: the one the sums were just written into)
+  double* counter = nullptr;  // behind a reduction, any kind: counts the executed residual update (st + NUPD) when it is not latched
+  double rtol = 0.0, atol = 0.0;  // STEP_BEGIN: the start of a solve
   int max_it = 0;
-  double* alpha_slot = nullptr;  // PREDICT (the predicted stop behind PDOT, beat_pcg_predict): the ring slot's step length ...
-  double bound_c = 0.0;          // ... and beat_rr_predict_bound
+  double* alpha_slot = nullptr;  // STEP_PREDICT, STEP_MERGED: the ring slot's step length (d_alphas + slot)
+  double bound_c = 0.0;          // STEP_PREDICT: beat_rr_predict_bound
   // behind a deferred-x residual update: counts it and, with `roll`, rolls the iteration (beta, iteration count, latch)
-  static ScalarStep after_update(double* st, bool roll) { return {roll ? ROLL : NONE, st, st + beat_pde_detail::NUPD}; }
+  static ScalarStep after_update(double* st, bool roll) {
+    return {roll ? beat_pde_detail::STEP_ROLL : beat_pde_detail::STEP_NONE, st, st + beat_pde_detail::NUPD};
+  }
+  static ScalarStep roll(double* st) { return {beat_pde_detail::STEP_ROLL, st}; }
   static ScalarStep begin(double* st, const PcgStart* s) {
-    return s ? ScalarStep{BEGIN, st, nullptr, s->rtol, s->atol, s->max_it} : ScalarStep{};
+    return s ? ScalarStep{beat_pde_detail::STEP_BEGIN, st, nullptr, s->rtol, s->atol, s->max_it} : ScalarStep{};
+  }
+  static ScalarStep with_slot(beat_pde_detail::PcgStep kind, double* st, double* alpha_slot, double bound_c = 0.0) {
+    return {kind, st, nullptr, 0.0, 0.0, 0, alpha_slot, bound_c};
   }
 };
 // fixed-order sum of `count` block partials of `nsum` quantities into out[0..nsum), skipped when st[STOP] is set (st may be nullptr);
 // then `step` (beat_pde.hip)
 int beat_pde_launch_reduce(beat_pde* pde, int count, int nsum, double* out, const double* st, const ScalarStep& step = {});
+int beat_pcg_launch_step(beat_pde* pde, const ScalarStep& step);  // `step` alone, one thread
 
 // The hand-off between the two parts of a pass: part 0 puts its block count under the pass's name, the part 1 that follows takes it
 // (once) and must be of the same pass
@@ -316,9 +320,7 @@ int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const 
 double beat_rr_predict_bound(const beat_pde* pde);
 int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev_r_new, const double* dev_p, int slot,
                  bool roll = true);
-int beat_rr_next(beat_pde* pde, double* dev_st);
 // the single-reduction (Chronopoulos-Gear) iteration of a decomposed solve: see beat_pde_rr.hip
 int beat_rr_udot_part(beat_pde* pde, double* dev_st, const double* dev_r, int part);
-int beat_rr_merged_next(beat_pde* pde, double* dev_st, int slot);
 int beat_rr_prupd(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,
                   double* dev_r_new);

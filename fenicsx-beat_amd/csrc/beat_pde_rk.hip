@@ -15,6 +15,7 @@
 // out): 176 B/node, twice the 88 of the real iteration.  The stencil reads its 15 neighbours straight from global memory
 // (x-neighbours from the same cache lines, the y / z rows from L2): no LDS staging.
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <cmath>
 #include <vector>
@@ -41,13 +42,6 @@ struct ZOp {
   const double* tk;            // K table
   double a, b, c;
 };
-
-__device__ __forceinline__ int axis_t(int i, int n, int lo_phys, int hi_phys) {
-  if (n == 1 && lo_phys && hi_phys) return 1;
-  if (i == 0 && lo_phys) return 0;
-  if (i == n - 1 && hi_phys) return 2;
-  return 1;
-}
 
 // 1 / diag(S) of a node type
 __device__ __forceinline__ void zdinv(const ZOp& op, int type, double& dr, double& di) {
@@ -88,10 +82,10 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zapply_kernel(Geom g, ZOp op, cons
   double s_re = 0.0, s_im = 0.0;
   for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
     const int iz = row / g.ny, iy = row - iz * g.ny;
-    const int tyz = 3 * axis_t(iy, g.ny, 1, 1) + 9 * axis_t(iz, g.nz, 1, 1);
+    const int tyz = 3 * axis_type(iy, g.ny, 1, 1) + 9 * axis_type(iz, g.nz, 1, 1);
     const int64_t base = (int64_t)row * g.nx;
     for (int ix = lane; ix < g.nx; ix += 64) {
-      const int type = axis_t(ix, g.nx, 1, 1) + tyz;
+      const int type = axis_type(ix, g.nx, 1, 1) + tyz;
       const int64_t i = base + ix;
       double vr[15], vi[15];
       gather15(pre, g, ix, iy, iz, i, vr);
@@ -155,10 +149,10 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zbegin_kernel(Geom g, ZOp op, cons
   double s_zr = 0.0, s_zi = 0.0, s_rr = 0.0;
   for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
     const int iz = row / g.ny, iy = row - iz * g.ny;
-    const int tyz = 3 * axis_t(iy, g.ny, 1, 1) + 9 * axis_t(iz, g.nz, 1, 1);
+    const int tyz = 3 * axis_type(iy, g.ny, 1, 1) + 9 * axis_type(iz, g.nz, 1, 1);
     const int64_t base = (int64_t)row * g.nx;
     for (int ix = lane; ix < g.nx; ix += 64) {
-      const int type = axis_t(ix, g.nx, 1, 1) + tyz;
+      const int type = axis_type(ix, g.nx, 1, 1) + tyz;
       const int64_t i = base + ix;
       double dr, di;
       zdinv(op, type, dr, di);
@@ -206,10 +200,10 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zupdate_kernel(Geom g, ZOp op, con
   double s_zr = 0.0, s_zi = 0.0, s_rr = 0.0;
   for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
     const int iz = row / g.ny, iy = row - iz * g.ny;
-    const int tyz = 3 * axis_t(iy, g.ny, 1, 1) + 9 * axis_t(iz, g.nz, 1, 1);
+    const int tyz = 3 * axis_type(iy, g.ny, 1, 1) + 9 * axis_type(iz, g.nz, 1, 1);
     const int64_t base = (int64_t)row * g.nx;
     for (int ix = lane; ix < g.nx; ix += 64) {
-      const int type = axis_t(ix, g.nx, 1, 1) + tyz;
+      const int type = axis_type(ix, g.nx, 1, 1) + tyz;
       const int64_t i = base + ix;
       double dr, di;
       zdinv(op, type, dr, di);
@@ -255,10 +249,10 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zdirection_kernel(Geom g, ZOp op, 
   const int nrows = g.ny * g.nz;
   for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
     const int iz = row / g.ny, iy = row - iz * g.ny;
-    const int tyz = 3 * axis_t(iy, g.ny, 1, 1) + 9 * axis_t(iz, g.nz, 1, 1);
+    const int tyz = 3 * axis_type(iy, g.ny, 1, 1) + 9 * axis_type(iz, g.nz, 1, 1);
     const int64_t base = (int64_t)row * g.nx;
     for (int ix = lane; ix < g.nx; ix += 64) {
-      const int type = axis_t(ix, g.nx, 1, 1) + tyz;
+      const int type = axis_type(ix, g.nx, 1, 1) + tyz;
       const int64_t i = base + ix;
       double dr, di;
       zdinv(op, type, dr, di);
@@ -314,9 +308,9 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zscalar_kernel(const double* __res
     st[Z_MAXIT] = max_it;
     st[Z_ITERS] = 0.0;
     st[Z_BETA_RE] = st[Z_BETA_IM] = 0.0;
-    const bool done = rr <= st[Z_TOL2];
-    st[Z_STOP] = done ? 1.0 : 0.0;
-    st[Z_REASON] = done ? (rr <= tr ? 2.0 : 3.0) : 0.0;
+    const int reason = beat_pcg_stop_reason(rr, st[Z_TOL2], tr);
+    st[Z_STOP] = reason != 0 ? 1.0 : 0.0;
+    st[Z_REASON] = (double)reason;
   } else if (step == 1) {
     st[Z_PQ_RE] = s[0];
     st[Z_PQ_IM] = s[1];
@@ -336,9 +330,9 @@ __global__ __launch_bounds__(BEAT_BLOCK) void zscalar_kernel(const double* __res
     st[Z_RR] = s[2];
     st[Z_ITERS] += 1.0;
     const double tr = st[Z_RTOL] * st[Z_RTOL] * st[Z_BB];
-    if (st[Z_RR] <= st[Z_TOL2]) {
+    if (const int reason = beat_pcg_stop_reason(st[Z_RR], st[Z_TOL2], tr)) {
       st[Z_STOP] = 1.0;
-      st[Z_REASON] = st[Z_RR] <= tr ? 2.0 : 3.0;
+      st[Z_REASON] = (double)reason;
     } else if (st[Z_ITERS] >= st[Z_MAXIT]) {
       st[Z_STOP] = 1.0;
       st[Z_REASON] = -3.0;
@@ -368,10 +362,10 @@ __global__ __launch_bounds__(BEAT_BLOCK) void rk_rhs_kernel(Geom g, RkRhsArgs a,
   const int nrows = g.ny * g.nz;
   for (int row = blockIdx.x * 4 + wave; row < nrows; row += gridDim.x * 4) {
     const int iz = row / g.ny, iy = row - iz * g.ny;
-    const int tyz = 3 * axis_t(iy, g.ny, 1, 1) + 9 * axis_t(iz, g.nz, 1, 1);
+    const int tyz = 3 * axis_type(iy, g.ny, 1, 1) + 9 * axis_type(iz, g.nz, 1, 1);
     const int64_t base = (int64_t)row * g.nx;
     for (int ix = lane; ix < g.nx; ix += 64) {
-      const int type = axis_t(ix, g.nx, 1, 1) + tyz;
+      const int type = axis_type(ix, g.nx, 1, 1) + tyz;
       const int64_t i = base + ix;
       double kr = 0.0, ki = 0.0;
       const double* __restrict__ rk = a.tk + type * TABW;

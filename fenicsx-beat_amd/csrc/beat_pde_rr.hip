@@ -18,6 +18,7 @@
 //
 // Replaces, like beat_pde.hip, dolfinx assemble_vector + PETSc KSP.solve of src/beat/base_model.py:196-236.
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -87,18 +88,6 @@ struct RKernArgs {
   double* Y2;
 };
 
-// lane i <- lane i-1 (lane 0 <- 0) / lane i <- lane i+1 (lane 63 <- 0); all 64 lanes must be active
-__device__ __forceinline__ double from_left(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);  // wave_shr:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double from_right(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);  // wave_shl:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
 // BEAT_RR_BUF (round 5; 0 = the clamped global loads of rounds 2 - 4): the rows of a plane through a raw buffer over that plane -- a lane
 // that is to hold 0 (outside the box, a plane beyond a physical face) passes an offset beyond the buffer's end (or the plane gets no
 // records): the load returns 0 and fetches nothing, and neither the clamped address nor the select that zeroed the value afterwards
@@ -109,8 +98,6 @@ __device__ __forceinline__ double from_right(double v) {
 #ifndef BEAT_RR_BUF
 #define BEAT_RR_BUF 2
 #endif
-typedef int rr_v2i __attribute__((ext_vector_type(2)));
-[[maybe_unused]] constexpr unsigned RR_OOB = 0x80000000u;
 // BEAT_RR_NT (round 6): bit 0 non-temporal row loads, bit 1 non-temporal stores of the pass's output field.  2 is the build: the
 // output field is written once and read by the NEXT launch (1 GB at 512^3: from HBM either way), and not keeping it in the L2 leaves
 // the L2 to the y-halo rows neighbouring waves re-read -- diffusion part of the 512^3 step 3.38 - 3.42 -> 3.31 - 3.36 ms, of the developed
@@ -125,11 +112,7 @@ __device__ __forceinline__ void rr_store(double* p, double v) {
   *p = v;
 #endif
 }
-__device__ __forceinline__ double rr_buf_load(const double* base, unsigned bytes, unsigned off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  const rr_v2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, (BEAT_RR_NT & 1) ? 2 : 0);
-  return __hiloint2double(v.y, v.x);
-}
+constexpr int RR_LOAD_AUX = (BEAT_RR_NT & 1) ? 2 : 0;  // buf_load's cache policy for the row loads
 
 // BEAT_RR_ALIGN = 1 (round 5): in PDOT and RUPD (and the two passes of the single-reduction iteration) a wave owns 64 x-nodes that start on a multiple of 64 (whole aligned 512-byte pieces of
 // a row) instead of 62 that start 8 bytes before a multiple of 496.  The access pattern alone -- six rows of a plane read, four written,
@@ -161,18 +144,6 @@ constexpr bool rr_aligned_mode(int mode) {
   return BEAT_RR_ALIGN == 1 && BEAT_RR_BUF != 0 && (mode == 0 || mode == 1 || mode == 3 || mode == 4 || (mode == 2 && BEAT_RR_ALIGN_RHS == 1));
 }
 
-__device__ __forceinline__ int axis_type3(int i, int n, int lo_phys, int hi_phys) {
-  if (n == 1 && lo_phys && hi_phys) return 1;  // collapsed axis: no coupling along it
-  if (i == 0 && lo_phys) return 0;
-  if (i == n - 1 && hi_phys) return 2;
-  return 1;
-}
-
-__device__ __forceinline__ int xcd_block(int b, int total) {
-  const int per = (total + 7) >> 3;
-  return (b & 7) * per + (b >> 3);
-}
-
 // waves per SIMD asked of the register allocator: the right-hand side with a guess (two register windows) / the iteration's two passes
 #ifndef BEAT_RR_WAVES_RHS
 #define BEAT_RR_WAVES_RHS 3
@@ -184,7 +155,7 @@ __device__ __forceinline__ int xcd_block(int b, int total) {
 // passes distinct buffers (the residual update writes r out of place), and without the no-alias guarantee every
 // store would have to complete (s_waitcnt vmcnt(0)) before the next plane's loads may issue.
 // PRED (PDOT only, beat_rr_pdot with a ring slot): the pass also sums r . (A p) and (A p) . (A p), the two sums the prediction of the
-// next residual's r.r needs (beat_pcg_predict in beat_pde.hip); r of the owned rows is parked in LDS when its plane is staged and read
+// next residual's r.r needs (beat_pcg_predict in beat_pcg_scalar.h); r of the owned rows is parked in LDS when its plane is staged and read
 // back row by row where it is used -- a wave-private slot per plane parity, no barrier, and its waits count on lgkmcnt, not on the
 // vmcnt of the plane in flight
 template <int MODE, int RY, int PD, bool GUESS = false, bool PRED = false>
@@ -243,7 +214,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
   const int ze = wave_ok ? min(zb + g.zc, g.z_hi) : zb;
   const bool x_in = wave_ok && gx >= 0 && gx < g.nx;
   const bool x_out = x_in && (ALIGNED || (lane >= 1 && lane <= SEG));  // this lane produces outputs
-  const int tx = axis_type3(gx, g.nx, 1, 1);
+  const int tx = axis_type(gx, g.nx, 1, 1);
   bool row_in[NR];
   int txy[NR];  // tx + 3 ty of the register rows
   int off[NR];  // in-plane offset of the (clamped, always addressable) element this lane loads of each row
@@ -252,22 +223,22 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
   for (int r = 0; r < NR; ++r) {
     const int gy = y0 + r;
     row_in[r] = x_in && gy >= 0 && gy < g.ny;
-    txy[r] = tx + 3 * axis_type3(gy, g.ny, 1, 1);
+    txy[r] = tx + 3 * axis_type(gy, g.ny, 1, 1);
     off[r] = min(max(gy, 0), g.ny - 1) * g.nx + cx;
-    if constexpr (BUF) off[r] = row_in[r] ? (int)((unsigned)(gy * g.nx + gx) * 8u) : (int)RR_OOB;  // byte offset within the plane, or out of range
+    if constexpr (BUF) off[r] = row_in[r] ? (int)((unsigned)(gy * g.nx + gx) * 8u) : (int)BUF_OOB;  // byte offset within the plane, or out of range
   }
   [[maybe_unused]] const unsigned pbytes = (unsigned)(g.plane * 8);
   // ALIGNED: what this lane fetches in the x-halo load of a plane (lanes 0 .. NR-1: left of the segment in rows 0 .. NR-1, lanes
   // 8 .. 8+NR-1: right of it), and the node type of that element (PDOT forms p_new there as everywhere)
-  [[maybe_unused]] unsigned hoff = RR_OOB;
+  [[maybe_unused]] unsigned hoff = BUF_OOB;
   [[maybe_unused]] int htxy = 13 % 9;
   if constexpr (ALIGNED) {
     const int hr = lane < 8 ? lane : lane - 8;
     const int hx = lane < 8 ? seg * SEGW - 1 : seg * SEGW + SEGW;
     const int hy = y0 + hr;
     const bool hv = wave_ok && (lane < NR || (lane >= 8 && lane < 8 + NR)) && hx >= 0 && hx < g.nx && hy >= 0 && hy < g.ny;
-    hoff = hv ? (unsigned)(hy * g.nx + hx) * 8u : RR_OOB;
-    htxy = axis_type3(min(max(hx, 0), g.nx - 1), g.nx, 1, 1) + 3 * axis_type3(min(max(hy, 0), g.ny - 1), g.ny, 1, 1);
+    hoff = hv ? (unsigned)(hy * g.nx + hx) * 8u : BUF_OOB;
+    htxy = axis_type(min(max(hx, 0), g.nx - 1), g.nx, 1, 1) + 3 * axis_type(min(max(hy, 0), g.ny - 1), g.ny, 1, 1);
   }
   double beta = 0.0, alpha = 0.0;
   if (OLD) beta = a.st[BETA];
@@ -321,7 +292,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
       [[maybe_unused]] const bool zok = (k >= 0 || !g.z_lo_phys) && (k < g.nz || !g.z_hi_phys);
       // ghost planes (another rank's boundary planes): their z type comes with the geometry; PDOT keeps p_new there
       // too -- both neighbours form it from the same exchanged r and the same p_old, so it needs no exchange of its own
-      const int tz9 = 9 * (k < 0 ? g.ghost_lo_tz : k >= g.nz ? g.ghost_hi_tz : axis_type3(k, g.nz, g.z_lo_phys, g.z_hi_phys));
+      const int tz9 = 9 * (k < 0 ? g.ghost_lo_tz : k >= g.nz ? g.ghost_hi_tz : axis_type(k, g.nz, g.z_lo_phys, g.z_hi_phys));
       const bool own_plane = (k >= zb && k < ze) || (k == -1 && zb == 0 && !g.z_lo_phys) ||
                              (k == g.nz && ze == g.nz && !g.z_hi_phys);
 #pragma unroll
@@ -366,7 +337,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
       if (z + PD >= zb && z + PD < ze) {
         const double* __restrict__ br = X2 + (int64_t)(z + PD) * g.plane;
 #pragma unroll
-        for (int j = 0; j < RY; ++j) rvn[u][j] = BUF ? rr_buf_load(br, pbytes, (unsigned)off[j + 1]) : br[off[j + 1]];
+        for (int j = 0; j < RY; ++j) rvn[u][j] = BUF ? buf_load<RR_LOAD_AUX>(br, pbytes, (unsigned)off[j + 1]) : br[off[j + 1]];
       }
     }
     {
@@ -380,18 +351,18 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
           const unsigned pb = ((kf >= 0 || !g.z_lo_phys) && (kf < g.nz || !g.z_hi_phys)) ? pbytes : 0u;
 #pragma unroll
           for (int r = 0; r < NR; ++r) {
-            ra[u][r] = rr_buf_load(bx, pb, (unsigned)off[r]);
-            if (OLD) rb2[u][r] = rr_buf_load(bx2, pb, (unsigned)off[r]);
+            ra[u][r] = buf_load<RR_LOAD_AUX>(bx, pb, (unsigned)off[r]);
+            if (OLD) rb2[u][r] = buf_load<RR_LOAD_AUX>(bx2, pb, (unsigned)off[r]);
           }
           if constexpr (ALIGNED) {
-            rha[u] = rr_buf_load(bx, pb, hoff);
-            if (OLD) rhb[u] = rr_buf_load(bx2, pb, hoff);
-            if (GUESS) rhb[u] = rr_buf_load(X2 + (int64_t)cz * g.plane, pb, hoff);
+            rha[u] = buf_load<RR_LOAD_AUX>(bx, pb, hoff);
+            if (OLD) rhb[u] = buf_load<RR_LOAD_AUX>(bx2, pb, hoff);
+            if (GUESS) rhb[u] = buf_load<RR_LOAD_AUX>(X2 + (int64_t)cz * g.plane, pb, hoff);
           }
           if (GUESS) {
             const double* __restrict__ b1 = X2 + (int64_t)cz * g.plane;  // (e comes as X2: see the note on aliasing)
 #pragma unroll
-            for (int r = 0; r < NR; ++r) re1[u][r < NE ? r : 0] = rr_buf_load(b1, pb, (unsigned)off[r]);
+            for (int r = 0; r < NR; ++r) re1[u][r < NE ? r : 0] = buf_load<RR_LOAD_AUX>(b1, pb, (unsigned)off[r]);
           }
         } else {
 #pragma unroll
@@ -442,7 +413,7 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
         eRp[r] = ALIGNED ? from_right_h(Ep[r], HEp, 8 + r) : from_right(Ep[r]);
       }
     }
-    const int tz = axis_type3(z, g.nz, g.z_lo_phys, g.z_hi_phys);
+    const int tz = axis_type(z, g.nz, g.z_lo_phys, g.z_hi_phys);
 #pragma unroll
     for (int j = 0; j < RY; ++j) {
       const int r = j + 1;
@@ -612,53 +583,6 @@ __global__ __launch_bounds__(BEAT_BLOCK, (GUESS && RY == 2 && PD == 1) ? BEAT_RR
       a.partials[2 * BEAT_MAX_PARTIALS + g.part_off + blockIdx.x] = s2;
     }
   }
-}
-
-// scalar roll between K_B and the next K_A (beta, iteration count, convergence latch): pcg_next_kernel of beat_pde.hip
-__global__ void rr_next_kernel(double* st) {
-  if (st[STOP] != 0.0) return;
-  st[BETA] = st[RZN] / st[RZ];
-  st[RZ] = st[RZN];
-  st[RR] = st[RRN];
-  st[ITERS] += 1.0;
-  const double tr = st[RTOL] * st[RTOL] * st[BB];
-  if (st[RR] <= st[TOL2]) {
-    st[STOP] = 1.0;
-    st[REASON] = st[RR] <= tr ? 2.0 : 3.0;
-  } else if (st[ITERS] >= st[MAXIT]) {
-    st[STOP] = 1.0;
-    st[REASON] = -3.0;
-  }
-}
-
-// The scalar step of the single-reduction iteration (Chronopoulos & Gear 1989), after the ONE all-reduce of
-//   st[PQ] = u . A u,  st[RZN] = r . u,  st[RRN] = r . r      (u = D^-1 r, r = r_i):
-// the stopping test on r_i, then  beta_i = (r_i.u_i) / (r_{i-1}.u_{i-1}),  alpha_i = (r.u) / (u.Au - beta_i (r.u) / alpha_{i-1})
-// -- the value p_i . A p_i has in exact arithmetic, without forming p_i first.  Counts the update that follows.
-__global__ void rr_merged_next_kernel(double* st, double* alphas, int slot) {
-  if (st[STOP] != 0.0) return;
-  const double g = st[RZN], d = st[PQ], rr = st[RRN];
-  st[RR] = rr;
-  const double tr = st[RTOL] * st[RTOL] * st[BB];
-  if (rr <= st[TOL2]) {
-    st[STOP] = 1.0;
-    st[REASON] = rr <= tr ? 2.0 : 3.0;
-    return;
-  }
-  if (st[ITERS] >= st[MAXIT]) {
-    st[STOP] = 1.0;
-    st[REASON] = -3.0;
-    return;
-  }
-  const bool first = st[ITERS] == 0.0;
-  const double beta = first ? 0.0 : g / st[RZ];
-  const double alpha = first ? g / d : g / (d - beta * g / st[ALPHA]);
-  st[BETA] = beta;
-  st[ALPHA] = alpha;
-  st[RZ] = g;
-  alphas[slot] = alpha;
-  st[NUPD] += 1.0;
-  st[ITERS] += 1.0;
 }
 
 // Rows per wave and blocks per launch: on big slabs (>= 64 M nodes) 4 rows and ~4096 blocks are best (the 6-of-4 row
@@ -861,7 +785,7 @@ int beat_rr_rhs(beat_pde* pde, const double* dev_v_prev, const double* const* ho
   return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 3, dev_st, nullptr, ScalarStep::begin(dev_st, start));
 }
 
-// Bound constant of the predicted stop (beat_pcg_predict in beat_pde.hip): E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds
+// Bound constant of the predicted stop (beat_pcg_predict in beat_pcg_scalar.h): E = c (sqrt(RR) + |alpha| sqrt(QQ))^2 bounds
 // |rho - RR'|, rho = RR - 2 alpha RQ + alpha^2 QQ formed from the computed sums, RR' = what the residual update's reduction would
 // compute for r_{i+1}.  Every sum here is a chain of roundings: a lane's accumulator (acc = fma(x, y, acc): the product is exact, one
 // rounding per node it sums, zc planes x RY rows), the block tree (beat_block_sum: 6 shuffle levels + 2), the partials one thread of
@@ -917,10 +841,8 @@ int beat_rr_pdot_part(beat_pde* pde, double* dev_st, const double* dev_r, const 
   if (part == 0) return BEAT_OK;
   if (pred) {
     static_assert(RQ == PQS + 1 && QQ == PQS + 2, "the three sums are reduced into one run of slots");
-    ScalarStep predict{ScalarStep::PREDICT, dev_st};
-    predict.alpha_slot = pde->d_alphas + slot;
-    predict.bound_c = pde->predict_c;
-    return beat_pde_launch_reduce(pde, count, 3, dev_st + PQS, dev_st, predict);
+    return beat_pde_launch_reduce(pde, count, 3, dev_st + PQS, dev_st,
+                                  ScalarStep::with_slot(STEP_PREDICT, dev_st, pde->d_alphas + slot, pde->predict_c));
   }
   return beat_pde_launch_reduce(pde, count, 1, dev_st + PQ, dev_st);
 }
@@ -932,7 +854,7 @@ int beat_rr_pdot(beat_pde* pde, double* dev_st, const double* dev_r, const doubl
 
 // alpha = st[RZ]/st[PQ] (kept for `slot`); r_new = r - alpha A p (out of place; ghost planes of p current); LOCAL
 // r.D^-1 r, r.r -> dev_st[RZN..RRN]; counts the update; with `roll` the scalar roll (beta, latch) follows -- a
-// decomposed solve all-reduces dev_st[RZN..RRN] first and calls beat_rr_next itself.
+// decomposed solve all-reduces dev_st[RZN..RRN] first and launches the roll itself (beat_pcg_launch_step).
 int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev_r_new, const double* dev_p, int slot,
                  bool roll) {
   const RGeom g = make_geom(pde, 0, pde->g.nz, 0, 0, RR_RUPD);
@@ -944,7 +866,7 @@ int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev
   a.slot = slot;
   launch_rr<RR_RUPD>(pde, g, a);
   BEAT_LAUNCH_CHECK();
-  // (with `roll` the scalar step -- beta, iteration count, latch: rr_next_kernel's -- runs in the reduction's launch)
+  // (with `roll` the scalar step -- beta, iteration count, latch: beat_pcg_roll -- runs in the reduction's launch)
   return beat_pde_launch_reduce(pde, grid_blocks(g), 2, dev_st + RZN, dev_st, ScalarStep::after_update(dev_st, roll));
 }
 
@@ -952,7 +874,7 @@ int beat_rr_rupd(beat_pde* pde, double* dev_st, const double* dev_r, double* dev
 // Iteration i of the classic loop needs two all-reduces that depend on each other (p.Ap, then r.z / r.r of the updated
 // residual).  In Chronopoulos & Gear's form both come from ONE pass over r_i:
 //   K_U (udot):   u = D^-1 r_i formed while loading;  partials  u . A u,  r . u,  r . r     -- reads r, writes nothing
-//   [one all-reduce of three values; scalar step: stopping test, beta_i, alpha_i]
+//   [one all-reduce of three values; scalar step: stopping test, beta_i, alpha_i (beat_pcg_merged_next in beat_pcg_scalar.h)]
 //   K_P (prupd):  p_i = u + beta_i p_{i-1} formed while loading, stored;  r_{i+1} = r_i - alpha_i A p_i   -- no dot product
 // With the operator re-applied from registers neither w = A u nor s = A p is ever stored (the textbook form keeps both and
 // updates s by recurrence): 8 + 32 B/node per iteration against 24 + 24, two stencil passes as before, and k + 1 reductions
@@ -973,12 +895,6 @@ int beat_rr_udot_part(beat_pde* pde, double* dev_st, const double* dev_r, int pa
   return part == 0 ? BEAT_OK : beat_pde_launch_reduce(pde, count, 3, dev_st + PQ, dev_st);
 }
 
-int beat_rr_merged_next(beat_pde* pde, double* dev_st, int slot) {
-  BEAT_KERNEL(rr_merged_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st, pde->d_alphas, slot);
-  BEAT_LAUNCH_CHECK();
-  return BEAT_OK;
-}
-
 // p_new = D^-1 r + st[BETA] p_old on the slab and on the ghost planes next to it (as beat_rr_pdot_part: no exchange of p),
 // r_new = r - st[ALPHA] A p_new (out of place).  The ghost planes of r (and of p_old) must be current.
 int beat_rr_prupd(beat_pde* pde, double* dev_st, const double* dev_r, const double* dev_p_old, double* dev_p_new,
@@ -990,12 +906,6 @@ int beat_rr_prupd(beat_pde* pde, double* dev_st, const double* dev_r, const doub
   a.y = dev_p_new;
   a.y2 = dev_r_new;
   launch_rr<RR_PRUPD>(pde, g, a);
-  BEAT_LAUNCH_CHECK();
-  return BEAT_OK;
-}
-
-int beat_rr_next(beat_pde* pde, double* dev_st) {
-  BEAT_KERNEL(rr_next_kernel, dim3(1), dim3(1), 0, pde->ctx->stream, dev_st);
   BEAT_LAUNCH_CHECK();
   return BEAT_OK;
 }

@@ -12,6 +12,7 @@
 // summation order in the dot products.  Replaces, like beat_pde.hip, dolfinx assemble_vector + PETSc KSP.solve of
 // src/beat/base_model.py:196-236 -- for the reference's own CPU-sized configurations (demos/niederer_benchmark.py).
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -43,13 +44,6 @@ struct SmallArgs {
   GuessTerms gt;         // gt.d == nullptr: no guess
   double* st;            // PCG scalar state out (BB, RR, ITERS, REASON, STOP, NUPD)
 };
-
-__device__ __forceinline__ int axis_type_s(int i, int n) {
-  if (n == 1) return 1;  // collapsed axis: no coupling along it
-  if (i == 0) return 0;
-  if (i == n - 1) return 2;
-  return 1;
-}
 
 // sum over the workgroup, the same value in every thread; `slot` alternates between two partial buffers so that one
 // barrier per reduction suffices
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void pcg_small_kernel(SmallArgs a) {
     r[j] = xinc[j] = 0.0;
     if (i < a.n) {
       const int iz = i / plane, rem = i - iz * plane, iy = rem / a.nx, ix = rem - iy * a.nx;
-      type[j] = axis_type_s(ix, a.nx) + 3 * axis_type_s(iy, a.ny) + 9 * axis_type_s(iz, a.nz);
+      type[j] = axis_type(ix, a.nx, 1, 1) + 3 * axis_type(iy, a.ny, 1, 1) + 9 * axis_type(iz, a.nz, 1, 1);
       p[i] = a.v[i];
     }
   }
@@ -165,8 +159,7 @@ __global__ __launch_bounds__(SMALL_THREADS) void pcg_small_kernel(SmallArgs a) {
   const double rr0 = rr;
   const double tr = a.rtol * a.rtol * bb, ta = a.atol * a.atol;
   const double tol2 = tr > ta ? tr : ta;
-  int iters = 0, reason = 0;
-  if (rr <= tol2) reason = rr <= tr ? 2 : 3;
+  int iters = 0, reason = beat_pcg_stop_reason(rr, tol2, tr);
   // first direction p = D^-1 r (the reductions' barriers have ended the reads of p = x0)
   if (reason == 0) {
 #pragma unroll
@@ -212,10 +205,8 @@ __global__ __launch_bounds__(SMALL_THREADS) void pcg_small_kernel(SmallArgs a) {
     const double beta = rzn / rz;
     rz = rzn;
     ++iters;
-    if (rr <= tol2) {
-      reason = rr <= tr ? 2 : 3;
-      break;
-    }
+    reason = beat_pcg_stop_reason(rr, tol2, tr);
+    if (reason != 0) break;
 #pragma unroll
     for (int j = 0; j < M; ++j) {
       if (type[j] >= 0) {

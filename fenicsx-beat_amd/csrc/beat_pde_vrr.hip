@@ -21,6 +21,7 @@
 // Replaces, like beat_pde_var.hip, PETSc's MatMult inside KSP.solve (src/beat/base_model.py:236) for operators assembled
 // from per-cell conductivity tensors (src/beat/conductivities.py:101-118, demos/biv_endocardial.py:187-282).
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -49,17 +50,6 @@ struct VrrArgs {
   int part_off;
   const double* st;
 };
-
-__device__ __forceinline__ double from_left(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);  // wave_shr:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double from_right(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);  // wave_shl:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
 
 // forward slots of the 15-point stencil (beat_stencil_offsets): 0 centre, 1 +x, 3 +y, 5 +z, 7 +x+y, 9 +y+z, 11 +x+z,
 // 13 +x+y+z; the backward slot k+1 pairs with the forward slot k

@@ -32,6 +32,7 @@
 // Replaces, like beat_pde_var.hip, PETSc's MatMult inside KSP.solve (src/beat/base_model.py:236) for operators assembled
 // from per-cell conductivity tensors (src/beat/conductivities.py:101-118, demos/biv_endocardial.py:187-282).
 #include "beat_pde_internal.h"
+#include "beat_pde_device.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -87,37 +88,18 @@ struct VtlArgs {
   int ignore_stop;         // launches outside the iteration (the latch of the previous solve is still set)
 };
 
-__device__ __forceinline__ double vtl_from_left(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x138, 0xf, 0xf, true);  // wave_shr:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x138, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double vtl_from_right(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, true);  // wave_shl:1
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-
 // One plane of a field (or of a coefficient row) as a raw buffer: a lane that wants nothing passes an offset beyond the
 // buffer's end -- its load returns 0 and fetches nothing, its store is dropped -- so neither needs a branch or a change
 // of the exec mask, and the compiler can count what is outstanding at every point of the march.
-typedef int vtl_v2i __attribute__((ext_vector_type(2)));
-constexpr unsigned VTL_OOB = 0x80000000u;
 // (-DBEAT_VTL_NT, an experiment of round 5: bit 0 = the coefficient loads non-temporal -- every coefficient is read once per pass
 // and should not push the vector rows the neighbouring tiles share out of the L2 --, bit 1 = the stores of p and q; measured in
 // profiles/r05_shell400.md; default 0)
 #ifndef BEAT_VTL_NT
 #define BEAT_VTL_NT 0
 #endif
-template <int AUX = 0>
-__device__ __forceinline__ double vtl_buf_load(const double* base, unsigned bytes, unsigned off) {
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  const vtl_v2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, AUX);
-  return __hiloint2double(v.y, v.x);
-}
 __device__ __forceinline__ void vtl_buf_store(double* base, unsigned bytes, unsigned off, double val) {
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-  vtl_v2i v;
+  buf_v2i v;
   v.x = __double2loint(val);
   v.y = __double2hiint(val);
   __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)off, 0, (BEAT_VTL_NT & 2) ? 2 : 0);
@@ -202,10 +184,10 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
     // With branches around the loads and the store the compiler cannot count what is outstanding where the paths join
     // and waits for everything (vmcnt(0) right behind the store of q, every plane).
     const unsigned pbytes = (unsigned)a.plane * 8u;
-    auto lane_off = [&](u64 mk, unsigned ro) -> unsigned { return (mk & lanebit) ? ro * 8u : VTL_OOB; };
-    auto ldp = [&](u64 mk, int z, unsigned ro) -> double { return vtl_buf_load(X + (int64_t)z * a.plane, pbytes, lane_off(mk, ro)); };
+    auto lane_off = [&](u64 mk, unsigned ro) -> unsigned { return (mk & lanebit) ? ro * 8u : BUF_OOB; };
+    auto ldp = [&](u64 mk, int z, unsigned ro) -> double { return buf_load(X + (int64_t)z * a.plane, pbytes, lane_off(mk, ro)); };
     auto ldc = [&](u64 mk, int slot, int z, unsigned ro) -> double {
-      return vtl_buf_load(A + (int64_t)slot * a.ld + (int64_t)z * a.plane, pbytes, lane_off(mk, ro));
+      return buf_load(A + (int64_t)slot * a.ld + (int64_t)z * a.plane, pbytes, lane_off(mk, ro));
     };
     // PDOT: a value of p is formed from three loads -- the residual, the previous direction and the row's centre coefficient
     // c0 (D^-1 = 1 / c0, rounded as var_form_A_kernel rounds the stored 1/diag; p = fma(beta, p_old, D^-1 r): the very
@@ -245,9 +227,9 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
       asm volatile("" : "+s"(kr));
       const double* Rr = ((const VtlArgs*)kr)->r;
       Trio t;
-      t.r = vtl_buf_load(Rr + (int64_t)z * a.plane, pbytes, off);
-      t.q = vtl_buf_load(X + (int64_t)z * a.plane, pbytes, no_second ? VTL_OOB : off);
-      t.c0 = RES ? 0.0 : vtl_buf_load(c0_of(z), pbytes, off);
+      t.r = buf_load(Rr + (int64_t)z * a.plane, pbytes, off);
+      t.q = buf_load(X + (int64_t)z * a.plane, pbytes, no_second ? BUF_OOB : off);
+      t.c0 = RES ? 0.0 : buf_load(c0_of(z), pbytes, off);
       return t;
     };
     // (a ghost plane of a physical face: its mask is empty, nothing is loaded, p = 0; the decomposed solve does not come here)
@@ -285,13 +267,13 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
         KArgPtr kr = ka;
         asm volatile("" : "+s"(kr));
         const double* base = is_p ? ((const VtlArgs*)kr)->r : A + slot * ld;
-        const unsigned off = lane_off(m, ro), offp = is_p ? off : VTL_OOB;
-        t.r = vtl_buf_load(base + (int64_t)zz * a.plane, pbytes, off);
-        t.q = vtl_buf_load(X + (int64_t)zz * a.plane, pbytes, no_second ? VTL_OOB : offp);
-        t.c0 = RES ? 0.0 : vtl_buf_load(c0_of(zz), pbytes, offp);
+        const unsigned off = lane_off(m, ro), offp = is_p ? off : BUF_OOB;
+        t.r = buf_load(base + (int64_t)zz * a.plane, pbytes, off);
+        t.q = buf_load(X + (int64_t)zz * a.plane, pbytes, no_second ? BUF_OOB : offp);
+        t.c0 = RES ? 0.0 : buf_load(c0_of(zz), pbytes, offp);
       } else {
         const double* base = is_p ? X : A + slot * ld;
-        t.r = vtl_buf_load(base + (int64_t)zz * a.plane, pbytes, lane_off(m, ro));
+        t.r = buf_load(base + (int64_t)zz * a.plane, pbytes, lane_off(m, ro));
       }
       return t;
     };
@@ -335,10 +317,10 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
         // the next iteration: the two planes as ONE buffer (a second descriptor costs the SGPRs the kernel does not have)
         if constexpr (GHOST) {
           double* const two = a.pnew + (int64_t)(zb - 1) * a.plane;
-          vtl_buf_store(two, 2u * pbytes, (zb == 0 && (a.first & 2) && (mo & lanebit & out_lanes)) ? roff * 8u : VTL_OOB, Pm);
-          vtl_buf_store(two, 2u * pbytes, (M0 & lanebit & out_lanes) ? pbytes + roff * 8u : VTL_OOB, P0);
+          vtl_buf_store(two, 2u * pbytes, (zb == 0 && (a.first & 2) && (mo & lanebit & out_lanes)) ? roff * 8u : BUF_OOB, Pm);
+          vtl_buf_store(two, 2u * pbytes, (M0 & lanebit & out_lanes) ? pbytes + roff * 8u : BUF_OOB, P0);
         } else {
-          vtl_buf_store(a.pnew + (int64_t)zb * a.plane, pbytes, (M0 & lanebit & out_lanes) ? roff * 8u : VTL_OOB, P0);
+          vtl_buf_store(a.pnew + (int64_t)zb * a.plane, pbytes, (M0 & lanebit & out_lanes) ? roff * 8u : BUF_OOB, P0);
         }
       } else {
         P0 = ldp(M0, zb, roff);
@@ -367,14 +349,14 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
       asm volatile("" : "+s"(ld));
       const double* bc = A + (int64_t)z * a.plane;
       constexpr int CNT = (BEAT_VTL_NT & 1) ? 2 : 0;
-      Fn[0] = PDOT ? 0.0 : vtl_buf_load<CNT>(bc, pbytes, off);  // (PDOT: the centre coefficient comes with r and p_old, a plane earlier)
+      Fn[0] = PDOT ? 0.0 : buf_load<CNT>(bc, pbytes, off);  // (PDOT: the centre coefficient comes with r and p_old, a plane earlier)
       bc += ld;
-      Fn[1] = vtl_buf_load<CNT>(bc, pbytes, off);
+      Fn[1] = buf_load<CNT>(bc, pbytes, off);
       ld += ld;
 #pragma unroll
       for (int k = 2; k < 8; ++k) {
         bc += ld;
-        Fn[k] = vtl_buf_load<CNT>(bc, pbytes, off);
+        Fn[k] = buf_load<CNT>(bc, pbytes, off);
       }
     };
     load_coefs(M0, zb);
@@ -385,7 +367,7 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
     } else {
       Pn = ldp(M1, zb + 1, roff);
     }
-    if constexpr (RES) Bn = vtl_buf_load(a.t + (int64_t)zb * a.plane, pbytes, lane_off(M0, roff));  // b of this plane
+    if constexpr (RES) Bn = buf_load(a.t + (int64_t)zb * a.plane, pbytes, lane_off(M0, roff));  // b of this plane
     Trio Ean = halo_load(ea, halo_mask(ea, moff_a, zb - 1), roff_a, zb - 1);
     Trio Ebn{0.0, 0.0, 0.0};
     if (TWO) Ebn = halo_load(eb, halo_mask(eb, moff_b, zb - 1), roff_b, zb - 1);
@@ -407,7 +389,7 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
         C0keep = Tn.c0;
         // (the plane above a slab with a live upper neighbour: the direction on the ghost plane, kept for the next iteration)
         const bool keep = z + 1 < ze || (GHOST && z + 1 == a.nz && az.gc0_hi != nullptr);
-        vtl_buf_store(az.pnew + (int64_t)(z + 1) * a.plane, pbytes, (keep && (M1 & lanebit & out_lanes)) ? roff * 8u : VTL_OOB, Pp);
+        vtl_buf_store(az.pnew + (int64_t)(z + 1) * a.plane, pbytes, (keep && (M1 & lanebit & out_lanes)) ? roff * 8u : BUF_OOB, Pp);
       }
       const double Ea = halo_value(ea, Ean), Eb = TWO ? halo_value(eb, Ebn) : 0.0;
       const double Bv = Bn;
@@ -422,7 +404,7 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
       } else {
         Pn = ldp(z + 2 <= ze ? M2 : 0ull, z + 2, roff);
       }
-      if constexpr (RES) Bn = vtl_buf_load(az.t + (int64_t)(z + 1) * a.plane, pbytes, lane_off(z + 1 < ze ? M1 : 0ull, roff));
+      if constexpr (RES) Bn = buf_load(az.t + (int64_t)(z + 1) * a.plane, pbytes, lane_off(z + 1 < ze ? M1 : 0ull, roff));
       Ean = halo_load(ea, HA, roff_a, z);
       if (TWO) Ebn = halo_load(eb, HB, roff_b, z);
       // publish this row
@@ -445,35 +427,35 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
       double c[15], v[15];
       c[0] = F[0];
       c[1] = F[1];
-      c[2] = vtl_from_left(F[1]);  // -x: the left neighbour's +x
+      c[2] = from_left(F[1]);  // -x: the left neighbour's +x
       c[3] = F[2];
       c[4] = H3;                   // -y: the lower row's +y
       c[5] = F[3];
       c[6] = K5;                   // -z: the lower plane's +z
       c[7] = F[4];
-      c[8] = vtl_from_left(H7);    // -x-y
+      c[8] = from_left(H7);    // -x-y
       c[9] = F[5];
       c[10] = K9;                  // -y-z
       c[11] = F[6];
-      const double K11l = vtl_from_left(K11), K13l = vtl_from_left(K13);
+      const double K11l = from_left(K11), K13l = from_left(K13);
       c[12] = direct ? K11 : K11l;  // -x-z
       c[13] = F[7];
       c[14] = direct ? K13 : K13l;  // -x-y-z
       v[0] = P0;
-      v[1] = vtl_from_right(P0);
-      v[2] = vtl_from_left(P0);
+      v[1] = from_right(P0);
+      v[2] = from_left(P0);
       v[3] = U0;
       v[4] = D0;
       v[5] = Pp;
       v[6] = Pm;
-      v[7] = vtl_from_right(U0);
-      v[8] = vtl_from_left(D0);
+      v[7] = from_right(U0);
+      v[8] = from_left(D0);
       v[9] = Un;
       v[10] = Dm;
-      v[11] = vtl_from_right(Pp);
-      v[12] = vtl_from_left(Pm);
-      v[13] = vtl_from_right(Un);
-      v[14] = vtl_from_left(Dm);
+      v[11] = from_right(Pp);
+      v[12] = from_left(Pm);
+      v[13] = from_right(Un);
+      v[14] = from_left(Dm);
       // values are selected, never multiplied by a zero coefficient: a stale ghost plane cannot leak a NaN
       double s = 0.0;
 #pragma unroll
@@ -483,10 +465,10 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
         // b = B v_ + dt stim (rr_kernel's expression for the constant-coefficient grids), stored for the second pass
         double stim = 0.0;
         for (int k = 0; k < az.nstim; ++k)
-          stim = fma(az.amp[k], vtl_buf_load(az.w[k] + (int64_t)z * a.plane, pbytes, out ? roff * 8u : VTL_OOB), stim);
+          stim = fma(az.amp[k], buf_load(az.w[k] + (int64_t)z * a.plane, pbytes, out ? roff * 8u : BUF_OOB), stim);
         const double b = fma(az.dt, stim, s);
         acc = fma(out ? b : 0.0, b, acc);
-        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : VTL_OOB, b);
+        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : BUF_OOB, b);
       } else if constexpr (RES) {
         // s = A x0: r = b - A x0 (the textbook form: its rounding error is ~1e-16 |b|, far below any threshold rtol |b|), z = D^-1 r
         const double rr = Bv - s;
@@ -495,11 +477,11 @@ __global__ __launch_bounds__(RY * 64, 4) void vtl_spmv_kernel(VtlArgs a_) {  // 
           acc1 = fma(rr, zz, acc1);
           acc2 = fma(rr, rr, acc2);
         }
-        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : VTL_OOB, rr);
-        vtl_buf_store(az.pnew + (int64_t)z * a.plane, pbytes, (out && az.pnew != nullptr) ? roff * 8u : VTL_OOB, zz);
+        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : BUF_OOB, rr);
+        vtl_buf_store(az.pnew + (int64_t)z * a.plane, pbytes, (out && az.pnew != nullptr) ? roff * 8u : BUF_OOB, zz);
       } else {
         acc = fma(out ? P0 : 0.0, s, acc);  // (an inactive lane's P0 is 0 anyway; s is finite)
-        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : VTL_OOB, s);
+        vtl_buf_store(az.y + (int64_t)z * a.plane, pbytes, out ? roff * 8u : BUF_OOB, s);
       }
       // roll: this plane becomes the plane below
       Pm = P0;

@@ -1,4 +1,4 @@
-"""The predicted stop of the register-row PCG (beat_pcg_predict, csrc/beat_pde.hip).
+"""The predicted stop of the register-row PCG (beat_pcg_predict, csrc/beat_pcg_scalar.h).
 
 The pass that forms p_i and sums p.Ap also sums r.Ap and Ap.Ap; the scalar step behind it predicts r_{i+1}.r_{i+1} with a proven
 error bound and, when that settles the stopping test, latches the solve so that the residual update of the last iteration is a

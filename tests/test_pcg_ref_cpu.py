@@ -126,7 +126,7 @@ def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(shape):
 
 
 def test_single_reduction_recurrence_gives_the_same_iterates():
-    """Chronopoulos & Gear's step lengths (rr_merged_next_kernel's expressions), in longdouble: the iterates of the classic loop."""
+    """Chronopoulos & Gear's step lengths (beat_pcg_merged_next's expressions), in longdouble: the iterates of the classic loop."""
     L = np.longdouble
     shape = (65, 3, 5)
     p, r = ref.problem(shape), ref.plain_reference(shape)
