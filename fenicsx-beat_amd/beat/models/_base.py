@@ -68,32 +68,31 @@ class DeviceModel:
         raise NotImplementedError(f"{self.name} is a hand-written kernel whose intermediates are not kept by name: "
                                   "use beat.models.from_ode on the model's .ode file to monitor its currents")
 
-    # ---- the reference's `fun` calling convention ---------------------------------------------
-    def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
-        """Advance ``states`` ((S,) or (S, N) NumPy) by one step on the GPU; returns a new array."""
-        from .. import _hip
+    def _stage(self, states, parameters):
+        """(context, the states as an (S, N) device array, N, whether they were (S,), host_and_device_parameters' tuple: it holds what a launch reads)."""
         from .._device import Context, StateArray
 
-        if dt is None:
-            raise TypeError("dt is required")
         ctx = Context.default()
         arr = np.asarray(states, dtype=np.float64)
-        one_d = arr.ndim == 1
         a2 = arr.reshape(arr.shape[0], -1)
         S, n = a2.shape
         if S != self.num_states:
             raise ValueError(f"{self.name} has {self.num_states} states, got {S}")
         sa = StateArray(ctx, S, n)
         sa.set(a2)
-        hp, ppn, pld = host_and_device_parameters(ctx, parameters, self.num_parameters, n)
-        _hip.check(
-            ctx.lib.beat_ode_step(ctx.handle, self.model_id, sa.ptr, n, sa.ld,
-                                  None if hp is None else hp.ctypes.data_as(C.c_void_p), self.num_parameters if (hp is not None or ppn is not None) else 0,
-                                  None if ppn is None else C.c_void_p(ppn.data_ptr()), pld, float(t), float(dt), 0, None)
-        )
+        return ctx, sa, n, arr.ndim == 1, host_and_device_parameters(ctx, parameters, self.num_parameters, n)
+
+    # ---- the reference's `fun` calling convention ---------------------------------------------
+    def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
+        """Advance ``states`` ((S,) or (S, N) NumPy) by one step on the GPU; returns a new array."""
+        from .. import _hip
+
+        if dt is None:
+            raise TypeError("dt is required")
+        ctx, sa, n, one_d, params = self._stage(states, parameters)
+        _hip.check(ctx.lib.beat_ode_step(ctx.handle, self.model_id, sa.ptr, n, sa.ld, *parameter_args(*params, self.num_parameters), float(t), float(dt), 0, None))
         out = sa.numpy()
         return out[:, 0].copy() if one_d else out
-
 
     # ---- many steps in one launch ---------------------------------------------------------------------
     def run(self, states, parameters, dt, nsteps, nbeats=1, t0=0.0, track_indices=None, save_freq=1):
@@ -101,18 +100,8 @@ class DeviceModel:
         t0 each beat, t = t0 + j*dt within it).  Returns (new_states, track) where track has shape
         (rows, len(track_indices)[, N]) or is None."""
         from .. import _hip
-        from .._device import Context, StateArray
 
-        ctx = Context.default()
-        arr = np.asarray(states, dtype=np.float64)
-        one_d = arr.ndim == 1
-        a2 = arr.reshape(arr.shape[0], -1)
-        S, n = a2.shape
-        if S != self.num_states:
-            raise ValueError(f"{self.name} has {self.num_states} states, got {S}")
-        sa = StateArray(ctx, S, n)
-        sa.set(a2)
-        hp, ppn, pld = host_and_device_parameters(ctx, parameters, self.num_parameters, n)
+        ctx, sa, n, one_d, params = self._stage(states, parameters)
         ntrack = 0 if track_indices is None else len(track_indices)
         trace, tidx = None, None
         rows = 0
@@ -121,10 +110,7 @@ class DeviceModel:
             trace = ctx.zeros(rows * ntrack * n)
             tidx = (C.c_int * ntrack)(*[int(i) for i in track_indices])
         _hip.check(
-            ctx.lib.beat_ode_run(ctx.handle, self.model_id, sa.ptr, n, sa.ld,
-                                 None if hp is None else hp.ctypes.data_as(C.c_void_p),
-                                 self.num_parameters if (hp is not None or ppn is not None) else 0,
-                                 None if ppn is None else C.c_void_p(ppn.data_ptr()), pld, float(t0), float(dt), int(nsteps),
+            ctx.lib.beat_ode_run(ctx.handle, self.model_id, sa.ptr, n, sa.ld, *parameter_args(*params, self.num_parameters), float(t0), float(dt), int(nsteps),
                                  int(nbeats), int(save_freq), tidx, ntrack,
                                  None if trace is None else C.c_void_p(trace.data_ptr()))
         )
@@ -202,3 +188,10 @@ def host_and_device_parameters(ctx, parameters, num_parameters, n):
     if p.shape != (num_parameters, n):
         raise ValueError(f"per-node parameters must have shape ({num_parameters}, {n}), got {p.shape}")
     return None, ctx.from_numpy(np.ascontiguousarray(p)), n
+
+
+def parameter_args(hp, ppn, pld, num_parameters):
+    """What ``host_and_device_parameters`` returned as the C entry points take it: (host vector | None, P -- 0 without parameters --,
+    per-node rows | None, ld).  ``ppn``: a tensor, or the pointer itself; the caller keeps it alive, the pointer does not."""
+    return (None if hp is None else hp.ctypes.data_as(C.c_void_p), num_parameters if (hp is not None or ppn is not None) else 0,
+            C.c_void_p(ppn.data_ptr()) if hasattr(ppn, "data_ptr") else ppn, int(pld))

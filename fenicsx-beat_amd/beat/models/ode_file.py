@@ -30,12 +30,13 @@ from __future__ import annotations
 
 import ast
 import copy
+import ctypes as C
 import hashlib
 from pathlib import Path
 
 import numpy as np
 
-from ._base import DeviceModel, host_and_device_parameters
+from ._base import DeviceModel, host_and_device_parameters, parameter_args
 
 _SCHEMES = ("generalized_rush_larsen", "forward_euler")
 # gotranx's own names for the same two schemes (gotranx.schemes: what its code generator is asked for)
@@ -570,8 +571,6 @@ class OdeFileModel(DeviceModel):
     def register(self) -> int:
         """The library's id for this model (beat_ode_model_register: the source is handed over once per process; the kernel is
         compiled when a step first needs it).  Raises BeatHipError where the library cannot compile at run time."""
-        import ctypes as C
-
         from .. import _hip
 
         if self._registered is None:
@@ -665,8 +664,6 @@ class OdeFileModel(DeviceModel):
         """[(the library's monitor id, number of rows)] for ``names``, one per launch of at most _hip.MAX_MONITORS rows
         (beat_ode_monitor_register: a selection's source is handed over once per process; its kernel is compiled when a launch
         first needs it).  The id is handed out once the selection's plain instance has passed ``_monitor_self_check``."""
-        import ctypes as C
-
         from .. import _hip
 
         self.register()
@@ -685,7 +682,7 @@ class OdeFileModel(DeviceModel):
     def monitor_on_device(self, ctx, names, states_ptr, n, ld, t, out_ptr, out_ld, host_params=None, per_node=None, classes=None):
         """Enqueue the monitor kernel(s) for ``names`` on a RESIDENT state array (``states_ptr``: its row 0, rows ``ld`` apart):
         row j of the selection goes to ``out_ptr`` + 8 j ``out_ld`` bytes.  Parameters: ``host_params`` (a (P,) NumPy vector), or
-        ``per_node`` = (device pointer of the (P, n) rows, their stride), or ``classes`` = (marker bytes, table, number of classes)
+        ``per_node`` = (the (P, n) device rows, tensor or pointer, their stride), or ``classes`` = (marker bytes, table, number of classes)
         as ``_DeviceODE.set_classes`` keeps them.  Does not wait."""
         row = 0
         for mid, m in self._monitor_launches(self._monitor_selection(names)):
@@ -694,21 +691,15 @@ class OdeFileModel(DeviceModel):
 
     def _monitor_call(self, ctx, mid, states_ptr, n, ld, t, out_addr, out_ld, host_params, per_node, classes):
         """beat_ode_monitor for one registered selection (see monitor_on_device for the arguments)."""
-        import ctypes as C
-
         from .. import _hip
 
         hp = None if host_params is None else np.ascontiguousarray(host_params, dtype=np.float64)
-        ppn, pld = (None, 0) if per_node is None else per_node
         mk, table, ncls = (None, None, 0) if classes is None else (C.c_void_p(classes[0].data_ptr()), C.c_void_p(classes[1].data_ptr()), int(classes[2]))
-        _hip.check(ctx.lib.beat_ode_monitor(ctx.handle, mid, states_ptr, int(n), int(ld), None if hp is None else hp.ctypes.data_as(C.c_void_p),
-                                            max(self.num_parameters, 1) if (hp is not None or ppn is not None) else 0, ppn, int(pld), table, ncls, mk,
-                                            float(t), C.c_void_p(out_addr), int(out_ld)))
+        _hip.check(ctx.lib.beat_ode_monitor(ctx.handle, mid, states_ptr, int(n), int(ld), *parameter_args(hp, *(per_node or (None, 0)), max(self.num_parameters, 1)),
+                                            table, ncls, mk, float(t), C.c_void_p(out_addr), int(out_ld)))
 
     def _monitor_staged(self, mid, m, y2, t, parameters):
         """One launch on host arrays staged through the device: (m, N)."""
-        import ctypes as C
-
         from .._device import Context, StateArray
 
         ctx = Context.default()
@@ -717,7 +708,7 @@ class OdeFileModel(DeviceModel):
         sa.set(y2)
         hp, ppn, pld = host_and_device_parameters(ctx, parameters, self.num_parameters, n)
         out = ctx.zeros(m * n)
-        self._monitor_call(ctx, mid, sa.ptr, n, sa.ld, t, out.data_ptr(), n, hp, None if ppn is None else (C.c_void_p(ppn.data_ptr()), pld), None)
+        self._monitor_call(ctx, mid, sa.ptr, n, sa.ld, t, out.data_ptr(), n, hp, None if ppn is None else (ppn, pld), None)
         return out.cpu().numpy().reshape(m, n)
 
     @staticmethod

@@ -109,7 +109,7 @@ class MonodomainSplittingSolver:
         if recorder is not None and recorder._f is not pde.state:
             return False
         ode._dev.parameters = ode.parameters
-        return ode._dev._param_args()[0] is not None  # uniform parameters (one host vector)
+        return ode._dev.routes.resolve(ode.parameters).kind == "uniform"  # (one host vector)
 
     def _batched_steps(self, steps, recorder) -> None:
         ode, pde = self.ode, self.pde
@@ -127,7 +127,7 @@ class MonodomainSplittingSolver:
         pde._set_timestep(dt)
         stims = [s for s in pde._stimuli if s.field is not None]
         rtol, atol, max_it = pde._solver_tolerances()
-        hp, npar, _, _ = dev._param_args()
+        hp, npar = dev.routes.resolve(dev.parameters).args()[:2]
         w_ptrs = (C.c_void_p * max(1, len(stims)))(*[s.field.ptr for s in stims])
         done = 0
         if not ops.small_active():

@@ -11,13 +11,16 @@ from __future__ import annotations
 import abc
 import ctypes as C
 import logging
+import os
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Any, Callable, NamedTuple
 
 import numpy as np
 
 from . import _hip, grid
-from .models._base import DeviceModel, DeviceParameters, host_and_device_parameters
+from ._param_route import ParameterRoutes
+from .models._base import DeviceModel, DeviceParameters
 from .telemetry import BaseMonitor, NullMonitor
 from .utils import local_project
 
@@ -108,6 +111,21 @@ class _CallableMonitor:
         return self._call(names, t, out=out)
 
 
+def _route_ops(ctx):
+    """What ``ParameterRoutes`` does on the device or in the library (beat/_param_route.py)."""
+    def class_table_doubles(model_id):
+        stride = C.c_int()
+        _hip.check(ctx.lib.beat_ode_class_table_doubles(model_id, C.byref(stride)))
+        return stride.value
+
+    def class_table_fill(model_id, sets, table):
+        _hip.check(ctx.lib.beat_ode_class_table_fill(ctx.handle, model_id, sets.ctypes.data_as(C.c_void_p), sets.shape[1], sets.shape[0],
+                                                     C.c_void_p(table.data_ptr())))
+
+    return SimpleNamespace(torch=ctx.torch, from_numpy=ctx.from_numpy, zeros=ctx.zeros, class_table_doubles=class_table_doubles,
+                           class_table_fill=class_table_fill, jit_available=lambda: ctx.lib.beat_ode_jit_stats(None) == 1)
+
+
 class _DeviceODE:
     """(S, N) state array in HBM advanced by a built-in model kernel."""
 
@@ -124,38 +142,17 @@ class _DeviceODE:
         self.states = StateArray(ctx, num_states, n, plane)
         self.parameters = parameters
         self.monitor = monitor
-        self._ppn = None
-        self._ppn_host = None  # what the device copy was uploaded from (None: the per-node route's cache is not current)
-        self._dp_key = None    # (id, version) of the DeviceParameters handle the cached route was derived from
-        self._per_node_args = None
-        self._sparse = None    # (uniform vector, indices of the varying rows, their (K, N) device rows) or None
-        self.classes = None    # (marker bytes on the device, class table, number of classes): see set_classes
-        self.explicit_classes = False  # the owner set the classes itself (DolfinMultiODESolver); else they follow the parameters
         self.node_map = None   # (int32 node of the PDE grid per entry, the field holding the potential): compact layout
-        self._class_host = None
+        self.routes = ParameterRoutes(model.name, model.num_parameters, model.model_id, n, _route_ops(ctx))
+
+    # How the parameters reach the kernel is decided and cached by ``routes`` alone; these answer from its current route.
+    classes = property(lambda self: self.routes.current.classes)  # (marker bytes on the device, class table, number of classes) | None
+    _sparse = property(lambda self: self.routes.current.rows)  # (uniform vector, indices of the varying rows, their (K, N) rows) | None
+    explicit_classes = property(lambda self: self.routes.explicit, lambda self, on: setattr(self.routes, "explicit", bool(on)))
 
     def set_classes(self, markers_dev, param_sets) -> None:
-        """One launch for several uniform parameter sets (beat_ode_step_classes): ``markers_dev`` = a byte per node naming
-        its set (255: none, the node is not advanced), ``param_sets`` = the sets in class order.  Calling it again with
-        the same byte row only refreshes the table, and only if a set changed (the reference hands ``fun`` the live
-        parameter arrays every step, odesolver.py:70-76)."""
-        P = np.ascontiguousarray(np.stack([np.asarray(p, dtype=np.float64) for p in param_sets]))
-        if P.ndim != 2 or P.shape[1] != self.model.num_parameters or not 1 <= P.shape[0] <= _hip.MAX_CLASSES:
-            raise ValueError(f"{self.model.name}: {P.shape[0]} parameter sets of {P.shape[1:]} values "
-                             f"(expected 1..{_hip.MAX_CLASSES} sets of {self.model.num_parameters})")
-        lib = self.ctx.lib
-        if self.classes is None or self.classes[2] != P.shape[0]:
-            stride = C.c_int()
-            _hip.check(lib.beat_ode_class_table_doubles(self.model.model_id, C.byref(stride)))
-            table = self.ctx.zeros(stride.value * P.shape[0])
-            self._class_host = None
-        else:
-            table = self.classes[1]
-        if self._class_host is None or not np.array_equal(self._class_host, P):
-            _hip.check(lib.beat_ode_class_table_fill(self.ctx.handle, self.model.model_id, P.ctypes.data_as(C.c_void_p), P.shape[1],
-                                                     P.shape[0], C.c_void_p(table.data_ptr())))
-            self._class_host = P.copy()
-        self.classes = (markers_dev, table, P.shape[0])
+        """The explicit route (ParameterRoutes.set_classes): a byte per node names one of ``param_sets``; the parameters no longer decide."""
+        self.routes.set_classes(markers_dev, param_sets)
 
     def set_initial(self, values) -> None:
         if values.ndim == 1:
@@ -164,164 +161,44 @@ class _DeviceODE:
         else:
             self.states.set(values)
 
-    def _classify(self, t):
-        """Per-node parameters (P, N) that are piecewise constant -- demos/pace_train.py:133-167 zeroes two conductances
-        in half of the cable -- are a handful of uniform parameter sets: the distinct columns become classes, a byte per
-        node names its class, and the step runs the class kernel (uniform parameters in scalar registers, no per-node
-        rows to load: 424 B/node for TP06, 896 for ToR-ORd) instead of the per-node one.  Returns (marker bytes on the
-        device, (classes, P) host array) or None when the columns are not few (a smooth gradient: per-node kernel).
-        BEAT_PARAM_CLASSES=0 turns the analysis off."""
-        import os
-
-        if os.environ.get("BEAT_PARAM_CLASSES", "1") == "0":
-            return None
-        torch = self.ctx.torch
-        varying = (t != t[:, :1]).any(dim=1)
-        n = t.shape[1]
-        if not bool(varying.any()):
-            return torch.zeros(n, dtype=torch.uint8, device=t.device), t[:, :1].T.cpu().numpy()
-        cols = t[varying]
-        stride = max(1, n // 65536)  # a sample first: a smooth field shows at once
-        if torch.unique(cols[:, ::stride], dim=1).shape[1] > _hip.MAX_CLASSES:
-            return None
-        uniq, inv = torch.unique(cols, dim=1, return_inverse=True)
-        if uniq.shape[1] > _hip.MAX_CLASSES:
-            return None
-        first = torch.full((uniq.shape[1],), n, dtype=torch.int64, device=t.device)
-        first.scatter_reduce_(0, inv, torch.arange(n, device=t.device), reduce="amin")
-        return inv.to(torch.uint8), t[:, first].T.contiguous().cpu().numpy()
-
-    def _per_node_or_classes(self, tensor, num_rows):
-        """(host params, P, device rows, ld) for per-node parameters held in ``tensor``: the class route if they allow it,
-        else -- when at most sixteen ROWS vary over the nodes (smooth gradients in a few conductances; four without run-time
-        compilation) -- those rows alone
-        next to the uniform vector (``self._sparse``: beat_ode_step_rows reads 8 B per varying row and node instead of 8 P),
-        else all P rows."""
-        per_node = (None, num_rows, C.c_void_p(tensor.data_ptr()), self.n)
-        self._sparse = None
-        found = self._classify(tensor)
-        if found is not None:
-            self.set_classes(found[0], list(found[1]))
-            self._per_node_args = per_node  # for the caller the class kernel does not serve (a mirror of another row than V)
-            return None, num_rows, None, 0
-        self.classes = None
-        import os
-
-        # (a model registered as source has no compiled sparse-row instance: all its rows are read)
-        if os.environ.get("BEAT_PARAM_SPARSE", "1") != "0" and tensor.shape[1] == self.n and self.model.model_id < _hip.CUSTOM_MODEL_BASE:
-            varying = (tensor != tensor[:, :1]).any(dim=1)
-            idx = varying.nonzero().flatten().cpu().numpy().astype(np.int32)
-            # (up to 16 varying rows on a kernel instance compiled for their indices, 4 where that cannot be had)
-            jit = os.environ.get("BEAT_JIT", "1") != "0" and self.ctx.lib.beat_ode_jit_stats(None) == 1
-            if 1 <= len(idx) <= (_hip.MAX_SPARSE_ROWS if jit else _hip.MAX_SPARSE_ROWS_RT):
-                rows = tensor[varying].contiguous()  # (K, N): the only parameter data a step reads from memory
-                uniform = np.ascontiguousarray(tensor[:, 0].cpu().numpy(), dtype=np.float64)
-                self._sparse = (uniform, np.ascontiguousarray(idx), rows)
-        return per_node
-
-    def _forget_routes(self) -> None:
-        """The parameters are no per-node rows (any more): no classes, and neither cached route may be taken for current
-        again -- a classified (P, N) array, then a vector, then the same array must classify again (the vector branch
-        cleared the classes the cached arguments rely on)."""
-        self.classes = None
-        self._sparse = None
-        self._ppn_host = None
-        self._dp_key = None
-
-    def _param_args(self):
-        p = self.parameters
-        if p is None:
-            self._forget_routes()
-            return None, 0, None, 0
-        if isinstance(p, DeviceParameters):  # resident handle: nothing to check or move per step
-            _, dev, ld = host_and_device_parameters(self.ctx, p, self.model.num_parameters, self.n)
-            key = (id(p), p.version)
-            if self._dp_key != key:  # new values: look at them once
-                self._ppn_host = None  # (the classes now follow THIS handle: the NumPy route's cache is stale)
-                self._dp_args = self._per_node_or_classes(dev, p.shape[0])
-                self._dp_key = key
-            return self._dp_args
-        p = np.asarray(p, dtype=np.float64)
-        if p.ndim == 1:
-            hp = np.ascontiguousarray(p)
-            self._keep = hp
-            self._forget_routes()
-            return hp.ctypes.data_as(C.c_void_p), len(hp), None, 0
-        # per-node NumPy parameters: the reference hands the live array to ``fun`` every step (odesolver.py:70-76),
-        # so any in-place edit must reach the kernel.  Exact comparison with the copy that was uploaded (one host
-        # pass over (P, N) per step; pass a DeviceParameters handle to avoid it on large grids).
-        if self._ppn is None or self._ppn_host is None or self._ppn_host.shape != p.shape or not np.array_equal(self._ppn_host, p):
-            _, self._ppn, _ = host_and_device_parameters(self.ctx, p, self.model.num_parameters, self.n)
-            self._ppn_host = p.copy()
-            self._dp_key = None  # (see above)
-            self._ppn_args = self._per_node_or_classes(self._ppn, p.shape[0])
-        return self._ppn_args
-
     def monitor_rows(self, names, t, out_ptr, out_ld) -> None:
         """The monitor kernel of a generated model on the resident states, with the parameters as they are now and by the route the
         next step would take them (uniform vector, classes; per-node rows are read whole -- a generated model has no sparse-row
         instance).  The caller has brought the potential row up to date.  Does not wait."""
-        hp, _, ppn, pld = (None, 0, None, 0) if self.explicit_classes else self._param_args()
-        args = dict(host_params=None, per_node=None, classes=None)
-        if self.classes is not None:
-            args["classes"] = self.classes
-        elif ppn is not None:
-            args["per_node"] = (ppn, pld)
-        elif hp is not None:
-            args["host_params"] = self._keep  # (the vector _param_args handed out as `hp`)
-        else:
+        route = self.routes.resolve(self.parameters)
+        if route.kind == "none":
             raise ValueError(f"{self.model.name}: monitored values need the parameters")
-        self.model.monitor_on_device(self.ctx, names, self.states.ptr, self.n, self.states.ld, t, out_ptr, out_ld, **args)
+        self.model.monitor_on_device(self.ctx, names, self.states.ptr, self.n, self.states.ld, t, out_ptr, out_ld, **route.monitor_kwargs())
 
     def step(self, t0, dt, v_index=0, v_copy=None, pending_ops=None, v_row=None):
         """``pending_ops``: diffusion operators whose last solve deferred its update of ``v_row`` (row v_index of
         these states): the kernel adds it while loading the potential (beat_ode_step_pending)."""
-        # (classes set explicitly -- one model for several markers -- stay; otherwise the parameters decide the route)
-        hp, npar, ppn, pld = (None, 0, None, 0) if self.explicit_classes else self._param_args()
-        use_classes = self.classes is not None
-        if use_classes and not self.explicit_classes and v_copy is not None and self.model.v_name \
-                and int(v_index) != self.model.state_index(self.model.v_name):
+        route = self.routes.resolve(self.parameters)
+        model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
+        if route.kind == "classes" and route.fallback is not None and v_copy is not None and self.model.v_name and int(v_index) != model_v:
             # the class kernel mirrors the model's own potential row only: per-node parameters that were routed to classes
             # go back to the per-node kernel, which mirrors any row (what the reference's v_index means, odesolver.py:135-146)
-            use_classes = False
-            hp, npar, ppn, pld = self._per_node_args
-        model_v = self.model.state_index(self.model.v_name) if self.model.v_name else -1
+            route = route.fallback
         # (operator, ring, field stride, count) of what the launch applies, as the pending-update entry points take them; count -1:
         # the launch is enqueued BEHIND a solve that is still open (beat_ode_step_pending)
         pend_args = (None, None, 0, 0) if pending_ops is None else pending_ops.deferred.claim(
-            v_row, int(v_index) == model_v, None if self.node_map is None else self.node_map[1], use_classes)
-        pend = None if pend_args[0] is None else pend_args
-        behind = pend_args[3] < 0
+            v_row, int(v_index) == model_v, None if self.node_map is None else self.node_map[1], route.kind == "classes")
+        lib, states = self.ctx.lib, (self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld)
+        when = (float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr)
         with self.monitor.track_time("ode_total_step"):
-            with self.monitor.track_time("ode_function_call"):
-                if use_classes:
-                    mk, table, ncls = self.classes
-                    if int(v_index) != model_v and pend is not None:
+            with self.monitor.track_time("ode_function_call"):  # the one place that maps a route's kind to its entry point
+                if route.kind == "classes":
+                    if int(v_index) != model_v and pend_args[0] is not None:
                         raise ValueError("a pending update needs the model's own potential row")
                     nmap, vfield = (None, None) if self.node_map is None else (C.c_void_p(self.node_map[0].data_ptr()), self.node_map[1].ptr)
-                    _hip.check(self.ctx.lib.beat_ode_step_classes(
-                        self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, C.c_void_p(table.data_ptr()),
-                        ncls, C.c_void_p(mk.data_ptr()), float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr,
-                        nmap, vfield, *pend_args))
-                elif self._sparse is not None and ppn is not None and not self.explicit_classes:
-                    uni, idx, rows = self._sparse
-                    _hip.check(self.ctx.lib.beat_ode_step_rows(
-                        self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, uni.ctypes.data_as(C.c_void_p),
-                        len(uni), idx.ctypes.data_as(C.c_void_p), len(idx), C.c_void_p(rows.data_ptr()), self.n, float(t0), float(dt),
-                        int(v_index), None if v_copy is None else v_copy.ptr, *pend_args))
-                elif pend is not None:
-                    _hip.check(
-                        self.ctx.lib.beat_ode_step_pending(
-                            self.ctx.handle, self.model.model_id, self.states.ptr, self.n, self.states.ld, hp, npar, ppn,
-                            pld, float(t0), float(dt), int(v_index), None if v_copy is None else v_copy.ptr, *pend_args)
-                    )
+                    _hip.check(lib.beat_ode_step_classes(*states, *route.args(), *when, nmap, vfield, *pend_args))
+                elif route.kind == "rows":
+                    _hip.check(lib.beat_ode_step_rows(*states, *route.args(), *when, *pend_args))
+                elif pend_args[0] is not None:
+                    _hip.check(lib.beat_ode_step_pending(*states, *route.args(), *when, *pend_args))
                 else:
-                    _hip.check(
-                        self.ctx.lib.beat_ode_step(self.ctx.handle, self.model.model_id, self.states.ptr, self.n,
-                                                   self.states.ld, hp, npar, ppn, pld, float(t0), float(dt), int(v_index),
-                                                   None if v_copy is None else v_copy.ptr)
-                    )
-            if behind:  # the call has finished the solve it was enqueued behind: take its record
+                    _hip.check(lib.beat_ode_step(*states, *route.args(), *when))
+            if pend_args[3] < 0:  # the call has finished the solve it was enqueued behind: take its record
                 pending_ops.deferred.finished_behind()
             with self.monitor.track_time("ode_state_update"):
                 pass  # updated in place by the kernel
@@ -591,8 +468,6 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         nodes live in ONE (S, N) state array with a byte per node naming the node's parameter set, and a step is one
         kernel launch (beat_ode_step_classes) instead of one per marker plus a scatter and a gather of the potential
         (BEAT_MULTI_ONE_LAUNCH=0 keeps the per-marker arrays: the reference's literal data layout)."""
-        import os
-
         if os.environ.get("BEAT_MULTI_ONE_LAUNCH", "1") == "0":
             return False
         ms = self._marker_values
@@ -607,8 +482,6 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         )
 
     def _setup_one_launch(self, marker_arr) -> None:
-        import os
-
         ctx, ms = self._ctx, self._marker_values
         model, S, vi = self.fun[ms[0]], int(self.num_states[ms[0]]), int(self.v_index[ms[0]])
         n = marker_arr.size
@@ -694,7 +567,6 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
                 nodes = ctx.from_numpy(np.nonzero(self._inds[marker])[0].astype(np.int64))
                 self._v_row.data.index_copy_(0, nodes, rows[vi].index_select(0, self._idx_dev[marker]))
         self._cls_dev = ctx.from_numpy(cls)
-        self._dev.explicit_classes = True
         self._dev.set_classes(self._cls_dev, [self.parameters[m] for m in ms])
         self._odes = {}
 
@@ -726,6 +598,14 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         if self._all_states_equal_size:
             self._full_values = np.zeros((ns[0], self.markers.x.array.size))
 
+    def _each_v_row(self, scatter: bool, field) -> None:
+        """Per-marker arrays: every marker's potential row is scattered to ``field`` (``scatter``) or gathered from it."""
+        move = self._ctx.lib.beat_scatter if scatter else self._ctx.lib.beat_gather  # (both: destination, source, indices, count)
+        for marker in self._marker_values:
+            row = self._odes[marker].states.row_field(self.v_index[marker])
+            dst, src = (field, row) if scatter else (row, field)
+            _hip.check(move(self._ctx.handle, dst.ptr, src.ptr, C.c_void_p(self._idx_dev[marker].data_ptr()), row.n))
+
     def to_dolfin(self) -> None:
         if self._marked:
             if self.v_ode._alias is self._v_row:
@@ -734,11 +614,7 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
             self._masked_copy(self.v_ode.writable_field(overwrite_all=False), self._v_row)
             self.v_ode._touch()
         elif self.on_device:
-            dst = self.v_ode.writable_field(overwrite_all=False)
-            for marker in self._marker_values:
-                row = self._odes[marker].states.row_field(self.v_index[marker])
-                _hip.check(self._ctx.lib.beat_scatter(self._ctx.handle, dst.ptr, row.ptr,
-                                                      C.c_void_p(self._idx_dev[marker].data_ptr()), row.n))
+            self._each_v_row(True, self.v_ode.writable_field(overwrite_all=False))
             self.v_ode._touch()
         else:
             arr = np.asarray(self.v_ode.x.array).copy()
@@ -751,20 +627,14 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         if self._marked:
             self._sync_v()
             return self._masked_copy(dst, self._v_row)
-        for marker in self._marker_values:
-            row = self._odes[marker].states.row_field(self.v_index[marker])
-            _hip.check(self._ctx.lib.beat_scatter(self._ctx.handle, dst.ptr, row.ptr,
-                                                  C.c_void_p(self._idx_dev[marker].data_ptr()), row.n))
+        self._each_v_row(True, dst)
 
     def gather_v(self, src) -> None:
         """Field ``src`` -> the potential rows of every marker's states (fused split step)."""
         if self._marked:
             self._release_aliases()
             return self._masked_copy(self._v_row, src)
-        for marker in self._marker_values:
-            row = self._odes[marker].states.row_field(self.v_index[marker])
-            _hip.check(self._ctx.lib.beat_gather(self._ctx.handle, row.ptr, src.ptr,
-                                                 C.c_void_p(self._idx_dev[marker].data_ptr()), row.n))
+        self._each_v_row(False, src)
 
     def from_dolfin(self) -> None:
         if self._marked:
@@ -773,11 +643,7 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
             self._release_aliases()
             self._masked_copy(self._v_row, self.v_ode.field)
         elif self.on_device:
-            src = self.v_ode.field
-            for marker in self._marker_values:
-                row = self._odes[marker].states.row_field(self.v_index[marker])
-                _hip.check(self._ctx.lib.beat_gather(self._ctx.handle, row.ptr, src.ptr,
-                                                     C.c_void_p(self._idx_dev[marker].data_ptr()), row.n))
+            self._each_v_row(False, self.v_ode.field)
         else:
             arr = np.asarray(self.v_ode.x.array)
             for marker in self._marker_values:

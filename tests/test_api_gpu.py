@@ -1057,6 +1057,68 @@ def test_piecewise_constant_per_node_parameters_run_as_classes():
     ref = ionic.tp06_generalized_rush_larsen(ref, 0.14, 0.02, Pg)
     assert (np.abs(np.asarray(ode_g.values) - ref) / np.maximum(np.abs(ref), 1e-3)).max() < 1e-10
 
+
+def test_one_solver_through_every_parameter_route_equals_fresh_solvers(monkeypatch):
+    """One TP06 solver of 640 nodes (two and a half 256-node tiles) whose parameters change kind every two steps -- vector, two-column
+    array (the class boundary inside a wavefront, at node 430), vector, the same array, an array with two smooth rows, a resident
+    handle of it, ``set_row`` on the handle: after each pair of steps the states equal, bit for bit, those of a fresh solver started
+    from the states before the pair with the same parameters (no route outlives the input it was derived from), and ``classes`` /
+    ``_sparse`` read as tests/test_param_route_cpu.py says the kinds are.  BEAT_JIT=0: the shipped kernels, nothing is compiled."""
+    import beat
+    from beat import grid as g
+    from beat.models import tp06
+    from beat.odesolver import DeviceParameters
+
+    monkeypatch.setenv("BEAT_JIT", "0")
+    mesh = g.create_box(g.COMM_WORLD, [np.zeros(3), np.array([3.9, 0.3, 0.3])], [39, 3, 3])
+    V = g.functionspace(mesh, ("P", 1))
+    n = V.dofmap.index_map.size_local
+    assert n == 640
+    vi, dt = tp06.state_index("V"), 0.02
+    P0 = tp06.init_parameter_values(stim_amplitude=0.0)
+    A = np.repeat(P0[:, None], n, axis=1)
+    A[tp06.parameter_index("g_Kr"), 430:] = 0.0
+    A[tp06.parameter_index("g_Ks"), 430:] *= 0.5
+    G = np.repeat(P0[:, None], n, axis=1)
+    G[tp06.parameter_index("g_Na")] *= np.linspace(0.8, 1.2, n)
+    G[tp06.parameter_index("g_CaL")] *= 1.0 + 0.2 * np.sin(np.linspace(0.0, 3.0, n))
+    two = sorted([tp06.parameter_index("g_Na"), tp06.parameter_index("g_CaL")])
+    S0 = np.repeat(tp06.init_state_values()[:, None], n, axis=1)
+    S0[vi] = np.random.default_rng(5).uniform(-90.0, 30.0, n)
+
+    def solver(states, parameters):
+        return beat.odesolver.DolfinODESolver(v_ode=g.Function(V), v_pde=g.Function(V), fun=tp06.generalized_rush_larsen,
+                                              init_states=states, parameters=parameters, num_states=19, v_index=vi)
+
+    def kind(dev):
+        return (None if dev.classes is None else dev.classes[2]), (None if dev._sparse is None else sorted(dev._sparse[1].tolist()))
+
+    ode = solver(S0, P0)
+    handle = DeviceParameters(G)
+
+    def more_rows():
+        handle.set_row(tp06.parameter_index("g_to"), P0[tp06.parameter_index("g_to")] * np.linspace(1.0, 0.7, n))
+        return handle
+
+    stages = [("vector", lambda: P0, (None, None)), ("two columns", lambda: A, (2, None)), ("vector again", lambda: P0.copy(), (None, None)),
+              ("the same array", lambda: A, (2, None)), ("two smooth rows", lambda: G, (None, two)), ("handle", lambda: handle, (None, two)),
+              ("set_row", more_rows, (None, sorted(two + [tp06.parameter_index("g_to")])))]
+    for k, (what, parameters, want) in enumerate(stages):
+        before = np.asarray(ode.values).copy()
+        ode.parameters = parameters()
+        for j in range(2):
+            ode.step(dt * (2 * k + j), dt)
+        assert kind(ode._dev) == want, what
+        p = ode.parameters
+        other = solver(before, p.numpy() if isinstance(p, DeviceParameters) else np.array(p))
+        for j in range(2):
+            other.step(dt * (2 * k + j), dt)
+        assert kind(other._dev) == want, what
+        got = np.asarray(ode.values)
+        assert np.isfinite(got).all() and not np.array_equal(got, before)
+        np.testing.assert_array_equal(got, np.asarray(other.values), err_msg=what)
+
+
 def test_split_step_with_a_smooth_per_node_parameter_runs_on_sparse_rows():
     """A smooth gradient in one conductance over a slab, through the public API and the fused split step (the ionic kernel
     applies the previous solve's pending update): the sparse-rows route (one parameter row on the device) against all 53
