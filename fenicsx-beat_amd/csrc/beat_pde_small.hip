@@ -254,6 +254,12 @@ int small_margin(const beat_pde* pde) { return (int)(pde->g.plane + pde->g.nx + 
 // Grids the one-workgroup solve takes: constant coefficients, Jacobi, both z faces physical, at most 16 nodes per
 // thread (their r, increment and A p in registers) and the search direction + tables within the 160 KB of LDS.  BEAT_SMALL=0 switches it off for
 // the process, beat_pde_set_small_grid_solve for one operator.
+// Not taken: a box with an axis of one node in FRONT of a longer one (nx = 1 with more than one node, ny = 1 with nz > 1).  The
+// kernel reaches a neighbour through ONE linear offset ox + nx oy + plane oz into the flat vector and relies on the coefficient of
+// a point outside the box being zero; a collapsed axis is 'interior' (axis_type), under tables of a higher dimension its
+// coefficients are not zero, and with nx = 1 the offset of (1, 0, 0) is that of (0, 1, 0) -- a node of the box.  A trailing
+// collapsed axis only reaches the zero margins, and tables of the grid's own dimension have zero coefficients there, so no grid
+// the mesh layer builds is declined; the multi-launch kernels, which index per axis, solve the others.
 bool beat_small_available(const beat_pde* pde) {
   static const bool enabled = [] {
     const char* e = std::getenv("BEAT_SMALL");
@@ -262,6 +268,7 @@ bool beat_small_available(const beat_pde* pde) {
   if (!enabled || !pde->small_enabled || pde->var || pde->pc_ncoef != 1) return false;
   if (!pde->g.z_lo_phys || !pde->g.z_hi_phys) return false;
   if (pde->n > (int64_t)SMALL_MAX_PER_THREAD * SMALL_THREADS) return false;
+  if ((pde->g.nx == 1 && pde->n > 1) || (pde->g.ny == 1 && pde->g.nz > 1)) return false;
   return small_lds_bytes(pde, small_margin(pde)) <= (size_t)150 * 1024;
 }
 

@@ -429,8 +429,10 @@ int beat_pde_guess_history(const beat_pde* pde, double** dev_d, double** dev_e, 
  * what bench.py charges the ionic kernel for. */
 int beat_pde_guess_traffic(const beat_pde* pde, int* host_out);
 
-/* Small grids (constant coefficients, Jacobi, undivided, <= 8192 nodes -- the reference's own CPU-sized cases, e.g.
- * the Niederer slab at dx = 0.5 mm): beat_pde_solve[_ex] runs the whole solve -- right-hand side, every iteration,
+/* Small grids (constant coefficients, Jacobi, undivided, <= 8192 nodes and a search direction that fits the LDS -- the
+ * reference's own CPU-sized cases, e.g. the Niederer slab at dx = 0.5 mm; not a box whose x axis has one node while
+ * another has more, or whose y axis has one node while z has more: no mesh of this package is one, and
+ * beat_pde_solve solves it with the multi-launch kernels): beat_pde_solve[_ex] runs the whole solve -- right-hand side, every iteration,
  * update of dev_x, bookkeeping of the initial guess -- in one launch of one workgroup (search direction in LDS, dot
  * products as block reductions), because a multi-launch iteration there is nothing but launch latency
  * (demos/niederer_benchmark.py: 0.38 -> 0.15 ms per split step).  Same iteration and stopping test, different

@@ -1,6 +1,7 @@
-"""Host reference of the production diffusion solve, iterate by iterate, and the table of cases the register-row kernels
-(csrc/beat_pde_rr.hip) are held to it on (tests/test_rr_iterates_gpu.py runs them, tests/test_pcg_ref_cpu.py checks the
-reference and the cases themselves).
+"""Host reference of the production diffusion solve, iterate by iterate, and the tables of cases the register-row kernels
+(csrc/beat_pde_rr.hip; SHAPES, tests/test_rr_iterates_gpu.py runs them) and the one-launch solve of small grids
+(csrc/beat_pde_small.hip; SMALL_SHAPES, tests/test_small_iterates_gpu.py) are held to it on; tests/test_pcg_ref_cpu.py checks the
+reference and the cases themselves.
 
 pcg_iterates is the textbook Jacobi-PCG of oracle/fem.pcg_jacobi without a stopping test, in np.longdouble (64-bit mantissa) or
 np.float64; the matrices are the assembled P1 matrices of oracle/fem.  The distance between the two precisions, per case and per
@@ -46,9 +47,72 @@ SHAPES = {
     (64, 1, 1): 1,      # one row
     (65, 1, 1): 1,
 }
+# The one-launch solve (pcg_small_kernel<M> of csrc/beat_pde_small.hip: 512 threads, thread t owns nodes t, t + 512, ...; M = 2, 4,
+# 6, 8, 10, 12 or 16 register slots per thread; the search direction in LDS between two zero margins of about a plane).  Kept apart
+# from SHAPES, which drives every child process of the register-row test.
+SMALL_SHAPES = {
+    (128, 2, 2): 3,     # <2>: 512 nodes, one per thread, slot j = 1 empty in every thread
+    (3, 3, 57): 3,      # <2>: 513 nodes, one thread owns two
+    (5, 5, 41): 3,      # <4>: 1025 nodes, the 2 -> 4 switch
+    (64, 32, 1): 2,     # <4> full, one plane (a margin of about n)
+    (43, 9, 7): 3,      # <6>
+    (16, 16, 16): 3,    # <8> full
+    (41, 15, 7): 3,     # <10>: the Niederer slab at dx = 0.5 mm, which the kernel was written for
+    (129, 7, 6): 3,     # <12>
+    (130, 6, 9): 3,     # <16>: 7020 nodes, slots 14 and 15 empty in every thread
+    (32, 16, 16): 3,    # <16> full: the size limit
+    (2, 2, 2048): 3,    # <16> full, the smallest plane
+    (64, 94, 1): 2,     # the largest LDS request taken (SMALL_LDS_LIMIT) ...
+    (64, 95, 1): 2,     # ... and one row more: not taken
+    (23, 1, 1): 1,      # fewer nodes than one wave
+    (1, 1, 7): 3,       # an axis of one node IN FRONT of a longer one under tables of higher dimension: the flat LDS index of its
+    (1, 5, 4): 3,       # neighbours (which are outside the box, with 'interior' coefficients that are not zero) is that of a node
+    (6, 1, 5): 3,       # in the box, so the one-launch solve declines these (small_declines_collapsed) and the multi-launch
+    (1, 9, 1): 3,       # kernels solve them
+}
+SMALL_GUESS_SHAPES = ((41, 15, 7), (129, 7, 6), (64, 32, 1), (32, 16, 16))
+SMALL_THREADS, SMALL_MAX_PER_THREAD, SMALL_TABW, SMALL_LDS_LIMIT = 512, 16, 16, 150 * 1024
 CHUNK_SHAPES = ((130, 6, 9), (129, 7, 6), (63, 5, 4), (1, 1, 7))  # every z-chunk length BEAT_RR_BLOCKS can ask for
 GUESS_SHAPES = ((65, 3, 5), (129, 7, 6), (130, 6, 9), (257, 5, 1))
 SEED_SHIFT: dict = {}  # shape -> added to its seed, should a seed put a stop within 1e-6 of its threshold (test_pcg_ref_cpu)
+
+
+def all_shapes() -> list:
+    """SHAPES, then what SMALL_SHAPES adds to them."""
+    return list(SHAPES) + [s for s in SMALL_SHAPES if s not in SHAPES]
+
+
+def dim_of(shape) -> int:
+    """The table dimension of a shape of either table (test_pcg_ref_cpu: a shape in both has one dimension)."""
+    shape = tuple(shape)
+    return SHAPES[shape] if shape in SHAPES else SMALL_SHAPES[shape]
+
+
+def small_lds_bytes(shape) -> int:
+    """The dynamic LDS the one-launch solve asks for (small_lds_bytes and small_margin of csrc/beat_pde_small.hip, written out):
+    two (27, TABW) tables, 6 x 8 reduction partials, 32 slots of 1 / diag, and n doubles between two margins of plane + nx + 1
+    rounded up to 8."""
+    nx, ny, nz = shape
+    margin = (nx * ny + nx + 1 + 7) // 8 * 8
+    return 8 * (2 * 27 * SMALL_TABW + 6 * (SMALL_THREADS // 64) + 32 + nx * ny * nz + 2 * margin)
+
+
+def small_declines_collapsed(shape) -> bool:
+    """beat_small_available's rule for an axis of one node in front of a longer one."""
+    nx, ny, nz = shape
+    return (nx == 1 and nx * ny * nz > 1) or (ny == 1 and nz > 1)
+
+
+def small_takes(shape) -> bool:
+    """Whether beat_small_available takes a constant-coefficient Jacobi operator of this shape on one slab."""
+    n = int(np.prod(shape))
+    return n <= SMALL_THREADS * SMALL_MAX_PER_THREAD and small_lds_bytes(shape) <= SMALL_LDS_LIMIT and not small_declines_collapsed(shape)
+
+
+def small_instance(shape) -> int:
+    """M of the pcg_small_kernel<M> beat_small_launch picks."""
+    per_thread = -(-int(np.prod(shape)) // SMALL_THREADS)
+    return next(m for m in (2, 4, 6, 8, 10, 12, 16) if per_thread <= m)
 
 
 def shape_key(shape) -> str:
@@ -155,7 +219,7 @@ def assembled(shape):
     """(Mass, K, stimulus weights) assembled on the whole mesh.  An axis of one node under tables of higher dimension (the
     degenerate boxes) is what the kernels make of it: the node is 'interior' along that axis and its neighbours there are not in
     the box -- the principal submatrix, on the centre nodes, of the matrices of a mesh with three nodes along that axis."""
-    dim = SHAPES[shape]
+    dim = dim_of(shape)
     assert all(s == 1 for s in shape[dim:])
     nodes = shape[:dim]
     mesh_nodes = tuple(3 if m == 1 else m for m in nodes)
@@ -177,7 +241,7 @@ def problem(shape) -> Problem:
     shape = tuple(int(s) for s in shape)
     if shape in _problems:
         return _problems[shape]
-    dim = SHAPES[shape]
+    dim = dim_of(shape)
     mt, kt = tables(dim)
     mass, stiff = expand(mt, shape), expand(kt, shape)
     assert np.array_equal(mass.indices, stiff.indices) and np.array_equal(mass.indptr, stiff.indptr)

@@ -899,7 +899,7 @@ def test_one_launch_solve_equals_the_multi_launch_solve(hip_ctx, nn):
     same operator: a sequence of solves with a stimulus and the extrapolated guess -- same iteration counts, solutions
     equal to rounding (the dot products are summed in another order), same recorded history; a solve cut short by
     max_it reports -3 with the same iterate; an atol-dominated stopping test reports reason 3; 8192 nodes is the
-    largest grid taken (8 per thread), one more node goes to the multi-launch path."""
+    largest grid taken (16 per thread), one more node goes to the multi-launch path."""
     import ctypes as C
 
     from beat import _hip, _stencil
@@ -949,14 +949,16 @@ def test_one_launch_solve_equals_the_multi_launch_solve(hip_ctx, nn):
 
 def test_one_launch_solve_size_limit(hip_ctx):
     """8192 nodes are solved in one launch, 8193 are not (observable: a deferring solve leaves its update pending only
-    on the multi-launch path)."""
+    on the multi-launch path).  The row of 8193 nodes is turned away by its LDS request (a 1-D grid needs about 5 n doubles:
+    8192 x 1 x 1 would be, too); 2 x 2 x 2048 and 2 x 2 x 2049, whose LDS request is small, meet the node count itself."""
     from beat import _stencil
     from beat._engine import HipOps
 
-    for nn, one_launch in (((32, 16, 16), True), ((8193, 1, 1), False)):
+    for nn, one_launch in (((32, 16, 16), True), ((8193, 1, 1), False), ((2, 2, 2048), True), ((2, 2, 2049), False)):
         dim = 3 if nn[1] > 1 else 1
         ops = HipOps(hip_ctx, nn, True, True, *_stencil.stencil_tables(dim, (0.1,) * dim, 1e-3))
         ops.set_small(True)
+        assert ops.small_active() == one_launch, nn
         ops.set_timestep(0.01, 0.5, 0.05)
         fv, fx = ops.new_field(), ops.new_field()
         fv.set(-85.0 + 50.0 * np.exp(-((np.arange(int(np.prod(nn))) % nn[0] - 5.0) ** 2) / 9.0))

@@ -1,5 +1,5 @@
-"""The host PCG of tests/_pcg_ref.py held to account, and the conditions its cases must meet for tests/test_rr_iterates_gpu.py to
-mean what it says: the reference converges to a direct solve and counts like oracle/fem.pcg_jacobi, no stop is a near tie (so
+"""The host PCG of tests/_pcg_ref.py held to account, and the conditions its cases must meet for tests/test_rr_iterates_gpu.py and
+tests/test_small_iterates_gpu.py to mean what they say: the reference converges to a direct solve and counts like oracle/fem.pcg_jacobi, no stop is a near tie (so
 the device's iteration count can be asked to EQUAL the host's), every cut happens while the iterate still moves, and every
 bound is positive."""
 import numpy as np
@@ -9,7 +9,8 @@ import scipy.sparse.linalg as spla
 import _pcg_ref as ref
 from oracle import fem
 
-SHAPES = list(ref.SHAPES)
+SHAPES = ref.all_shapes()  # the register-row cases, then what the one-launch cases add
+GUESS_SHAPES = list(ref.GUESS_SHAPES) + [s for s in ref.SMALL_GUESS_SHAPES if s not in ref.GUESS_SHAPES]
 
 
 def test_longdouble_has_a_64_bit_mantissa():
@@ -18,12 +19,64 @@ def test_longdouble_has_a_64_bit_mantissa():
 
 def test_case_table_is_consistent():
     assert set(ref.CHUNK_SHAPES) <= set(ref.SHAPES) and set(ref.GUESS_SHAPES) <= set(ref.SHAPES)
-    assert len({ref.seed_of(s) for s in ref.SHAPES}) == len(ref.SHAPES)
-    assert max(int(np.prod(s)) for s in ref.SHAPES) <= 8192  # a few thousand nodes: where the index arithmetic branches, not the workload
-    for s in ref.SHAPES:
+    assert set(ref.SMALL_GUESS_SHAPES) <= set(ref.SMALL_SHAPES)
+    assert all(ref.SHAPES[s] == ref.SMALL_SHAPES[s] for s in set(ref.SHAPES) & set(ref.SMALL_SHAPES))
+    assert len(SHAPES) == len(set(SHAPES)) == len(set(ref.SHAPES) | set(ref.SMALL_SHAPES))
+    assert len({ref.seed_of(s) for s in SHAPES}) == len(SHAPES)
+    assert max(int(np.prod(s)) for s in SHAPES) <= 8192  # a few thousand nodes: where the index arithmetic branches, not the workload
+    for s in SHAPES:
         v = ref.field(s)
         assert abs(v.mean()) < 1e-12 and 0.1 < np.abs(v).max() < 10.0
         assert np.array_equal(v, ref.field(s))  # fixed seeds
+
+
+def test_one_launch_cases_aim_at_what_they_say():
+    """The sizes of SMALL_SHAPES against the kernel's constants, its LDS request by small_lds_bytes / small_margin of
+    csrc/beat_pde_small.hip written out: every template instance is launched, by a full and by a partly empty register array where
+    there are both, and the LDS limit is met from both sides."""
+    assert ref.SMALL_THREADS * ref.SMALL_MAX_PER_THREAD == 8192 and ref.SMALL_LDS_LIMIT == 153_600
+
+    def lds(shape):  # tables A and B, 6 x 8 partials, 1 / diag, margin + n + margin
+        nx, ny, nz = shape
+        margin = -(-(nx * ny + nx + 1) // 8) * 8
+        return 8 * (2 * 27 * 16 + 6 * 8 + 32 + nx * ny * nz + 2 * margin)
+
+    assert all(ref.small_lds_bytes(s) == lds(s) for s in ref.SMALL_SHAPES)
+    assert lds((64, 94, 1)) == 153_088 and lds((64, 95, 1)) == 154_624
+    assert ref.small_takes((64, 94, 1)) and not ref.small_takes((64, 95, 1)) and int(np.prod((64, 95, 1))) <= 8192
+    assert max(lds(s) for s in ref.SMALL_SHAPES if ref.small_takes(s)) == lds((64, 94, 1))
+    taken = [s for s in ref.SMALL_SHAPES if ref.small_takes(s)]
+    assert {ref.small_instance(s) for s in taken} == {2, 4, 6, 8, 10, 12, 16}
+    nodes = {s: int(np.prod(s)) for s in ref.SMALL_SHAPES}
+    assert nodes[(128, 2, 2)] == 512 and nodes[(3, 3, 57)] == 513 and nodes[(5, 5, 41)] == 1025 and ref.small_instance((5, 5, 41)) == 4
+    assert nodes[(64, 32, 1)] == 4 * 512 and nodes[(16, 16, 16)] == 8 * 512 and nodes[(32, 16, 16)] == nodes[(2, 2, 2048)] == 8192
+    assert ref.small_instance((41, 15, 7)) == 10 and ref.small_instance((129, 7, 6)) == 12 and ref.small_instance((43, 9, 7)) == 6
+    assert ref.small_instance((130, 6, 9)) == 16 and nodes[(130, 6, 9)] <= 14 * 512  # slots 14 and 15 empty in every thread
+    assert not ref.small_takes((2, 2, 2049)) and ref.small_lds_bytes((2, 2, 2049)) < ref.SMALL_LDS_LIMIT // 2  # the node count alone
+    assert sorted(s for s in ref.SMALL_SHAPES if not ref.small_takes(s)) == [(1, 1, 7), (1, 5, 4), (1, 9, 1), (6, 1, 5), (64, 95, 1)]
+
+
+@pytest.mark.parametrize("shape", SHAPES + [(5, 4, 1), (1, 1, 1), (7, 1, 1)], ids=ref.shape_key)
+def test_flat_neighbour_index_is_right_where_the_one_launch_solve_takes_the_box(shape):
+    """pcg_small_kernel's stencil sum, s = sum_k tab[type][k] p[i + doff[k]] with ONE linear offset per stencil point into a vector
+    between zero margins, emulated in numpy: it is A p on every box beat_small_available's rule for collapsed axes lets through, and
+    wrong by O(1) on those of the cases it declines (an axis of one node in front of a longer one, under tables of higher
+    dimension: its 'interior' coefficients meet a node of the box)."""
+    dim = ref.dim_of(shape) if shape in SHAPES else 3
+    mt, kt = ref.tables(dim)
+    tab = ref.C_M * mt + ref.THETA * ref.DT * kt
+    nx, ny, nz = shape
+    n, margin = nx * ny * nz, nx * ny + nx + 1
+    x = np.random.default_rng(ref.seed_of(shape)).standard_normal(n)
+    p = np.concatenate([np.zeros(margin), x, np.zeros(margin)])
+    typ, at = fem.node_types(shape), margin + np.arange(n)
+    y = sum(tab[typ, k] * p[at + ox + nx * oy + nx * ny * oz] for k, (ox, oy, oz) in enumerate(fem.STENCIL_OFFSETS))
+    want = fem.apply_stencil(tab, shape, x)
+    err = np.abs(y - want).max() / np.abs(want).max()
+    if ref.small_declines_collapsed(shape):
+        assert err > 0.01, err
+    else:
+        assert err <= 16 * 2.0**-53, err
 
 
 def test_matvec_matches_scipy_and_gains_precision():
@@ -102,7 +155,7 @@ def test_reference_is_right_and_no_stop_is_a_near_tie(shape):
     assert r.rhs_norm_bound() > 0.0
 
 
-@pytest.mark.parametrize("shape", ref.GUESS_SHAPES, ids=ref.shape_key)
+@pytest.mark.parametrize("shape", GUESS_SHAPES, ids=ref.shape_key)
 def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(shape):
     """The fields of the guess cases with exact increments in place of the device's: the extrapolated start is still O(1) wrong, so
     the cut iterates (k = 1, 3) are far from converged."""
