@@ -11,9 +11,25 @@ as one C++ ``Model`` struct for ``csrc/beat_ode_kernel.h``; the library compiles
 run-time ``hipcc --genco``, cached like the sparse-row instances) and every entry point that takes a model id takes this one:
 the fused split step, the pending update, the library's step loop, per-node parameter rows, parameter classes and cell types in
 one launch (``DolfinMultiODESolver``), the in-kernel time loop (``run`` / ``single_cell.get_steady_state``).  Schemes: ``generalized_rush_larsen`` (gotranx's GRL1:
-y_i += f_i / J_ii (exp(J_ii dt) - 1) where |J_ii| > 1e-8, forward Euler elsewhere) and ``forward_euler``.  ``exp`` in the
+y_i += f_i / J_ii (exp(J_ii dt) - 1) where |J_ii| > 1e-8, forward Euler elsewhere), ``forward_euler`` and
+``generalized_rush_larsen_2`` (``grl2``: below).  ``exp`` in the
 kernel is the library's table-driven evaluation (what the shipped models use: <= 1 ulp, 13 instead of ~50 VALU instructions; the
 argument is kept inside double range); ``fast_exp=False`` prints libm's.
+
+GRL2 is the second-order generalised Rush-Larsen step (Sundnes, Artebrant, Skavhaug, Tveito, IEEE Trans. Biomed. Eng. 2009): it
+linearises about the midpoint and integrates from y_n.  With phi(a, h) = (exp(a h) - 1) / a where |a| > 1e-8 and h elsewhere
+(GRL1's switch),
+
+    stage 1   a_i = J_ii(y_n, t),          b_i = f_i(y_n, t),                               yh_i = y_n,i + phi(a_i, dt/2) b_i
+    stage 2   A_i = J_ii(yh, t + dt/2),    B_i = f_i(yh, t + dt/2) + A_i (y_n,i - yh_i),    y_n+1,i = y_n,i + phi(A_i, dt) B_i
+
+and a state whose self-derivative is identically zero takes the explicit midpoint rule (yh_i = y_i + dt/2 f_i(y_n, t),
+y_n+1,i = y_i + dt f_i(yh, t + dt/2)).  ``time`` in the file's expressions is t in stage 1 and t + dt/2 in stage 2; a linear scalar
+equation y' = a y + c is integrated exactly.  Both stages are printed into the one ``Model::step`` -- one launch, the states loaded
+once, nothing stored in between -- so every route of a generated model takes it as it is.  It costs one more evaluation of (f, J)
+per step; with ``MonodomainSplittingSolver(theta=0.5)`` and the PDE step's theta = 0.5 it makes the whole split step second order
+in time, where GRL1 and forward Euler leave it first order whatever the PDE side does.  The models this package ships as
+hand-written kernels (``tp06``, ``torord``, FHN) stay GRL1 / forward Euler.
 
 The same expressions, lambdified for NumPy, are the handle's HOST evaluation (``numpy_step``): what the tests compare the kernel
 with, and what runs where no GPU / compiler is to be had.  Parameters: a (P,) vector or per node (P, N); what a generated model
@@ -38,10 +54,11 @@ import numpy as np
 
 from ._base import DeviceModel, host_and_device_parameters, parameter_args
 
-_SCHEMES = ("generalized_rush_larsen", "forward_euler")
-# gotranx's own names for the same two schemes (gotranx.schemes: what its code generator is asked for)
+_SCHEMES = ("generalized_rush_larsen", "forward_euler", "generalized_rush_larsen_2")
+# gotranx's own names for the first two schemes (gotranx.schemes: what its code generator is asked for), and GRL2's short one
 _SCHEME_ALIASES = {"forward_generalized_rush_larsen": "generalized_rush_larsen", "forward_explicit_euler": "forward_euler",
-                   "explicit_euler": "forward_euler"}
+                   "explicit_euler": "forward_euler", "grl2": "generalized_rush_larsen_2"}
+_RUSH_LARSEN = ("generalized_rush_larsen", "generalized_rush_larsen_2")  # the schemes that need the self-derivatives J_ii
 
 
 def _walk(text: str, where: str):
@@ -182,20 +199,39 @@ def _on_gpu() -> bool:
 class _Body:
     """The body of a generated function as it is being written (the step's, a monitor selection's): the printer, the file's
     states, parameters and time as y_k / p_k / t, the common subexpressions ``repl`` in those symbols, the ``lines`` so far and the
-    symbols they use."""
+    symbols they use.
 
-    def __init__(self, model, repl):
+    ``second_of``: the body of a two-stage step's first stage.  This one then CONTINUES it -- same printer, same ``lines`` -- with
+    the same expressions at the midpoint: the states as yh_k, the time as th, and every common subexpression that depends on a
+    state or on the time under a name of its own (x_7 -> xh_7).  One that depends on parameters alone keeps its name and is not
+    printed again where the first stage has it."""
+
+    def __init__(self, model, repl, second_of=None):
         import sympy
 
-        self.pr, self.uses_mod = model._printer()
         y, p = model._sym["y"], model._sym["p"]
         self.ns, self.np = len(y), len(p)
-        self.sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
-        self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-        self.sub[model._sym["t"]] = sympy.Symbol("t")
-        self.temp = {lhs: e.xreplace(self.sub) for lhs, e in repl}
-        self.lines = []
+        if second_of is None:
+            self.pr, self.uses_mod = model._printer()
+            self.sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
+            self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
+            self.sub[model._sym["t"]] = sympy.Symbol("t")
+            self.temp = {lhs: e.xreplace(self.sub) for lhs, e in repl}
+            self.lines = []
+        else:
+            self.pr, self.uses_mod, self.lines = second_of.pr, second_of.uses_mod, second_of.lines
+            moving = {s for s in y} | {model._sym["t"]}
+            for lhs, e in repl:  # (in definition order: what a moving temporary is used in moves too)
+                if e.free_symbols & moving:
+                    moving.add(lhs)
+            self.sub = {s: sympy.Symbol(f"yh_{k}") for k, s in enumerate(y)}
+            self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
+            self.sub[model._sym["t"]] = sympy.Symbol("th")
+            self.sub.update({lhs: sympy.Symbol(str(lhs).replace("x_", "xh_")) for lhs, _ in repl if lhs in moving})
+            self.temp = {lhs.xreplace(self.sub): e.xreplace(self.sub) for lhs, e in repl}
         self.emit, self.emitted = model._emitter(self.temp, self.pr, self.lines)
+        if second_of is not None:
+            self.emitted |= second_of.emitted  # (the parameter-only temporaries the first stage has defined)
         self.used = set()
 
     def expr(self, e):
@@ -212,7 +248,8 @@ class _Body:
         import sympy
 
         for e in self.emitted:
-            self.used |= self.temp[e].free_symbols
+            if e in self.temp:  # (a second stage's set also names the first stage's temporaries: that body accounts for them)
+                self.used |= self.temp[e].free_symbols
         return ([f"    const double y_{k} = io.load({k});" for k in range(self.ns) if every_state or sympy.Symbol(f"y_{k}") in self.used],
                 [f"    const double p_{k} = p[{k}];" for k in range(self.np) if sympy.Symbol(f"p_{k}") in self.used])
 
@@ -278,7 +315,7 @@ class OdeFileModel(DeviceModel):
             raise ValueError(f"{self.path}: no d<state>_dt for {missing}")
         names = list(states)
         f = [rhs[s] for s in names]
-        J = [self._self_derivative(rhs[s], ysym[s], f"{self.path}:{line[s]}: d{s}_dt") if scheme == "generalized_rush_larsen"
+        J = [self._self_derivative(rhs[s], ysym[s], f"{self.path}:{line[s]}: d{s}_dt") if scheme in _RUSH_LARSEN
              else sympy.Integer(0) for s in names]
         self._grl = [bool(j != 0) for j in J]
         repl, red = sympy.cse(f + J, symbols=sympy.numbered_symbols("x_"), optimizations="basic")
@@ -392,25 +429,12 @@ class OdeFileModel(DeviceModel):
                    "      return m != 0.0 ? ((m < 0.0) != (b < 0.0) ? m + b : m) : copysign(0.0, b);\n"
                    "    };\n" if uses_mod else ""))
 
-    def _cxx(self, stem: str) -> str:
+    def _cxx_one_stage(self, body, order, exp_name) -> None:
+        """The lines of GRL1's and forward Euler's step, appended to ``body``'s (states in ``order``): per state its temporaries, the
+        update and its store."""
         import os
 
-        exp_name = "fexp" if self.fast_exp else "exp"
-        # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
-        # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
-        # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
-        # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
-        # per lane that way.)
-        body = _Body(self, self._sym["repl"])
-        pr, lines, ns_, np_ = body.pr, body.lines, body.ns, body.np
-        vi = self.state_index(self.v_name) if self.v_name else 0
-        order = list(range(ns_))
-        if os.environ.get("BEAT_ODE_V_LAST", "1") == "1" and self.v_name:  # the potential's equation sums every current: last, when the currents exist
-            order = [k for k in order if k != vi] + [vi]
-        if os.environ.get("BEAT_ODE_EMIT") == "global":  # every temporary first, in the elimination's order (tests: the heavily spilled form)
-            for lhs in body.temp:
-                body.emit(lhs)
-            order = list(range(ns_))
+        pr, lines = body.pr, body.lines
         for k in order:
             fk, jk = body.expr(self._sym["f"][k]), body.expr(self._sym["J"][k])
             if self._grl[k]:
@@ -422,6 +446,70 @@ class OdeFileModel(DeviceModel):
                              f"      io.store({k}, y_{k} + beat_sel(fabs(J) > 1e-8, f / J * ({exp_name}(J * dt) - 1.0), f * dt)); }}")
             else:
                 lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
+
+    def _cxx_two_stages(self, body, order, exp_name) -> None:
+        """The lines of GRL2's step, appended to ``body``'s (states in ``order``).  Stage 1, state by state: f_k and J_kk at
+        (y, t) and the midpoint value yh_k = y_k + phi(J, dt/2) f (GRL1 over half a step; y_k + dt/2 f where J_kk is
+        identically zero) -- f and J are scoped to their state, so what stays live is the NS values yh_k next to the loaded y_k.
+        Stage 2, in the one-stage schemes' order: the same expressions at (yh, t + dt/2) under names of their own
+        (``_Body(second_of=...)``), b = f + J (y_k - yh_k), and y_k + phi(J, dt) b stored as soon as it is final.  y_k is the
+        value loaded at the top of the step in both stages: nothing is loaded a second time (on the fused route the potential's
+        load applies the pending update, and the row is overwritten in place)."""
+        import os
+
+        pr, lines = body.pr, body.lines
+        branches = os.environ.get("BEAT_ODE_BRANCHES") == "1"  # (the former output: see _print_Piecewise)
+
+        def phi_times(h):  # phi(J, h) f in GRL1's operation order
+            grl, euler = f"f / J * ({exp_name}(J * {h}) - 1.0)", f"f * {h}"
+            return f"(fabs(J) > 1e-8 ? {grl} : {euler})" if branches else f"beat_sel(fabs(J) > 1e-8, {grl}, {euler})"
+
+        lines.append("    const double hdt = 0.5 * dt, th = t + hdt;  // stage 1: GRL1 over half a step, from (y, t)")
+        for k in order:
+            fk, jk = body.expr(self._sym["f"][k]), body.expr(self._sym["J"][k])
+            if self._grl[k]:
+                lines.append(f"    double yh_{k}; {{ const double f = {pr.doprint(fk)}; const double J = {pr.doprint(jk)};\n"
+                             f"      yh_{k} = y_{k} + {phi_times('hdt')}; }}")
+            else:
+                lines.append(f"    const double yh_{k} = y_{k} + hdt * ({pr.doprint(fk)});")
+        lines.append("    // stage 2: linearised about (yh, th), integrated from y over the whole step")
+        second = _Body(self, self._sym["repl"], second_of=body)
+        if os.environ.get("BEAT_ODE_EMIT") == "global":
+            for lhs in second.temp:
+                second.emit(lhs)
+        for k in order:
+            fk, jk = second.expr(self._sym["f"][k]), second.expr(self._sym["J"][k])
+            if self._grl[k]:
+                lines.append(f"    {{ const double J = {pr.doprint(jk)}; const double f = ({pr.doprint(fk)}) + J * (y_{k} - yh_{k});\n"
+                             f"      io.store({k}, y_{k} + {phi_times('dt')}); }}")
+            else:
+                lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
+        second.loads(every_state=False)
+        body.used |= {s for s in second.used if str(s).startswith("p_")}
+
+    def _cxx(self, stem: str) -> str:
+        import os
+
+        exp_name = "fexp" if self.fast_exp else "exp"
+        # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
+        # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
+        # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
+        # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
+        # per lane that way.)
+        body = _Body(self, self._sym["repl"])
+        lines, ns_, np_ = body.lines, body.ns, body.np
+        vi = self.state_index(self.v_name) if self.v_name else 0
+        order = list(range(ns_))
+        if os.environ.get("BEAT_ODE_V_LAST", "1") == "1" and self.v_name:  # the potential's equation sums every current: last, when the currents exist
+            order = [k for k in order if k != vi] + [vi]
+        if os.environ.get("BEAT_ODE_EMIT") == "global":  # every temporary first, in the elimination's order (tests: the heavily spilled form)
+            for lhs in body.temp:
+                body.emit(lhs)
+            order = list(range(ns_))
+        if self.scheme == "generalized_rush_larsen_2":
+            self._cxx_two_stages(body, order, exp_name)
+        else:
+            self._cxx_one_stage(body, order, exp_name)
         loads, pl = body.loads(every_state=True)
         digest = hashlib.sha1(("\n".join(lines) + self.scheme).encode()).hexdigest()[:12]
         self.cxx_name = f"Ode_{stem}_{digest}"
@@ -510,6 +598,21 @@ class OdeFileModel(DeviceModel):
     def numpy_step(self, states, t, parameters, dt):
         """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``)."""
         y2, args, one_d = self._numpy_args(states, t, parameters)
+        ns = y2.shape[0]
+        if self.scheme == "generalized_rush_larsen_2":
+            # stage 1 is the GRL1 step over dt / 2 (forward Euler where J_kk is identically zero); stage 2 takes f and J at
+            # (yh, t + dt / 2) and integrates b = f + J (y - yh) from y over dt -- the kernel's two stages, operation by operation
+            hdt = 0.5 * dt
+            yh = self._numpy_update(y2, args, hdt)
+            mid = [yh[k] for k in range(ns)] + args[ns:-1] + [np.full(y2.shape[1], float(t) + hdt)]
+            out = self._numpy_update(y2, mid, dt, about=yh)
+        else:
+            out = self._numpy_update(y2, args, dt)
+        return out[:, 0].copy() if one_d else out
+
+    def _numpy_update(self, y2, args, dt, about=None):
+        """y + phi(J, dt) b per state (y + dt b where J_kk is identically zero), f and J evaluated at ``args``:
+        b = f, or f + J (y - about) for a linearisation about another point than y."""
         with np.errstate(all="ignore"):
             f, J = self._numpy_rhs()(*args)
         out = np.empty_like(y2)
@@ -518,10 +621,12 @@ class OdeFileModel(DeviceModel):
             if self._grl[k]:
                 Jk = np.broadcast_to(np.asarray(J[k], dtype=np.float64), y2[k].shape)
                 with np.errstate(all="ignore"):
+                    if about is not None:
+                        fk = fk + Jk * (y2[k] - about[k])
                     out[k] = y2[k] + np.where(np.abs(Jk) > 1e-8, fk / np.where(Jk == 0, 1.0, Jk) * (np.exp(Jk * dt) - 1.0), fk * dt)
             else:
                 out[k] = y2[k] + dt * fk
-        return out[:, 0].copy() if one_d else out
+        return out
 
     def monitor_index(self, name: str) -> int:
         try:
@@ -649,7 +754,10 @@ class OdeFileModel(DeviceModel):
         expressions (``_check_against_numpy``, to 1e-6 of each value), once per process: a big generated kernel is heavily spilled,
         and such a kernel has been seen miscompiled (round 1; reproduced in round 5, tools/diag_spill.py) -- wrong values on part of
         the nodes, silently.  The other instances (per-node rows, pending update, classes) are held against this one by the library
-        at their first launch (csrc/beat_ode_jit.hip: custom_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both."""
+        at their first launch (csrc/beat_ode_jit.hip: custom_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both.  A GRL2 model is held
+        to the same 1e-6 through both of its stages (``numpy_step`` is the two-stage twin): a last-bit difference of the two
+        exp()s in stage 1 reaches the result only through stage 2's derivative with respect to the midpoint values, and the
+        bound needs no widening for it (tests/data/small_cell.ode on an MI355X: 2.3e-8 under GRL2, 3.3e-8 under GRL1)."""
         if getattr(self, "_verified", False):
             return
         worst = self._check_against_numpy(
@@ -765,5 +873,7 @@ class OdeFileModel(DeviceModel):
 def from_ode(path, scheme: str = "generalized_rush_larsen", v_name: str | None = None, name: str | None = None,
              fast_exp: bool = True) -> OdeFileModel:
     """A device cell model from a gotran ``.ode`` file: pass the result as ``fun`` to ``DolfinODESolver`` (and use its
-    ``init_state_values`` / ``init_parameter_values`` / ``state_index`` / ``parameter_index`` as those of a gotranx module)."""
+    ``init_state_values`` / ``init_parameter_values`` / ``state_index`` / ``parameter_index`` as those of a gotranx module).
+    ``scheme``: ``"generalized_rush_larsen"`` (GRL1), ``"forward_euler"``, or the second-order ``"generalized_rush_larsen_2"``
+    (``"grl2"``; see the module docstring)."""
     return OdeFileModel(path, scheme=scheme, v_name=v_name, name=name, fast_exp=fast_exp)

@@ -24,14 +24,11 @@ def demangle(names):
     return [re.sub(r"\(.*", "", n.replace("(anonymous namespace)::", "")).replace("void ", "") for n in out]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("source")
-    ap.add_argument("--filter", default="")
-    ap.add_argument("--md", default=None)
-    args = ap.parse_args()
-    res = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *EXTRA.get(args.source, []), "-Rpass-analysis=kernel-resource-usage", "-c",
-                          str(CSRC / args.source), "-o", "/dev/null"], capture_output=True, text=True)
+def resource_rows(source, extra=(), name_filter=""):
+    """[[kernel, VGPRs, AGPRs, scratch B/lane, waves/SIMD, SGPRs, spilled SGPRs, LDS B/block]] of ``source`` (a file of csrc/, or a
+    path: a generated unit that includes csrc's headers)."""
+    res = subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *EXTRA.get(str(source), []), *extra, f"-I{CSRC}", "-Rpass-analysis=kernel-resource-usage",
+                          "-c", str(CSRC / source), "-o", "/dev/null"], capture_output=True, text=True)
     blocks = re.split(r"remark: [^\n]*Function Name: ", res.stderr)[1:]
     rows = []
     for b in blocks:
@@ -42,7 +39,16 @@ def main():
                      g("TotalSGPRs"), g("SGPRs Spill"), g(r"LDS Size \[bytes/block\]")])
     for r, n in zip(rows, demangle([r[0] for r in rows])):
         r[0] = n
-    rows = [r for r in rows if args.filter in r[0]]
+    return [r for r in rows if name_filter in r[0]]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("source")
+    ap.add_argument("--filter", default="")
+    ap.add_argument("--md", default=None)
+    args = ap.parse_args()
+    rows = resource_rows(args.source, name_filter=args.filter)
     lines = ["| kernel | VGPRs | AGPRs | scratch B/lane | waves/SIMD | SGPRs | spilled SGPRs | LDS B/block |", "|---|---:|---:|---:|---:|---:|---:|---:|"]
     lines += ["| `" + r[0] + "` | " + " | ".join(str(v) for v in r[1:]) + " |" for r in rows]
     text = "\n".join(lines)
