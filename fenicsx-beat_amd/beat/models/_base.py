@@ -35,6 +35,14 @@ class DeviceModel:
     def num_parameters(self) -> int:
         return len(self.parameter_names)
 
+    # (only a model generated from a split .ode file has missing variables: input rows behind its states, ode_file.py)
+    num_missing_variables = 0
+
+    @property
+    def num_rows(self) -> int:
+        """Rows of the array the kernel works on: the states, and the input rows of a model with missing variables."""
+        return self.num_states
+
     def state_index(self, name: str) -> int:
         try:
             return self.state_names.index(name)
@@ -76,8 +84,8 @@ class DeviceModel:
         arr = np.asarray(states, dtype=np.float64)
         a2 = arr.reshape(arr.shape[0], -1)
         S, n = a2.shape
-        if S != self.num_states:
-            raise ValueError(f"{self.name} has {self.num_states} states, got {S}")
+        if S != self.num_rows:
+            raise ValueError(f"{self.name} has {self.num_states} states, got {S - (self.num_rows - self.num_states)}")
         sa = StateArray(ctx, S, n)
         sa.set(a2)
         return ctx, sa, n, arr.ndim == 1, host_and_device_parameters(ctx, parameters, self.num_parameters, n)

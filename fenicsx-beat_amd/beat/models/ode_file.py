@@ -40,6 +40,19 @@ Every assignment of the file -- currents, fluxes, rates, the ``d<state>_dt`` -- 
 ``monitor_names`` / ``monitor_index(name)`` / ``monitor_values(t, states, parameters, names)``.  For a selection of names a second
 struct is printed (``_monitor_cxx``: same printer, common subexpressions over the selection alone) and evaluated by a read-only
 kernel over the state array (``ode_monitor_kernel``, ``beat_ode_monitor``); ``numpy_monitor`` is its host twin.
+
+Missing variables.  A cell model is routinely cut in two -- an electrophysiology half and a mechanics half -- and each half then
+uses a few names the other half owns; the reference hands their values to ``fun`` as ``missing_variables`` on every step
+(src/beat/odesolver.py:51-57).  ``from_ode(path, missing=("ca", "lmbda"))`` (or ``missing="auto"``) declares them: each is a real
+symbol that is CONSTANT over a step -- the self-derivatives J_kk do not see it -- and may stand in any expression, the
+monitored ones included.  For the kernel the model has NS = S + M rows: rows S .. S + M - 1 of the state array are INPUTS, loaded
+where an expression uses them (8 B per used input row, node and step) and never stored, so every entry point of a generated
+model serves it unchanged, and the in-kernel time loop holds them fixed over the run.  Under GRL2 both stages see the step-start
+value of a missing variable: the step is then FIRST order in that variable, second order in the model's own states.
+``missing_names`` / ``num_missing_variables`` / ``missing_index(name)`` / ``init_missing_values(**values)`` are the names a
+gotranx-generated module of a split ODE is believed to offer; gotranx was not at hand when this was written, so that is a
+recollection, not a checked parity.  ``num_states``, ``state_names``, ``state_index`` and ``init_state_values`` cover the file's
+states alone.
 """
 
 from __future__ import annotations
@@ -210,12 +223,15 @@ class _Body:
         import sympy
 
         y, p = model._sym["y"], model._sym["p"]
-        self.ns, self.np = len(y), len(p)
+        self.ns, self.np, self.nin = len(y), len(p), len(model._sym["m"])
+        # a missing variable is input row S + j of the state array: y_{S+j} in either stage (held at its step-start value)
+        inputs = {s: sympy.Symbol(f"y_{self.ns + j}") for j, s in enumerate(model._sym["m"])}
         if second_of is None:
             self.pr, self.uses_mod = model._printer()
             self.sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
             self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
             self.sub[model._sym["t"]] = sympy.Symbol("t")
+            self.sub.update(inputs)
             self.temp = {lhs: e.xreplace(self.sub) for lhs, e in repl}
             self.lines = []
         else:
@@ -228,6 +244,7 @@ class _Body:
             self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
             self.sub[model._sym["t"]] = sympy.Symbol("th")
             self.sub.update({lhs: sympy.Symbol(str(lhs).replace("x_", "xh_")) for lhs, _ in repl if lhs in moving})
+            self.sub.update(inputs)
             self.temp = {lhs.xreplace(self.sub): e.xreplace(self.sub) for lhs, e in repl}
         self.emit, self.emitted = model._emitter(self.temp, self.pr, self.lines)
         if second_of is not None:
@@ -244,20 +261,22 @@ class _Body:
         return e
 
     def loads(self, every_state: bool):
-        """The load lines of the states (all of them, or the used ones) and of the used parameters, once the body is written."""
+        """The load lines of the states (all of them, or the used ones), of the used input rows (a model's missing variables:
+        rows S .. S + M - 1, read and never stored) and of the used parameters, once the body is written."""
         import sympy
 
         for e in self.emitted:
             if e in self.temp:  # (a second stage's set also names the first stage's temporaries: that body accounts for them)
                 self.used |= self.temp[e].free_symbols
-        return ([f"    const double y_{k} = io.load({k});" for k in range(self.ns) if every_state or sympy.Symbol(f"y_{k}") in self.used],
+        return ([f"    const double y_{k} = io.load({k});" for k in range(self.ns + self.nin)
+                 if (every_state and k < self.ns) or sympy.Symbol(f"y_{k}") in self.used],
                 [f"    const double p_{k} = p[{k}];" for k in range(self.np) if sympy.Symbol(f"p_{k}") in self.used])
 
 
 class OdeFileModel(DeviceModel):
     """A :class:`DeviceModel` generated from an ``.ode`` file (see the module docstring)."""
 
-    def __init__(self, path, scheme="generalized_rush_larsen", v_name=None, name=None, fast_exp=True):
+    def __init__(self, path, scheme="generalized_rush_larsen", v_name=None, name=None, fast_exp=True, missing=None, missing_ranges=None):
         import sympy
 
         self.fast_exp = bool(fast_exp)
@@ -280,6 +299,12 @@ class OdeFileModel(DeviceModel):
         if not states:
             raise ValueError(f"{self.path}: no states(...) found")
         assigns = _dependency_order(assigns)
+        self.missing_names = self._missing_names(missing, states, params, assigns)
+        self.missing_ranges = {nm: (0.0, 1.0) for nm in self.missing_names}
+        for nm, (lo, hi) in (missing_ranges or {}).items():
+            if nm not in self.missing_ranges:
+                raise ValueError(f"{self.path}: missing_ranges names {nm!r}, which is not a missing variable of this model")
+            self.missing_ranges[nm] = (float(lo), float(hi))
         if v_name is None:
             v_name = next((s for s in states if s.lower() in ("v", "vm", "v_m")), None)
         if v_name is not None and v_name not in states:
@@ -289,6 +314,7 @@ class OdeFileModel(DeviceModel):
         # ---- symbolic right-hand sides and total self-derivatives
         ysym = {s: sympy.Symbol(s, real=True) for s in states}
         psym = {p: sympy.Symbol(p, real=True) for p in params}
+        msym = {m: sympy.Symbol(m, real=True) for m in self.missing_names}  # constant over a step: J_kk never differentiates by one
         tsym, dtsym = sympy.Symbol("time", real=True), sympy.Symbol("dt", real=True)
 
         def piecewise(c, a, b):
@@ -298,6 +324,7 @@ class OdeFileModel(DeviceModel):
         ns.update({"Conditional": piecewise, "time": tsym, "t": tsym, "pi": sympy.pi,
                    "_indicator": lambda c: sympy.Piecewise((sympy.Integer(1), c), (sympy.Integer(0), True))})
         ns.update(psym)
+        ns.update(msym)
         ns.update(ysym)
         rhs, line, assigned = {}, {}, {}
         for nm, node in assigns:
@@ -319,7 +346,7 @@ class OdeFileModel(DeviceModel):
              else sympy.Integer(0) for s in names]
         self._grl = [bool(j != 0) for j in J]
         repl, red = sympy.cse(f + J, symbols=sympy.numbered_symbols("x_"), optimizations="basic")
-        self._sym = dict(y=[ysym[s] for s in names], p=[psym[p] for p in params], t=tsym, dt=dtsym, repl=repl,
+        self._sym = dict(y=[ysym[s] for s in names], p=[psym[p] for p in params], m=[msym[m] for m in self.missing_names], t=tsym, dt=dtsym, repl=repl,
                          f=red[: len(names)], J=red[len(names):])
         # every assignment of the file, in dependency order: what monitor_values / numpy_monitor can be asked for
         self.monitor_names = tuple(assigned)
@@ -332,6 +359,77 @@ class OdeFileModel(DeviceModel):
         self._library_id = None   # the id beat_ode_model_register gave (the source is handed over once per process)
         self.source = self._cxx(stem)
         self.key = f"{self.cxx_name}"
+
+    def _missing_names(self, missing, states, params, assigns) -> tuple:
+        """The names ``missing`` declares (None: none; "auto": every free name of the file, sorted), checked: a ValueError names the
+        file and the name that is declared or assigned in the file, reserved, used by nothing, or given twice."""
+        if missing is None:
+            return ()
+        assigned = {nm for nm, _ in assigns}
+        reserved = set(_FUNCTIONS) | set(_CONSTANTS) | {"dt"}
+        used = {n.id for _, node in assigns for n in ast.walk(node) if isinstance(n, ast.Name)}
+        if isinstance(missing, str):
+            if missing != "auto":
+                missing = (missing,)
+            else:
+                return tuple(sorted(used - set(states) - set(params) - assigned - reserved))
+        out = []
+        for nm in missing:
+            if not isinstance(nm, str) or not nm.isidentifier():
+                raise ValueError(f"{self.path}: {nm!r} is not the name of a missing variable")
+            if nm in out:
+                raise ValueError(f"{self.path}: missing variable {nm!r} is given twice")
+            for what, where in (("a state", states), ("a parameter", params), ("assigned", assigned), ("a reserved name", reserved)):
+                if nm in where:
+                    raise ValueError(f"{self.path}: {nm!r} cannot be a missing variable: it is {what} in the file")
+            if nm not in used:
+                raise ValueError(f"{self.path}: missing variable {nm!r} is used by no expression of the file")
+            out.append(nm)
+        return tuple(out)
+
+    @property
+    def num_missing_variables(self) -> int:
+        return len(self.missing_names)
+
+    @property
+    def num_rows(self) -> int:
+        """Rows of the state array the kernel works on: the states, then one input row per missing variable."""
+        return self.num_states + self.num_missing_variables
+
+    def missing_index(self, name: str) -> int:
+        try:
+            return self.missing_names.index(name)
+        except ValueError:
+            raise KeyError(f"Unknown missing variable {name}") from None
+
+    def init_missing_values(self, **values) -> np.ndarray:
+        """An (M,) vector of the missing variables in the order of ``missing_names``: 0.0 but for the ones given by name."""
+        d = dict.fromkeys(self.missing_names, 0.0)
+        for k, v in values.items():
+            if k not in d:
+                raise KeyError(f"Unknown missing variable {k}")
+            d[k] = v
+        return np.array([d[k] for k in self.missing_names], dtype=np.float64)
+
+    def _rows(self, states, missing_variables):
+        """(S + M, N) rows for the kernel -- ``states`` (S,) or (S, N) above ``missing_variables`` (M,) or (M, N) -- and whether
+        ``states`` was (S,).  TypeError where the model has missing variables and gets none, or has none and gets some."""
+        m = self.num_missing_variables
+        if m == 0:
+            if missing_variables is not None:
+                raise TypeError(f"{self.name} has no missing variables: missing_variables must not be given")
+            y = np.asarray(states, dtype=np.float64)
+            return y.reshape(y.shape[0], -1), y.ndim == 1
+        if missing_variables is None:
+            raise TypeError(f"{self.name} has the missing variables {self.missing_names}: missing_variables=... is required")
+        y = np.asarray(states, dtype=np.float64)
+        y2 = y.reshape(y.shape[0], -1)
+        if y2.shape[0] != self.num_states:
+            raise ValueError(f"{self.name} has {self.num_states} states, got {y2.shape[0]}")
+        c = np.asarray(missing_variables, dtype=np.float64)
+        if c.shape not in ((m,), (m, y2.shape[1])):
+            raise ValueError(f"missing_variables must have shape ({m},) or ({m}, {y2.shape[1]}), got {c.shape}")
+        return np.concatenate([y2, np.broadcast_to(c.reshape(m, -1), (m, y2.shape[1]))], axis=0), y.ndim == 1
 
     @staticmethod
     def _self_derivative(expr, y, where: str):
@@ -485,7 +583,8 @@ class OdeFileModel(DeviceModel):
             else:
                 lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
         second.loads(every_state=False)
-        body.used |= {s for s in second.used if str(s).startswith("p_")}
+        rows = {f"y_{k}" for k in range(body.ns, body.ns + body.nin)}  # (the second stage reads the input rows the first one loaded)
+        body.used |= {s for s in second.used if str(s).startswith("p_") or str(s) in rows}
 
     def _cxx(self, stem: str) -> str:
         import os
@@ -511,11 +610,15 @@ class OdeFileModel(DeviceModel):
         else:
             self._cxx_one_stage(body, order, exp_name)
         loads, pl = body.loads(every_state=True)
-        digest = hashlib.sha1(("\n".join(lines) + self.scheme).encode()).hexdigest()[:12]
+        # (the missing variables are part of the name -- it is the key of the compiled kernel's cache; without any, the name of before)
+        digest = hashlib.sha1(("\n".join(lines) + self.scheme + ("".join(f"|{nm}" for nm in self.missing_names))).encode()).hexdigest()[:12]
         self.cxx_name = f"Ode_{stem}_{digest}"
-        return (f"// generated by beat.models.from_ode from {self.path.name} ({self.scheme}): {ns_} states, {np_} parameters\n"
+        nin = body.nin  # (rows NS - NIN .. NS - 1 are inputs: loaded where used, never stored; a model without any prints as before)
+        return (f"// generated by beat.models.from_ode from {self.path.name} ({self.scheme}): {ns_} states, {np_} parameters"
+                + (f", {nin} missing variables ({', '.join(self.missing_names)}) as input rows {ns_} .. {ns_ + nin - 1}" if nin else "") + "\n"
                 f"struct {self.cxx_name} {{\n"
-                f"  static constexpr int NS = {ns_}, NP = {max(np_, 1)}, V_INDEX = {vi};\n"
+                f"  static constexpr int NS = {ns_ + nin}, NP = {max(np_, 1)}, V_INDEX = {vi};\n"
+                + (f"  static constexpr int NIN = {nin};\n" if nin else "") +
                 "  static constexpr bool REGISTER_LOOP = true;\n"
                 "  static constexpr int WAVES = 1, WAVES_PER_NODE = 1;\n"
                 "  struct Derived { double unused; };\n"
@@ -541,9 +644,10 @@ class OdeFileModel(DeviceModel):
         loads, pl = body.loads(every_state=False)
         digest = hashlib.sha1("\n".join(loads + pl + lines).encode()).hexdigest()[:12]
         name = f"Mon_{self._stem}_{digest}"
-        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {body.ns} states read\n"
+        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {body.ns + body.nin} "
+                      f"{'state and input rows' if body.nin else 'states'} read\n"
                       f"struct {name} {{\n"
-                      f"  static constexpr int NS = {body.ns}, NP = {max(body.np, 1)}, NM = {len(names)};\n"
+                      f"  static constexpr int NS = {body.ns + body.nin}, NP = {max(body.np, 1)}, NM = {len(names)};\n"
                       "  template <class IO, class P, class OUT>\n"
                       "  __device__ static __forceinline__ void eval(const IO& io, const P& p, const FastMath& fm, double t, const OUT& out) {\n"
                       + self._cxx_helpers(body.uses_mod)
@@ -558,11 +662,11 @@ class OdeFileModel(DeviceModel):
                 for k in range(0, len(names), _hip.MAX_MONITORS)]
 
     # ------------------------------------------------------------------------------------------------ NumPy
-    def _numpy_args(self, states, t, parameters):
-        """(states as (S, N), the arguments of a lambdified function over y + p + [t], whether ``states`` was (S,))."""
-        y = np.asarray(states, dtype=np.float64)
-        one_d = y.ndim == 1
-        y2 = y.reshape(y.shape[0], -1)
+    def _numpy_args(self, states, t, parameters, missing_variables=None):
+        """(states as (S, N), the arguments of a lambdified function over y + m + p + [t] -- m: the missing variables, none for
+        most models --, whether ``states`` was (S,))."""
+        rows, one_d = self._rows(states, missing_variables)
+        y2, m2 = rows[: rows.shape[0] - self.num_missing_variables], rows[rows.shape[0] - self.num_missing_variables:]
         p = np.asarray(parameters, dtype=np.float64)  # (P,) or per node (P, N)
         if p.ndim == 2 and p.shape[1] != y2.shape[1]:
             raise ValueError(f"per-node parameters must have shape ({len(p)}, {y2.shape[1]}), got {p.shape}")
@@ -570,7 +674,7 @@ class OdeFileModel(DeviceModel):
         # would otherwise be a reduction over a ragged pair)
         n = y2.shape[1]
         pn = [np.broadcast_to(np.asarray(p[k], dtype=np.float64), (n,)) for k in range(len(p))]
-        return y2, [y2[k] for k in range(y2.shape[0])] + pn + [np.full(n, float(t))], one_d
+        return y2, [y2[k] for k in range(y2.shape[0])] + [m2[k] for k in range(m2.shape[0])] + pn + [np.full(n, float(t))], one_d
 
     @staticmethod
     def _numpy_printer():
@@ -591,13 +695,15 @@ class OdeFileModel(DeviceModel):
         if self._numpy_fn is None:
             s = self._sym
             # (the common subexpressions found at construction are handed to lambdify as they are: local assignments in the generated function)
-            self._numpy_fn = sympy.lambdify(s["y"] + s["p"] + [s["t"]], [s["f"], s["J"]], "numpy", cse=lambda exprs: (s["repl"], exprs),
+            self._numpy_fn = sympy.lambdify(s["y"] + s["m"] + s["p"] + [s["t"]], [s["f"], s["J"]], "numpy", cse=lambda exprs: (s["repl"], exprs),
                                             printer=self._numpy_printer())
         return self._numpy_fn
 
-    def numpy_step(self, states, t, parameters, dt):
-        """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``)."""
-        y2, args, one_d = self._numpy_args(states, t, parameters)
+    def numpy_step(self, states, t, parameters, dt, missing_variables=None):
+        """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``).
+        ``missing_variables``: (M,) or (M, N), for a model made with ``missing=`` (TypeError where such a model gets none, or
+        another model gets some); held at these values through both stages of GRL2.  Returns the S states."""
+        y2, args, one_d = self._numpy_args(states, t, parameters, missing_variables)
         ns = y2.shape[0]
         if self.scheme == "generalized_rush_larsen_2":
             # stage 1 is the GRL1 step over dt / 2 (forward Euler where J_kk is identically zero); stage 2 takes f and J at
@@ -645,16 +751,16 @@ class OdeFileModel(DeviceModel):
             self.monitor_index(nm)
         return names
 
-    def numpy_monitor(self, states, t, parameters, names=None):
+    def numpy_monitor(self, states, t, parameters, names=None, missing_variables=None):
         """The values of the file's assignments ``names`` (None: all of ``monitor_names``) on the HOST with NumPy: (M,) for (S,)
         states, (M, N) for (S, N); parameters (P,) or per node (P, N).  What the monitor kernel is compared with, as ``numpy_step``
         is for the step.  The ``d<state>_dt`` rows are the right-hand sides ``numpy_step`` integrates, bit for bit (the same
         lambdified function); every other row comes from ONE function over all assignments, so that a selection gives the numbers
-        of the matching rows of ``names=None``."""
+        of the matching rows of ``names=None``.  ``missing_variables``: as for ``numpy_step``."""
         import sympy
 
         names = self._monitor_selection(names)
-        y2, args, one_d = self._numpy_args(states, t, parameters)
+        y2, args, one_d = self._numpy_args(states, t, parameters, missing_variables)
         n = y2.shape[1]
         rhs_row = {f"d{s}_dt": k for k, s in enumerate(self.state_names)}
         plain = [nm for nm in self.monitor_names if nm not in rhs_row]
@@ -665,7 +771,7 @@ class OdeFileModel(DeviceModel):
             if any(nm not in rhs_row for nm in names):
                 if self._mon_numpy_fn is None:
                     s = self._sym
-                    self._mon_numpy_fn = sympy.lambdify(s["y"] + s["p"] + [s["t"]], [self._mon_expr[nm] for nm in plain], "numpy", cse=True,
+                    self._mon_numpy_fn = sympy.lambdify(s["y"] + s["m"] + s["p"] + [s["t"]], [self._mon_expr[nm] for nm in plain], "numpy", cse=True,
                                                         printer=self._numpy_printer())
                 vals = dict(zip(plain, self._mon_numpy_fn(*args)))
         for j, nm in enumerate(names):
@@ -682,7 +788,7 @@ class OdeFileModel(DeviceModel):
             if self._library_id is None:
                 lib = _hip.load()
                 mid = C.c_int(-1)
-                _hip.check(lib.beat_ode_model_register(self.cxx_name.encode(), self.source.encode(), self.num_states,
+                _hip.check(lib.beat_ode_model_register(self.cxx_name.encode(), self.source.encode(), self.num_rows,
                                                        max(self.num_parameters, 1), self.state_index(self.v_name) if self.v_name else 0,
                                                        C.byref(mid)))
                 self._library_id = int(mid.value)
@@ -699,7 +805,8 @@ class OdeFileModel(DeviceModel):
 
     def _sample_states(self, n: int, seed: int = 0) -> np.ndarray:
         """States to try a kernel on: the initial values, the potential spread over [-100, 60] mV, values in [0, 1] (gates) spread
-        over [0, 1], everything else within +-30 % of its initial value."""
+        over [0, 1], everything else within +-30 % of its initial value.  A model with missing variables gets (S + M, n): each
+        input row spread over its ``missing_ranges`` entry ((0, 1) unless ``from_ode`` was told otherwise)."""
         rng = np.random.default_rng(seed)
         y = np.repeat(self.init_state_values()[:, None], n, axis=1)
         for k, name in enumerate(self.state_names):
@@ -711,7 +818,26 @@ class OdeFileModel(DeviceModel):
             else:
                 y[k] = y0 * rng.uniform(0.7, 1.3, n)
         y[:, 0] = self.init_state_values()
+        if self.missing_names:
+            y = np.concatenate([y, np.stack([rng.uniform(*self.missing_ranges[nm], n) for nm in self.missing_names])], axis=0)
         return y
+
+    def _split_rows(self, rows):
+        """(the S state rows, the M input rows or None) of an (S + M, N) array."""
+        S = self.num_states
+        return rows[:S], (rows[S:] if self.missing_names else None)
+
+    def _numpy_step_rows(self, rows, t, parameters, dt):
+        """``numpy_step`` on the kernel's (S + M, N) rows: the states advanced, the input rows as they were."""
+        y, c = self._split_rows(rows)
+        out = self.numpy_step(y, t, parameters, dt, missing_variables=c)
+        return out if c is None else np.concatenate([out, c], axis=0)
+
+    def step_rows(self, rows, t, parameters, dt):
+        """One kernel step of the (S + M, N) rows as the state array holds them -- the states above the input rows -- staged
+        through the device: all rows back, the input rows untouched.  (``__call__`` takes and returns the S states.)"""
+        self.register()
+        return DeviceModel.__call__(self, states=rows, t=t, parameters=parameters, dt=dt)
 
     @staticmethod
     def step_error(dev, ref, y):
@@ -757,12 +883,13 @@ class OdeFileModel(DeviceModel):
         at their first launch (csrc/beat_ode_jit.hip: custom_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both.  A GRL2 model is held
         to the same 1e-6 through both of its stages (``numpy_step`` is the two-stage twin): a last-bit difference of the two
         exp()s in stage 1 reaches the result only through stage 2's derivative with respect to the midpoint values, and the
-        bound needs no widening for it (tests/data/small_cell.ode on an MI355X: 2.3e-8 under GRL2, 3.3e-8 under GRL1)."""
+        bound needs no widening for it (tests/data/small_cell.ode on an MI355X: 2.3e-8 under GRL2, 3.3e-8 under GRL1).  The input
+        rows of a model with missing variables are part of both sides: the kernel must hand them back as they went in."""
         if getattr(self, "_verified", False):
             return
         worst = self._check_against_numpy(
-            "kernel", [f"state {s}" for s in self.state_names],
-            lambda y, t, p, dt: DeviceModel.__call__(self, states=y, t=t, parameters=p, dt=dt), self.numpy_step, self.step_error)
+            "kernel", [f"state {s}" for s in self.state_names] + [f"input row {m}" for m in self.missing_names],
+            lambda y, t, p, dt: DeviceModel.__call__(self, states=y, t=t, parameters=p, dt=dt), self._numpy_step_rows, self.step_error)
         if worst is not None:
             self.self_check_error = worst
             self._verified = True
@@ -837,43 +964,66 @@ class OdeFileModel(DeviceModel):
         The per-node and class instances are held against this one by the library at their first launch (csrc/beat_ode_jit.hip:
         monitor_cross_check).  BEAT_JIT_SELF_CHECK=0 skips both; a failing instance raises."""
         self._check_against_numpy("monitor kernel", names, lambda y, t, p, dt: self._monitor_staged(mid, len(names), y, t, p),
-                                  lambda y, t, p, dt: self.numpy_monitor(y, t, p, list(names)), lambda dev, ref, y: self.monitor_error(dev, ref))
+                                  lambda y, t, p, dt: self.numpy_monitor(self._split_rows(y)[0], t, p, list(names), missing_variables=self._split_rows(y)[1]),
+                                  lambda dev, ref, y: self.monitor_error(dev, ref))
 
-    def monitor_values(self, t, states, parameters, names=None):
+    def monitor_values(self, t, states, parameters, names=None, missing_variables=None):
         """gotranx's ``monitor_values(t, states, parameters)``: the values of the file's assignments ``names`` (None: all, in the
         order of ``monitor_names``; ``monitor_index(name)`` gives a row) for (S,) or (S, N) states and (P,) or (P, N) parameters,
         as (M,) or (M, N).  With a GPU the arrays are staged through the device and the monitor kernel runs; without one this is
-        ``numpy_monitor``, as ``__call__`` is ``numpy_step``."""
+        ``numpy_monitor``, as ``__call__`` is ``numpy_step``.  ``missing_variables``: (M,) or (M, N) for a model made with
+        ``missing=`` (the kernel reads them as rows behind the states)."""
         if not _on_gpu():
-            return self.numpy_monitor(states, t, parameters, names)
+            return self.numpy_monitor(states, t, parameters, names, missing_variables=missing_variables)
         names = self._monitor_selection(names)
-        y = np.asarray(states, dtype=np.float64)
-        one_d = y.ndim == 1
-        y2 = np.ascontiguousarray(y.reshape(y.shape[0], -1))
-        if y2.shape[0] != self.num_states:
-            raise ValueError(f"{self.name} has {self.num_states} states, got {y2.shape[0]}")
+        y2, one_d = self._rows(states, missing_variables)
+        y2 = np.ascontiguousarray(y2)
+        if y2.shape[0] != self.num_rows:
+            raise ValueError(f"{self.name} has {self.num_states} states, got {y2.shape[0] - self.num_missing_variables}")
         out = np.concatenate([self._monitor_staged(mid, m, y2, t, parameters) for mid, m in self._monitor_launches(names)], axis=0)
         return out[:, 0].copy() if one_d else out
 
-    def __call__(self, states=None, t=0.0, parameters=None, dt=None, **kwargs):
+    def __call__(self, states=None, t=0.0, parameters=None, dt=None, missing_variables=None, **kwargs):
+        """The reference's ``fun(states=, t=, parameters=, dt=[, missing_variables=])``: the S states advanced by one step.  A model
+        made with ``missing=`` needs ``missing_variables`` ((M,) or (M, N)); any other refuses them (TypeError either way)."""
         if dt is None:
             raise TypeError("dt is required")
-        if _on_gpu():
+        if not _on_gpu():
+            return self.numpy_step(states, t, parameters, dt, missing_variables=missing_variables)
+        rows, one_d = self._rows(states, missing_variables)
+        if not self.missing_names:
             self.register()
             return super().__call__(states=states, t=t, parameters=parameters, dt=dt, **kwargs)
-        return self.numpy_step(states, t, parameters, dt)
+        out = self.step_rows(rows, t, parameters, dt)[: self.num_states]
+        return out[:, 0].copy() if one_d else out
 
-    def run(self, states, parameters, dt, nsteps, nbeats=1, t0=0.0, track_indices=None, save_freq=1):
+    def run(self, states, parameters, dt, nsteps, nbeats=1, t0=0.0, track_indices=None, save_freq=1, missing_variables=None):
         """nbeats x nsteps steps inside ONE launch (beat_ode_run: ``ode_run_kernel`` instantiated for this model at first use), as
-        for the shipped models -- ``single_cell.get_steady_state`` with a generated model paces on the device."""
+        for the shipped models -- ``single_cell.get_steady_state`` with a generated model paces on the device.
+        ``missing_variables``: (M,) or (M, N), held constant over the whole run (the kernel keeps the input rows in registers
+        next to the states and never advances them)."""
         self.register()
-        return super().run(states, parameters, dt, nsteps, nbeats=nbeats, t0=t0, track_indices=track_indices, save_freq=save_freq)
+        rows, one_d = self._rows(states, missing_variables)
+        if not self.missing_names:
+            return super().run(states, parameters, dt, nsteps, nbeats=nbeats, t0=t0, track_indices=track_indices, save_freq=save_freq)
+        if track_indices is not None and any(not 0 <= int(i) < self.num_states for i in track_indices):
+            raise ValueError(f"track_indices must name states of {self.name} (0 .. {self.num_states - 1})")
+        out, track = super().run(rows, parameters, dt, nsteps, nbeats=nbeats, t0=t0, track_indices=track_indices, save_freq=save_freq)
+        out = out[: self.num_states]
+        if one_d:
+            out, track = out[:, 0].copy(), (None if track is None else track[:, :, 0])
+        return out, track
 
 
 def from_ode(path, scheme: str = "generalized_rush_larsen", v_name: str | None = None, name: str | None = None,
-             fast_exp: bool = True) -> OdeFileModel:
+             fast_exp: bool = True, missing=None, missing_ranges: dict | None = None) -> OdeFileModel:
     """A device cell model from a gotran ``.ode`` file: pass the result as ``fun`` to ``DolfinODESolver`` (and use its
     ``init_state_values`` / ``init_parameter_values`` / ``state_index`` / ``parameter_index`` as those of a gotranx module).
     ``scheme``: ``"generalized_rush_larsen"`` (GRL1), ``"forward_euler"``, or the second-order ``"generalized_rush_larsen_2"``
-    (``"grl2"``; see the module docstring)."""
-    return OdeFileModel(path, scheme=scheme, v_name=v_name, name=name, fast_exp=fast_exp)
+    (``"grl2"``; see the module docstring).
+
+    ``missing``: the missing variables of a SPLIT cell model -- names the file uses and neither declares nor assigns, because the
+    other half of the model owns them (see the module docstring).  ``None``: there are none, and an undefined name is an error;
+    a sequence of names: these, in this order; ``"auto"``: every free name of the file, sorted.  ``missing_ranges``:
+    ``{name: (lo, hi)}``, the range the kernel's self check draws a missing variable from, (0, 1) where not given."""
+    return OdeFileModel(path, scheme=scheme, v_name=v_name, name=name, fast_exp=fast_exp, missing=missing, missing_ranges=missing_ranges)

@@ -109,6 +109,7 @@ class MonodomainSplittingSolver:
         if recorder is not None and recorder._f is not pde.state:
             return False
         ode._dev.parameters = ode.parameters
+        ode._refresh_missing()  # (a split cell model's input rows, as the live array has them: constant over the batch)
         return ode._dev.routes.resolve(ode.parameters).kind == "uniform"  # (one host vector)
 
     def _batched_steps(self, steps, recorder) -> None:
@@ -242,6 +243,7 @@ class MonodomainSplittingSolver:
         if hasattr(ode, "_fused_prepare"):
             return ode._fused_prepare()
         ode._dev.parameters = ode.parameters
+        ode._refresh_missing()
         return ode.v_index
 
     def _fused_step(self, t0, t1):

@@ -127,7 +127,9 @@ def _route_ops(ctx):
 
 
 class _DeviceODE:
-    """(S, N) state array in HBM advanced by a built-in model kernel."""
+    """(S, N) state array in HBM advanced by a built-in model kernel.  For a model with M missing variables
+    (``beat.models.from_ode(..., missing=...)``) the array has S + M rows: the kernel reads rows S .. S + M - 1 as its inputs and
+    never writes them; ``set_initial`` / ``set_states`` / ``state_values`` mean the S state rows."""
 
     def __init__(self, ctx, model: DeviceModel, num_states, n, plane, parameters, monitor):
         from ._device import StateArray
@@ -139,7 +141,8 @@ class _DeviceODE:
         self.ctx = ctx
         self.model = model
         self.n = n
-        self.states = StateArray(ctx, num_states, n, plane)
+        self.num_states, self.num_inputs = int(num_states), int(model.num_missing_variables)
+        self.states = StateArray(ctx, self.num_states + self.num_inputs, n, plane)
         self.parameters = parameters
         self.monitor = monitor
         self.node_map = None   # (int32 node of the PDE grid per entry, the field holding the potential): compact layout
@@ -159,7 +162,25 @@ class _DeviceODE:
             for k, val in enumerate(values):
                 self.states.row_field(k).fill(float(val))
         else:
-            self.states.set(values)
+            self.set_states(values)
+
+    def set_states(self, values) -> None:
+        """The S state rows from an (S, N) host array."""
+        if self.num_inputs == 0:
+            return self.states.set(values)
+        values = np.ascontiguousarray(np.asarray(values, dtype=np.float64))
+        assert values.shape == (self.num_states, self.n), (values.shape, (self.num_states, self.n))
+        self.states.rows[: self.num_states].copy_(self.ctx.torch.from_numpy(values))
+
+    def state_values(self) -> np.ndarray:
+        """The S state rows as an (S, N) host array."""
+        return self.states.numpy() if self.num_inputs == 0 else self.states.rows[: self.num_states].cpu().numpy()
+
+    def input_field(self, j: int):
+        """Input row j (row S + j of the array) as a field."""
+        if not 0 <= int(j) < self.num_inputs:
+            raise IndexError(f"{self.model.name} has {self.num_inputs} missing variables, asked for {j}")
+        return self.states.row_field(self.num_states + int(j))
 
     def monitor_rows(self, names, t, out_ptr, out_ld) -> None:
         """The monitor kernel of a generated model on the resident states, with the parameters as they are now and by the route the
@@ -276,6 +297,12 @@ class DolfinODESolver(BaseDolfinODESolver):
         self.on_device = isinstance(self.fun, DeviceModel)
         values = _initial_values(self.init_states, self.shape, self.on_device)
         if self.on_device:
+            m = int(self.fun.num_missing_variables)
+            if m == 0 and self.missing_variables is not None:
+                raise ValueError(f"{self.fun.name} has no missing variables: missing_variables would be ignored (a model made by "
+                                 "beat.models.from_ode(..., missing=...) takes them)")
+            if m and m != int(self.num_missing_variables):
+                raise ValueError(f"{self.fun.name} has {m} missing variables, num_missing_variables={self.num_missing_variables}")
             mesh = self.v_ode.function_space.mesh
             plane = mesh.plane if self.v_ode.function_space.is_p1 else 0  # only P1 rows are stencil operands
             self._dev = _DeviceODE(self.v_ode._ctx, self.fun, self.num_states, self.num_points, plane,
@@ -283,6 +310,13 @@ class DolfinODESolver(BaseDolfinODESolver):
             self._dev.set_initial(values)
             self._v_row = self._dev.states.row_field(self.v_index)
             self._ode = self._dev
+            self._missing_sent = None      # the (M, N) values that were uploaded: what the live array is compared with
+            self._missing_functions = {}   # row -> (the function that IS the row, its version when handed out)
+            self._missing_resident = set()  # rows written on the device: the NumPy array no longer decides them
+            if m:
+                if self.missing_variables is None:
+                    self.missing_variables = self.fun.init_missing_values()
+                self._refresh_missing()
         else:
             self._values = values
             self._ode = ODESystemSolver(fun=self.fun, states=self._values, parameters=self.parameters,
@@ -316,8 +350,89 @@ class DolfinODESolver(BaseDolfinODESolver):
     def values(self):
         if self.on_device:
             self._sync_v()
-            return self._dev.states.numpy()
+            return self._dev.state_values()
         return self._values
+
+    # ---- missing variables of a split cell model, on the device -----------------------------------
+    def _refresh_missing(self) -> None:
+        """The input rows as ``missing_variables`` has them NOW: the live (M,) or (M, N) array is compared with the copy that was
+        uploaded and the rows edited in place since are uploaded again (the reference hands ``fun`` the live array on every step;
+        the rule ``ParameterRoutes.resolve`` applies to a live (P, N) parameter array).  A row that has been written on the
+        device -- through ``missing_function`` or ``set_missing`` -- is resident: the array is no longer consulted for it."""
+        m = self._dev.num_inputs if self.on_device else 0
+        if m == 0:
+            return
+        for j, (f, version) in self._missing_functions.items():
+            if f._version != version:
+                self._missing_resident.add(j)
+        if len(self._missing_resident) == m:
+            return
+        live = np.asarray(self.missing_variables, dtype=np.float64)
+        if live.shape not in ((m,), (m, self.num_points)):
+            raise ValueError(f"missing_variables must have shape ({m},) or {self.shape_missing_values}, got {live.shape}")
+        live = live.reshape(m, -1)
+        sent = self._missing_sent
+        for j in range(m):
+            if j in self._missing_resident or (sent is not None and sent[j].shape == live[j].shape and np.array_equal(sent[j], live[j])):
+                continue
+            self._dev.input_field(j).set(live[j])  # ((1,) is broadcast to the row)
+            if j in self._missing_functions:  # (the upload is not a write THROUGH the function: the row stays the array's)
+                f = self._missing_functions[j][0]
+                f._touch()
+                self._missing_functions[j] = (f, f._version)
+        self._missing_sent = live.copy()
+
+    def _missing_row(self, name) -> int:
+        if not (self.on_device and self._dev.num_inputs):
+            raise ValueError(f"{getattr(self.fun, 'name', self.fun)} has no missing variables on the device")
+        return self.fun.missing_index(name) if isinstance(name, str) else int(name)
+
+    def missing_function(self, name) -> grid.Function:
+        """A function on ``v_ode``'s space whose field IS the kernel's input row of the missing variable ``name``: whatever writes
+        it -- ``other.monitor([...], t, out=[f])``, ``other.state_to_function(k, f)``, ``f.x.array[:] = ...`` -- writes what the
+        next step reads, with no pass over the host.  Once the row has been written through it, the ``missing_variables`` array
+        is no longer consulted for that row."""
+        j = self._missing_row(name)
+        if j not in self._missing_functions:
+            f = grid.Function(self.v_ode.function_space, name=self.fun.missing_names[j], field=self._dev.input_field(j))
+            self._missing_functions[j] = (f, f._version)
+        return self._missing_functions[j][0]
+
+    def set_missing(self, name, value) -> None:
+        """The missing variable ``name`` at every node from a float, an (N,) array or a ``grid.Function`` (a device copy).  The
+        row is resident from here on: the ``missing_variables`` array is no longer consulted for it."""
+        j = self._missing_row(name)
+        row = self._dev.input_field(j)
+        if isinstance(value, grid.Function):
+            if value.num_values != row.n:  # (the copy is row.n values long)
+                raise ValueError(f"expected a function of {row.n} values, got {value.num_values}")
+            row.copy_from(value.field)
+        elif np.ndim(value) == 0:
+            row.fill(float(value))
+        else:
+            value = np.asarray(value, dtype=np.float64)
+            if value.shape != (self.num_points,):
+                raise ValueError(f"expected {self.num_points} values, got shape {value.shape}")
+            row.set(value)
+        self._missing_resident.add(j)
+        if j in self._missing_functions:
+            self._missing_functions[j][0]._touch()
+
+    def state_to_function(self, index_or_name, out: grid.Function) -> grid.Function:
+        """State row ``index_or_name`` copied on the device into ``out`` (for instance another solver's ``missing_function``).
+        With ``missing_function`` and ``set_missing`` this couples two device solvers without a device-to-host copy."""
+        if not self.on_device:
+            raise NotImplementedError("state_to_function copies a row of the device's state array: fun is a host callable")
+        k = self.fun.state_index(index_or_name) if isinstance(index_or_name, str) else int(index_or_name)
+        if not 0 <= k < self.num_states:
+            raise IndexError(f"state {k} of {self.num_states}")
+        if out.num_values != self._dev.n:  # (the copy is as long as ``out``)
+            raise ValueError(f"expected a function of {self._dev.n} values, got {out.num_values}")
+        if k == self.v_index:
+            self._sync_v()
+        out.writable_field().copy_from(self._dev.states.row_field(k))
+        out._touch()
+        return out
 
     @property
     def num_parameters(self) -> int:
@@ -339,6 +454,7 @@ class DolfinODESolver(BaseDolfinODESolver):
         if self.on_device:
             self._release_aliases()
             self._dev.parameters = self.parameters
+            self._refresh_missing()
             self._dev.step(t0, dt)
         else:
             self._ode.step(t0=t0, dt=dt)
@@ -351,8 +467,6 @@ class DolfinODESolver(BaseDolfinODESolver):
         if not self.on_device or not hasattr(self.fun, "monitor_on_device"):
             raise NotImplementedError("monitor() evaluates the named intermediates of a model made by beat.models.from_ode: a hand-written "
                                       "kernel or a host callable keeps none; use from_ode on the model's .ode file")
-        if self.missing_variables is not None:
-            raise NotImplementedError("monitor() does not take missing_variables")
         V = self.v_ode.function_space
         if V.mesh.comm.size > 1:
             raise NotImplementedError("monitor() is not available on a decomposed mesh")
@@ -365,6 +479,7 @@ class DolfinODESolver(BaseDolfinODESolver):
         # (what to_dolfin / values do before they read the row: finish the solve, apply the update)
         self._sync_v()
         self._dev.parameters = self.parameters
+        self._refresh_missing()  # (a model with missing variables: the monitor kernel reads them as rows, like the step)
         mesh = V.mesh
         rows = StateArray(self.v_ode._ctx, len(names), self.num_points, mesh.plane if V.is_p1 else 0)
         self._dev.monitor_rows(names, t, rows.ptr, rows.ld)
@@ -386,7 +501,7 @@ class DolfinODESolver(BaseDolfinODESolver):
         values = np.asarray(values, dtype=np.float64)
         if self.on_device:
             self._release_aliases()
-            self._dev.states.set(np.broadcast_to(values.reshape(self.num_states, -1), self.shape))
+            self._dev.set_states(np.broadcast_to(values.reshape(self.num_states, -1), self.shape))
         else:
             self._values[:] = values.reshape(self.num_states, -1)
 
@@ -433,6 +548,10 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
         self._ctx = ctx
         self.on_device = all(isinstance(f, DeviceModel) for f in self.fun.values())
         if self.on_device:
+            for f in self.fun.values():
+                if f.num_missing_variables:
+                    raise NotImplementedError(f"{f.name} has missing variables: DolfinMultiODESolver takes none (nor does the reference's); "
+                                              "use one DolfinODESolver per half")
             for f in self.fun.values():  # models generated from .ode files get their ids now (markers sharing one are compared below)
                 if hasattr(f, "register"):
                     f.register()

@@ -33,11 +33,11 @@ def _identity_of(fun: Callable) -> bytes:
 
 
 def compute_hash(fun: Callable, init_states: np.ndarray, parameters: np.ndarray, nbeats: int = 200,
-                 BCL: float = 1000.0, dt: float = 0.05) -> str:
-    """Cache key of one pacing run: the step function, the exact bytes of the initial states and parameters, and the
-    protocol."""
+                 BCL: float = 1000.0, dt: float = 0.05, missing_variables=None) -> str:
+    """Cache key of one pacing run: the step function, the exact bytes of the initial states and parameters (and of the missing
+    variables, where a split model is given some: without them the key is what it was), and the protocol."""
     key = hashlib.md5(_identity_of(fun))
-    for arr in (init_states, parameters):
+    for arr in (init_states, parameters) + (() if missing_variables is None else (missing_variables,)):
         a = np.ascontiguousarray(arr, dtype=np.float64)
         key.update(str(a.shape).encode())
         key.update(a.tobytes())
@@ -90,9 +90,12 @@ def solve_without_save(fun, nbeats, times, y, p, dt):
 
 def get_steady_state(fun: Callable, init_states: np.ndarray, parameters: np.ndarray, outdir: Path, nbeats: int = 200,
                      BCL: int = 1000, save_every_ms: float = 1.0, dt: float = 0.05,
-                     track_indices: list[int] | None = None):
+                     track_indices: list[int] | None = None, missing_variables=None):
+    """``missing_variables``: (M,) or (M, N), the constant inputs of a split cell model (``beat.models.from_ode(..., missing=...)``)
+    over the whole run; on the host they are handed to ``fun`` on every step, as the reference's ODE solver hands them."""
     outdir = Path(outdir)
-    key = compute_hash(fun=fun, init_states=init_states, parameters=parameters, nbeats=nbeats, BCL=BCL, dt=dt)
+    key = compute_hash(fun=fun, init_states=init_states, parameters=parameters, nbeats=nbeats, BCL=BCL, dt=dt,
+                       missing_variables=missing_variables)
     cached = outdir / f"steady_states_{key}.npy"
     if cached.is_file():
         return np.load(cached)
@@ -100,11 +103,13 @@ def get_steady_state(fun: Callable, init_states: np.ndarray, parameters: np.ndar
     logger.info(f"Computing steady state with {nbeats} beats.")
     nsteps = len(np.arange(0.0, BCL, dt))  # the reference's step times; t = j * dt within a beat
     save_freq = int(np.ceil(save_every_ms / dt))
+    extra = {} if missing_variables is None else {"missing_variables": missing_variables}
     if isinstance(fun, DeviceModel):
         y, tracked = fun.run(np.array(init_states, dtype=np.float64), parameters, dt, nsteps=nsteps, nbeats=nbeats, t0=0.0,
-                             track_indices=track_indices, save_freq=save_freq)
+                             track_indices=track_indices, save_freq=save_freq, **extra)
     else:
-        y, tracked = pace_on_host(fun, init_states, parameters, dt, nsteps, nbeats, save_freq, track_indices)
+        step = fun if missing_variables is None else (lambda **kw: fun(**kw, **extra))
+        y, tracked = pace_on_host(step, init_states, parameters, dt, nsteps, nbeats, save_freq, track_indices)
     if tracked is not None:
         np.save(outdir / f"tracked_values_{key}.npy", tracked)
     np.save(cached, y)
