@@ -57,146 +57,18 @@ states alone.
 
 from __future__ import annotations
 
-import ast
-import copy
 import ctypes as C
-import hashlib
 from pathlib import Path
 
 import numpy as np
 
 from ._base import DeviceModel, host_and_device_parameters, parameter_args
+from ._ode_parse import parse_ode
 
 _SCHEMES = ("generalized_rush_larsen", "forward_euler", "generalized_rush_larsen_2")
 # gotranx's own names for the first two schemes (gotranx.schemes: what its code generator is asked for), and GRL2's short one
 _SCHEME_ALIASES = {"forward_generalized_rush_larsen": "generalized_rush_larsen", "forward_explicit_euler": "forward_euler",
                    "explicit_euler": "forward_euler", "grl2": "generalized_rush_larsen_2"}
-_RUSH_LARSEN = ("generalized_rush_larsen", "generalized_rush_larsen_2")  # the schemes that need the self-derivatives J_ii
-
-
-def _walk(text: str, where: str):
-    tree = ast.parse(text, filename=where)
-    for node in tree.body:
-        if isinstance(node, ast.Expr) and isinstance(node.value, ast.Call) and isinstance(node.value.func, ast.Name):
-            yield "call", node.value.func.id, node.value
-        elif isinstance(node, ast.Assign):
-            if len(node.targets) != 1 or not isinstance(node.targets[0], ast.Name):
-                raise ValueError(f"{where}:{node.lineno}: only plain assignments `name = expression` are understood")
-            yield "assign", node.targets[0].id, node.value
-        elif isinstance(node, ast.Expr):  # a docstring / bare constant
-            continue
-        else:
-            raise ValueError(f"{where}:{node.lineno}: statement not understood in an .ode file")
-
-
-_EXPR_NODES = (ast.BinOp, ast.UnaryOp, ast.Call, ast.Name, ast.Constant, ast.Load, ast.Add, ast.Sub, ast.Mult, ast.Div, ast.Pow,
-               ast.USub, ast.UAdd, ast.Compare, ast.Lt, ast.LtE, ast.Gt, ast.GtE, ast.Eq, ast.NotEq, ast.BoolOp, ast.And, ast.Or, ast.Not,
-               ast.Mod)
-# What an expression of an .ode file may call (SymPy's function of the same name, but for the two renamed below and Conditional),
-# and the constants it may name besides its states, parameters and intermediates (tests/data/language_cell.ode uses each of them)
-_FUNCTIONS = ("exp", "log", "sqrt", "floor", "abs", "Abs", "pow", "sin", "cos", "tan", "tanh", "sinh", "cosh", "atan", "asin", "acos",
-              "Conditional", "Lt", "Le", "Gt", "Ge", "Eq", "And", "Or", "Not")
-_SYMPY_NAMES = {"abs": "Abs", "pow": "Pow"}
-_CONSTANTS = ("time", "t", "pi")
-_RELATIONS = ("Lt", "Le", "Gt", "Ge", "Eq", "And", "Or", "Not")
-
-
-def _check_expression(node, where: str, known) -> None:
-    """The right-hand side of an assignment is evaluated (with SymPy objects for the names) to build the expression tree: only
-    arithmetic, comparisons and calls of the functions an .ode file may use pass -- no attribute access, subscripts, lambdas,
-    comprehensions or keyword tricks: an .ode file is data, and this is not the place where it gets to run code."""
-    for n in ast.walk(node):
-        if not isinstance(n, _EXPR_NODES):
-            raise ValueError(f"{where}:{getattr(n, 'lineno', '?')}: `{type(n).__name__}` is not understood in an expression of an .ode file")
-        if isinstance(n, ast.Call):
-            if not isinstance(n.func, ast.Name) or n.func.id not in known or n.keywords:
-                raise ValueError(f"{where}:{n.lineno}: call of an unknown function in an .ode file"
-                                 + (f": {n.func.id}" if isinstance(n.func, ast.Name) else ""))
-        if isinstance(n, ast.Constant) and not isinstance(n.value, (int, float)):
-            raise ValueError(f"{where}:{n.lineno}: only numbers are understood in an expression of an .ode file")
-
-
-class _ComparisonsAsNumbers(ast.NodeTransformer):
-    """gotran lets a comparison stand in arithmetic as 0 or 1 -- ``gammas*((zetas > 0)*zetas + (zetas < -1)*(-zetas - 1))`` in the
-    Land model, ``Gt(Zetas, 0)*Zetas`` in the reference's own file: a comparison (infix or Lt / Le / Gt / Ge / Eq / And / Or / Not)
-    that is an operand of an arithmetic operator becomes ``_indicator(comparison)``
-    (Piecewise((1, c), (0, True))); as an argument of Conditional / And / Or / Not it stays a condition.
-
-    Infix forms become the calls first, since Python's own meaning of them on SymPy objects is not gotran's: ``a == b`` and
-    ``a != b`` on a Symbol are a structural test that gives a bool (``Eq`` / ``Not(Eq)`` here), a chained ``a < b <= c`` and
-    ``and`` / ``or`` / ``not`` ask a relation for its truth value (``And`` of the pairs, ``And`` / ``Or`` / ``Not`` here).  The
-    operands of ``and`` / ``or`` / ``not`` must be comparisons: anything else is refused with its line."""
-
-    _OPS = {ast.Lt: "Lt", ast.LtE: "Le", ast.Gt: "Gt", ast.GtE: "Ge", ast.Eq: "Eq", ast.NotEq: "Eq"}
-
-    def __init__(self, where: str):
-        self.where = where
-
-    @staticmethod
-    def _call(name, args, like):
-        return ast.copy_location(ast.Call(func=ast.Name(id=name, ctx=ast.Load()), args=args, keywords=[]), like)
-
-    @staticmethod
-    def _is_relation(node):
-        return isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in _RELATIONS
-
-    def _wrap(self, node):
-        return self._call("_indicator", [node], node) if self._is_relation(node) else node
-
-    def _relations(self, nodes, what, like):
-        for n in nodes:
-            if not self._is_relation(n):
-                raise ValueError(f"{self.where}:{like.lineno}: the operands of `{what}` in an .ode file must be comparisons")
-        return nodes
-
-    def visit_Compare(self, node):
-        self.generic_visit(node)
-        pairs, left = [], node.left
-        for op, right in zip(node.ops, node.comparators):
-            rel = self._call(self._OPS[type(op)], [copy.deepcopy(left), copy.deepcopy(right)], node)
-            pairs.append(self._call("Not", [rel], node) if isinstance(op, ast.NotEq) else rel)
-            left = right
-        return pairs[0] if len(pairs) == 1 else self._call("And", pairs, node)
-
-    def visit_BoolOp(self, node):
-        self.generic_visit(node)
-        what = "and" if isinstance(node.op, ast.And) else "or"
-        return self._call("And" if what == "and" else "Or", self._relations(node.values, what, node), node)
-
-    def visit_BinOp(self, node):
-        self.generic_visit(node)
-        node.left, node.right = self._wrap(node.left), self._wrap(node.right)
-        return node
-
-    def visit_UnaryOp(self, node):
-        self.generic_visit(node)
-        if isinstance(node.op, ast.Not):
-            return self._call("Not", self._relations([node.operand], "not", node), node)
-        node.operand = self._wrap(node.operand)
-        return node
-
-
-def _number(node) -> float:
-    if isinstance(node, ast.Call):  # ScalarParam(value, unit=..., ...)
-        return float(ast.literal_eval(node.args[0]))
-    return float(ast.literal_eval(node))
-
-
-def _dependency_order(assignments):
-    """gotran files may use an intermediate before the line that defines it: order by dependencies (stable)."""
-    defined = {name for name, _ in assignments}
-    deps = {name: ({n.id for n in ast.walk(node) if isinstance(n, ast.Name)} & defined) - {name} for name, node in assignments}
-    out, done, pending = [], set(), list(assignments)
-    while pending:
-        rest = [(n, e) for n, e in pending if not deps[n] <= done]
-        ready = [(n, e) for n, e in pending if deps[n] <= done]
-        if not ready:
-            raise ValueError(f"cyclic definitions: {[n for n, _ in rest]}")
-        for n, e in ready:
-            out.append((n, e))
-            done.add(n)
-        pending = rest
-    return out
 
 
 def _on_gpu() -> bool:
@@ -209,183 +81,42 @@ def _on_gpu() -> bool:
         return False
 
 
-class _Body:
-    """The body of a generated function as it is being written (the step's, a monitor selection's): the printer, the file's
-    states, parameters and time as y_k / p_k / t, the common subexpressions ``repl`` in those symbols, the ``lines`` so far and the
-    symbols they use.
-
-    ``second_of``: the body of a two-stage step's first stage.  This one then CONTINUES it -- same printer, same ``lines`` -- with
-    the same expressions at the midpoint: the states as yh_k, the time as th, and every common subexpression that depends on a
-    state or on the time under a name of its own (x_7 -> xh_7).  One that depends on parameters alone keeps its name and is not
-    printed again where the first stage has it."""
-
-    def __init__(self, model, repl, second_of=None):
-        import sympy
-
-        y, p = model._sym["y"], model._sym["p"]
-        self.ns, self.np, self.nin = len(y), len(p), len(model._sym["m"])
-        # a missing variable is input row S + j of the state array: y_{S+j} in either stage (held at its step-start value)
-        inputs = {s: sympy.Symbol(f"y_{self.ns + j}") for j, s in enumerate(model._sym["m"])}
-        if second_of is None:
-            self.pr, self.uses_mod = model._printer()
-            self.sub = {s: sympy.Symbol(f"y_{k}") for k, s in enumerate(y)}
-            self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-            self.sub[model._sym["t"]] = sympy.Symbol("t")
-            self.sub.update(inputs)
-            self.temp = {lhs: e.xreplace(self.sub) for lhs, e in repl}
-            self.lines = []
-        else:
-            self.pr, self.uses_mod, self.lines = second_of.pr, second_of.uses_mod, second_of.lines
-            moving = {s for s in y} | {model._sym["t"]}
-            for lhs, e in repl:  # (in definition order: what a moving temporary is used in moves too)
-                if e.free_symbols & moving:
-                    moving.add(lhs)
-            self.sub = {s: sympy.Symbol(f"yh_{k}") for k, s in enumerate(y)}
-            self.sub.update({s: sympy.Symbol(f"p_{k}") for k, s in enumerate(p)})
-            self.sub[model._sym["t"]] = sympy.Symbol("th")
-            self.sub.update({lhs: sympy.Symbol(str(lhs).replace("x_", "xh_")) for lhs, _ in repl if lhs in moving})
-            self.sub.update(inputs)
-            self.temp = {lhs.xreplace(self.sub): e.xreplace(self.sub) for lhs, e in repl}
-        self.emit, self.emitted = model._emitter(self.temp, self.pr, self.lines)
-        if second_of is not None:
-            self.emitted |= second_of.emitted  # (the parameter-only temporaries the first stage has defined)
-        self.used = set()
-
-    def expr(self, e):
-        """``e`` in the body's symbols: the temporaries it needs are emitted, its symbols noted as used."""
-        import sympy
-
-        e = sympy.sympify(e).xreplace(self.sub)
-        self.emit(e)
-        self.used |= e.free_symbols
-        return e
-
-    def loads(self, every_state: bool):
-        """The load lines of the states (all of them, or the used ones), of the used input rows (a model's missing variables:
-        rows S .. S + M - 1, read and never stored) and of the used parameters, once the body is written."""
-        import sympy
-
-        for e in self.emitted:
-            if e in self.temp:  # (a second stage's set also names the first stage's temporaries: that body accounts for them)
-                self.used |= self.temp[e].free_symbols
-        return ([f"    const double y_{k} = io.load({k});" for k in range(self.ns + self.nin)
-                 if (every_state and k < self.ns) or sympy.Symbol(f"y_{k}") in self.used],
-                [f"    const double p_{k} = p[{k}];" for k in range(self.np) if sympy.Symbol(f"p_{k}") in self.used])
-
-
 class OdeFileModel(DeviceModel):
     """A :class:`DeviceModel` generated from an ``.ode`` file (see the module docstring)."""
 
     def __init__(self, path, scheme="generalized_rush_larsen", v_name=None, name=None, fast_exp=True, missing=None, missing_ranges=None):
-        import sympy
-
-        self.fast_exp = bool(fast_exp)
+        from . import _ode_cxx  # (SymPy is needed from here on, not by `import beat`)
+        from ._ode_numpy import NumpyTwin
+        from ._ode_symbolic import OdeSystem
 
         scheme = _SCHEME_ALIASES.get(scheme, scheme)
         if scheme not in _SCHEMES:
             raise ValueError(f"scheme must be one of {_SCHEMES}, got {scheme!r}")
-        self.path = Path(path)
-        self.scheme = scheme
-        text = self.path.read_text()
-        states, params, assigns = {}, {}, []
-        for kind, nm, node in _walk(text, str(self.path)):
-            if kind == "call" and nm in ("states", "parameters"):
-                target = states if nm == "states" else params
-                for kw in node.keywords:
-                    target[kw.arg] = _number(kw.value)
-            elif kind == "assign":
-                assigns.append((nm, node))
-            # (expressions(...), component(...), comment(...): grouping only)
-        if not states:
-            raise ValueError(f"{self.path}: no states(...) found")
-        assigns = _dependency_order(assigns)
-        self.missing_names = self._missing_names(missing, states, params, assigns)
+        self.path, self.scheme, self.fast_exp = Path(path), scheme, bool(fast_exp)
+        source = parse_ode(self.path, missing)
+        self.missing_names = source.missing_names
         self.missing_ranges = {nm: (0.0, 1.0) for nm in self.missing_names}
         for nm, (lo, hi) in (missing_ranges or {}).items():
             if nm not in self.missing_ranges:
                 raise ValueError(f"{self.path}: missing_ranges names {nm!r}, which is not a missing variable of this model")
             self.missing_ranges[nm] = (float(lo), float(hi))
         if v_name is None:
-            v_name = next((s for s in states if s.lower() in ("v", "vm", "v_m")), None)
-        if v_name is not None and v_name not in states:
+            v_name = next((s for s in source.states if s.lower() in ("v", "vm", "v_m")), None)
+        if v_name is not None and v_name not in source.states:
             raise KeyError(f"{v_name!r} is not a state of {self.path.name}")
-        stem = "".join(c if c.isalnum() else "_" for c in (name or self.path.stem))
-        super().__init__(f"{stem}_{scheme}", -1, states, params, v_name)
-        # ---- symbolic right-hand sides and total self-derivatives
-        ysym = {s: sympy.Symbol(s, real=True) for s in states}
-        psym = {p: sympy.Symbol(p, real=True) for p in params}
-        msym = {m: sympy.Symbol(m, real=True) for m in self.missing_names}  # constant over a step: J_kk never differentiates by one
-        tsym, dtsym = sympy.Symbol("time", real=True), sympy.Symbol("dt", real=True)
-
-        def piecewise(c, a, b):
-            return sympy.Piecewise((a, c), (b, True))
-
-        ns = {nm: getattr(sympy, _SYMPY_NAMES.get(nm, nm)) for nm in _FUNCTIONS if nm != "Conditional"}
-        ns.update({"Conditional": piecewise, "time": tsym, "t": tsym, "pi": sympy.pi,
-                   "_indicator": lambda c: sympy.Piecewise((sympy.Integer(1), c), (sympy.Integer(0), True))})
-        ns.update(psym)
-        ns.update(msym)
-        ns.update(ysym)
-        rhs, line, assigned = {}, {}, {}
-        for nm, node in assigns:
-            _check_expression(node, str(self.path), set(_FUNCTIONS))
-            node = ast.fix_missing_locations(_ComparisonsAsNumbers(str(self.path)).visit(node))
-            try:
-                expr = sympy.sympify(eval(compile(ast.Expression(node), str(self.path), "eval"), {"__builtins__": {}}, ns))
-            except Exception as exc:  # noqa: BLE001
-                raise ValueError(f"{self.path}: cannot turn `{nm} = ...` into an expression: {exc}") from exc
-            ns[nm] = assigned[nm] = expr
-            if nm.startswith("d") and nm.endswith("_dt") and nm[1:-3] in states:
-                rhs[nm[1:-3]], line[nm[1:-3]] = expr, node.lineno
-        missing = [s for s in states if s not in rhs]
-        if missing:
-            raise ValueError(f"{self.path}: no d<state>_dt for {missing}")
-        names = list(states)
-        f = [rhs[s] for s in names]
-        J = [self._self_derivative(rhs[s], ysym[s], f"{self.path}:{line[s]}: d{s}_dt") if scheme in _RUSH_LARSEN
-             else sympy.Integer(0) for s in names]
-        self._grl = [bool(j != 0) for j in J]
-        repl, red = sympy.cse(f + J, symbols=sympy.numbered_symbols("x_"), optimizations="basic")
-        self._sym = dict(y=[ysym[s] for s in names], p=[psym[p] for p in params], m=[msym[m] for m in self.missing_names], t=tsym, dt=dtsym, repl=repl,
-                         f=red[: len(names)], J=red[len(names):])
+        self._stem = "".join(c if c.isalnum() else "_" for c in (name or self.path.stem))
+        super().__init__(f"{self._stem}_{scheme}", -1, source.states, source.parameters, v_name)
+        self._system = OdeSystem.from_source(source, scheme)
+        self._grl = self._system.grl  # which J_kk are not identically zero: the states that take the exponential update
+        self._twin = NumpyTwin(self._system, scheme)
         # every assignment of the file, in dependency order: what monitor_values / numpy_monitor can be asked for
-        self.monitor_names = tuple(assigned)
-        self._mon_expr = assigned
-        self._mon_numpy_fn = None
+        self.monitor_names = tuple(self._system.assigned)
         self._monitors = {}       # names of one launch -> the library's monitor id (beat_ode_monitor_register), once self-checked
-        self._stem = stem
-        self._numpy_fn = None
         self._registered = None   # the library's id, once the compiled kernel has passed _self_check
         self._library_id = None   # the id beat_ode_model_register gave (the source is handed over once per process)
-        self.source = self._cxx(stem)
+        self.cxx_name, self.source = _ode_cxx.step_struct(self._system, scheme, self._stem, self.state_index(v_name) if v_name else None,
+                                                          _ode_cxx.CxxOptions.from_environment(self.fast_exp))
         self.key = f"{self.cxx_name}"
-
-    def _missing_names(self, missing, states, params, assigns) -> tuple:
-        """The names ``missing`` declares (None: none; "auto": every free name of the file, sorted), checked: a ValueError names the
-        file and the name that is declared or assigned in the file, reserved, used by nothing, or given twice."""
-        if missing is None:
-            return ()
-        assigned = {nm for nm, _ in assigns}
-        reserved = set(_FUNCTIONS) | set(_CONSTANTS) | {"dt"}
-        used = {n.id for _, node in assigns for n in ast.walk(node) if isinstance(n, ast.Name)}
-        if isinstance(missing, str):
-            if missing != "auto":
-                missing = (missing,)
-            else:
-                return tuple(sorted(used - set(states) - set(params) - assigned - reserved))
-        out = []
-        for nm in missing:
-            if not isinstance(nm, str) or not nm.isidentifier():
-                raise ValueError(f"{self.path}: {nm!r} is not the name of a missing variable")
-            if nm in out:
-                raise ValueError(f"{self.path}: missing variable {nm!r} is given twice")
-            for what, where in (("a state", states), ("a parameter", params), ("assigned", assigned), ("a reserved name", reserved)):
-                if nm in where:
-                    raise ValueError(f"{self.path}: {nm!r} cannot be a missing variable: it is {what} in the file")
-            if nm not in used:
-                raise ValueError(f"{self.path}: missing variable {nm!r} is used by no expression of the file")
-            out.append(nm)
-        return tuple(out)
 
     @property
     def num_missing_variables(self) -> int:
@@ -397,33 +128,29 @@ class OdeFileModel(DeviceModel):
         return self.num_states + self.num_missing_variables
 
     def missing_index(self, name: str) -> int:
-        try:
-            return self.missing_names.index(name)
-        except ValueError:
-            raise KeyError(f"Unknown missing variable {name}") from None
+        if name not in self.missing_names:
+            raise KeyError(f"Unknown missing variable {name}")
+        return self.missing_names.index(name)
 
     def init_missing_values(self, **values) -> np.ndarray:
         """An (M,) vector of the missing variables in the order of ``missing_names``: 0.0 but for the ones given by name."""
-        d = dict.fromkeys(self.missing_names, 0.0)
-        for k, v in values.items():
-            if k not in d:
+        for k in values:
+            if k not in self.missing_names:
                 raise KeyError(f"Unknown missing variable {k}")
-            d[k] = v
-        return np.array([d[k] for k in self.missing_names], dtype=np.float64)
+        return np.array([values.get(k, 0.0) for k in self.missing_names], dtype=np.float64)
 
     def _rows(self, states, missing_variables):
         """(S + M, N) rows for the kernel -- ``states`` (S,) or (S, N) above ``missing_variables`` (M,) or (M, N) -- and whether
         ``states`` was (S,).  TypeError where the model has missing variables and gets none, or has none and gets some."""
         m = self.num_missing_variables
-        if m == 0:
-            if missing_variables is not None:
-                raise TypeError(f"{self.name} has no missing variables: missing_variables must not be given")
-            y = np.asarray(states, dtype=np.float64)
-            return y.reshape(y.shape[0], -1), y.ndim == 1
-        if missing_variables is None:
+        if m == 0 and missing_variables is not None:
+            raise TypeError(f"{self.name} has no missing variables: missing_variables must not be given")
+        if m and missing_variables is None:
             raise TypeError(f"{self.name} has the missing variables {self.missing_names}: missing_variables=... is required")
         y = np.asarray(states, dtype=np.float64)
         y2 = y.reshape(y.shape[0], -1)
+        if m == 0:
+            return y2, y.ndim == 1
         if y2.shape[0] != self.num_states:
             raise ValueError(f"{self.name} has {self.num_states} states, got {y2.shape[0]}")
         c = np.asarray(missing_variables, dtype=np.float64)
@@ -431,227 +158,11 @@ class OdeFileModel(DeviceModel):
             raise ValueError(f"missing_variables must have shape ({m},) or ({m}, {y2.shape[1]}), got {c.shape}")
         return np.concatenate([y2, np.broadcast_to(c.reshape(m, -1), (m, y2.shape[1]))], axis=0), y.ndim == 1
 
-    @staticmethod
-    def _self_derivative(expr, y, where: str):
-        """d expr / d y, or a ValueError naming the equation: floor and % have no derivative the generator can print (SymPy
-        leaves ``Derivative(floor(y), y)`` in the result or refuses outright), and none is made up for them here."""
-        import sympy
-
-        try:
-            j = sympy.diff(expr, y)
-        except Exception as exc:  # noqa: BLE001
-            raise ValueError(f"{where}: cannot differentiate with respect to the state {y}: {exc}") from exc
-        if j.has(sympy.Derivative, sympy.Subs):
-            raise ValueError(f"{where}: the derivative with respect to the state {y} is not one the generator can print "
-                             f"({next(iter(j.atoms(sympy.Derivative, sympy.Subs)))}): floor and % of a state have none")
-        return j
-
-    # ------------------------------------------------------------------------------------------------ C++
-    def _printer(self):
-        """The C++ printer of the generated code (the step's and the monitors') and the list it notes a use of ``%`` in."""
-        import os
-
-        from sympy.printing.c import C99CodePrinter
-
-        class Printer(C99CodePrinter):
-            def _print_Pow(self, expr):  # small integer powers as products (pow() on fp64 is a long software routine)
-                b, e = expr.as_base_exp()
-                if e.is_Integer and 2 <= int(e) <= 4:
-                    pb = self.parenthesize(b, 1000)  # as an atom
-                    return "(" + "*".join([pb] * int(e)) + ")"
-                if e.is_Integer and -4 <= int(e) <= -1:
-                    pb = self.parenthesize(b, 1000)
-                    return "(1.0/(" + "*".join([pb] * (-int(e))) + "))"
-                return super()._print_Pow(expr)
-
-            def _print_Mod(self, expr):  # Python's %, as NumPy evaluates it (np.mod): the result takes the divisor's sign
-                uses_mod.append(True)
-                a, b = expr.args
-                return f"beat_mod({self._print(a)}, {self._print(b)})"
-
-            def _print_Piecewise(self, expr):
-                # BRANCH-FREE: both arms evaluated, the result selected (v_cndmask).  As `c ? a : b` with the arms inline the
-                # compiler builds divergent branches; a heavily spilled kernel (the reference's ToR-ORd files generate 250 - 300 spilled
-                # SGPRs and 450 spilled VGPRs) then reloads registers it spilled under another lane mask -- wrong values on exactly the
-                # nodes that take the other arm, in the states behind that arm, different from run to run (ROCm 7.2; seen in round 1
-                # on the generated ToR-ORd kernel and reproduced in round 5: tools/diag_spill.py, profiles/r05_generated_spills.md).
-                # A lane computes both arms of a divergent branch anyway.
-                if os.environ.get("BEAT_ODE_BRANCHES") == "1":  # the form that was seen miscompiled (tests of the self checks)
-                    return super()._print_Piecewise(expr)
-                args = list(expr.args)
-                out = self._print(args[-1][0])
-                if args[-1][1] != True:  # noqa: E712 -- no default arm: what C's chained ?: would leave undefined
-                    out = f"beat_sel({self._print(args[-1][1])}, {out}, 0.0)"
-                for e, c in reversed(args[:-1]):
-                    out = f"beat_sel({self._print(c)}, {self._print(e)}, {out})"
-                return out
-
-        # exp(): the library's table-driven evaluation (FastMath::exp of csrc/ionic_models.h, what the shipped models use: 13 VALU
-        # instructions, <= 1 ulp, the 256-entry table in LDS) with the argument kept inside double range -- or libm's
-        uses_mod = []
-        return Printer({"contract": False, "user_functions": {"exp": "fexp" if self.fast_exp else "exp"}}), uses_mod
-
-    @staticmethod
-    def _emitter(temp, pr, lines):
-        """``emit(expr)``: the common subexpressions ``expr`` needs and that are not out yet, appended to ``lines`` depth first --
-        a temporary is defined next to its first use -- and the set of those emitted so far."""
-        emitted = set()
-
-        def emit(expr):
-            stack = [(sym, False) for sym in sorted(expr.free_symbols, key=str, reverse=True) if sym in temp]
-            while stack:
-                sym, done = stack.pop()
-                if sym in emitted:
-                    continue
-                if done:
-                    emitted.add(sym)
-                    lines.append(f"    const double {sym} = {pr.doprint(temp[sym])};")
-                    continue
-                stack.append((sym, True))
-                for dep in sorted(temp[sym].free_symbols, key=str, reverse=True):
-                    if dep in temp and dep not in emitted:
-                        stack.append((dep, False))
-
-        return emit, emitted
-
-    def _cxx_helpers(self, uses_mod) -> str:
-        """The lambdas the printed expressions call (fexp, beat_sel, beat_mod), as the first lines of a generated function body."""
-        return (("    // (what libm / NumPy give everywhere: NaN stays NaN, overflow is inf, underflow goes through the subnormals to 0)\n"
-                 "    // (k = round(x 256 / ln 2) must fit 32 bits: the clamp; inside it v_ldexp_f64 underflows to 0 through the subnormals and\n"
-                 "    // overflows to inf as libm does; the clamp turns a NaN argument into a number, hence the select)\n"
-                 "    const auto fexp = [&fm](double x) { const double e = fm.exp(fmin(fmax(x, -1.0e6), 1.0e3)); return x != x ? x : e; };\n" if self.fast_exp else "")
-                + "    const auto beat_sel = [](bool c, double a, double b) { return c ? a : b; };\n"
-                + ("    // (a % b with Python's and NumPy's meaning: fmod's result moved by b where it has the other sign; a zero takes b's sign)\n"
-                   "    const auto beat_mod = [](double a, double b) {\n"
-                   "      const double m = fmod(a, b);\n"
-                   "      return m != 0.0 ? ((m < 0.0) != (b < 0.0) ? m + b : m) : copysign(0.0, b);\n"
-                   "    };\n" if uses_mod else ""))
-
-    def _cxx_one_stage(self, body, order, exp_name) -> None:
-        """The lines of GRL1's and forward Euler's step, appended to ``body``'s (states in ``order``): per state its temporaries, the
-        update and its store."""
-        import os
-
-        pr, lines = body.pr, body.lines
-        for k in order:
-            fk, jk = body.expr(self._sym["f"][k]), body.expr(self._sym["J"][k])
-            if self._grl[k]:
-                if os.environ.get("BEAT_ODE_BRANCHES") == "1":  # (the former output: see _print_Piecewise)
-                    lines.append(f"    {{ const double f = {pr.doprint(fk)}; const double J = {pr.doprint(jk)};\n"
-                                 f"      io.store({k}, y_{k} + (fabs(J) > 1e-8 ? f / J * ({exp_name}(J * dt) - 1.0) : f * dt)); }}")
-                    continue
-                lines.append(f"    {{ const double f = {pr.doprint(fk)}; const double J = {pr.doprint(jk)};\n"
-                             f"      io.store({k}, y_{k} + beat_sel(fabs(J) > 1e-8, f / J * ({exp_name}(J * dt) - 1.0), f * dt)); }}")
-            else:
-                lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
-
-    def _cxx_two_stages(self, body, order, exp_name) -> None:
-        """The lines of GRL2's step, appended to ``body``'s (states in ``order``).  Stage 1, state by state: f_k and J_kk at
-        (y, t) and the midpoint value yh_k = y_k + phi(J, dt/2) f (GRL1 over half a step; y_k + dt/2 f where J_kk is
-        identically zero) -- f and J are scoped to their state, so what stays live is the NS values yh_k next to the loaded y_k.
-        Stage 2, in the one-stage schemes' order: the same expressions at (yh, t + dt/2) under names of their own
-        (``_Body(second_of=...)``), b = f + J (y_k - yh_k), and y_k + phi(J, dt) b stored as soon as it is final.  y_k is the
-        value loaded at the top of the step in both stages: nothing is loaded a second time (on the fused route the potential's
-        load applies the pending update, and the row is overwritten in place)."""
-        import os
-
-        pr, lines = body.pr, body.lines
-        branches = os.environ.get("BEAT_ODE_BRANCHES") == "1"  # (the former output: see _print_Piecewise)
-
-        def phi_times(h):  # phi(J, h) f in GRL1's operation order
-            grl, euler = f"f / J * ({exp_name}(J * {h}) - 1.0)", f"f * {h}"
-            return f"(fabs(J) > 1e-8 ? {grl} : {euler})" if branches else f"beat_sel(fabs(J) > 1e-8, {grl}, {euler})"
-
-        lines.append("    const double hdt = 0.5 * dt, th = t + hdt;  // stage 1: GRL1 over half a step, from (y, t)")
-        for k in order:
-            fk, jk = body.expr(self._sym["f"][k]), body.expr(self._sym["J"][k])
-            if self._grl[k]:
-                lines.append(f"    double yh_{k}; {{ const double f = {pr.doprint(fk)}; const double J = {pr.doprint(jk)};\n"
-                             f"      yh_{k} = y_{k} + {phi_times('hdt')}; }}")
-            else:
-                lines.append(f"    const double yh_{k} = y_{k} + hdt * ({pr.doprint(fk)});")
-        lines.append("    // stage 2: linearised about (yh, th), integrated from y over the whole step")
-        second = _Body(self, self._sym["repl"], second_of=body)
-        if os.environ.get("BEAT_ODE_EMIT") == "global":
-            for lhs in second.temp:
-                second.emit(lhs)
-        for k in order:
-            fk, jk = second.expr(self._sym["f"][k]), second.expr(self._sym["J"][k])
-            if self._grl[k]:
-                lines.append(f"    {{ const double J = {pr.doprint(jk)}; const double f = ({pr.doprint(fk)}) + J * (y_{k} - yh_{k});\n"
-                             f"      io.store({k}, y_{k} + {phi_times('dt')}); }}")
-            else:
-                lines.append(f"    io.store({k}, y_{k} + dt * ({pr.doprint(fk)}));")
-        second.loads(every_state=False)
-        rows = {f"y_{k}" for k in range(body.ns, body.ns + body.nin)}  # (the second stage reads the input rows the first one loaded)
-        body.used |= {s for s in second.used if str(s).startswith("p_") or str(s) in rows}
-
-    def _cxx(self, stem: str) -> str:
-        import os
-
-        exp_name = "fexp" if self.fast_exp else "exp"
-        # Order: state by state, each one's common subexpressions right ahead of its update (depth first, those not yet emitted),
-        # then the update and its store -- a temporary is defined next to its first use and a state's result leaves the registers
-        # when it is final.  (All temporaries first and all updates last -- the order the elimination returns them in -- keeps every
-        # one of them and all NS results alive to the end: the 48-state test model needed 256 + 256 registers and 450 B of scratch
-        # per lane that way.)
-        body = _Body(self, self._sym["repl"])
-        lines, ns_, np_ = body.lines, body.ns, body.np
-        vi = self.state_index(self.v_name) if self.v_name else 0
-        order = list(range(ns_))
-        if os.environ.get("BEAT_ODE_V_LAST", "1") == "1" and self.v_name:  # the potential's equation sums every current: last, when the currents exist
-            order = [k for k in order if k != vi] + [vi]
-        if os.environ.get("BEAT_ODE_EMIT") == "global":  # every temporary first, in the elimination's order (tests: the heavily spilled form)
-            for lhs in body.temp:
-                body.emit(lhs)
-            order = list(range(ns_))
-        if self.scheme == "generalized_rush_larsen_2":
-            self._cxx_two_stages(body, order, exp_name)
-        else:
-            self._cxx_one_stage(body, order, exp_name)
-        loads, pl = body.loads(every_state=True)
-        # (the missing variables are part of the name -- it is the key of the compiled kernel's cache; without any, the name of before)
-        digest = hashlib.sha1(("\n".join(lines) + self.scheme + ("".join(f"|{nm}" for nm in self.missing_names))).encode()).hexdigest()[:12]
-        self.cxx_name = f"Ode_{stem}_{digest}"
-        nin = body.nin  # (rows NS - NIN .. NS - 1 are inputs: loaded where used, never stored; a model without any prints as before)
-        return (f"// generated by beat.models.from_ode from {self.path.name} ({self.scheme}): {ns_} states, {np_} parameters"
-                + (f", {nin} missing variables ({', '.join(self.missing_names)}) as input rows {ns_} .. {ns_ + nin - 1}" if nin else "") + "\n"
-                f"struct {self.cxx_name} {{\n"
-                f"  static constexpr int NS = {ns_ + nin}, NP = {max(np_, 1)}, V_INDEX = {vi};\n"
-                + (f"  static constexpr int NIN = {nin};\n" if nin else "") +
-                "  static constexpr bool REGISTER_LOOP = true;\n"
-                "  static constexpr int WAVES = 1, WAVES_PER_NODE = 1;\n"
-                "  struct Derived { double unused; };\n"
-                "  template <class P> __host__ __device__ static Derived derive(const P&) { return Derived{0.0}; }\n"
-                "  template <class IO, class P>\n"
-                "  __device__ static __forceinline__ void step(const IO& io, const P& p, const Derived&, const FastMath& fm, double t, double dt) {\n"
-                + self._cxx_helpers(body.uses_mod)
-                + "\n".join(loads + pl + lines) + "\n  }\n};\n")
-
     def _monitor_cxx(self, names):
-        """(struct name, source) of ``Mon_<stem>_<digest>`` for csrc/beat_ode_kernel.h's ode_monitor_kernel: the assignments ``names``
-        (at most _hip.MAX_MONITORS) evaluated from the node's states and parameters and stored to output rows 0 .. M-1.  Common
-        subexpressions are eliminated over the SELECTION alone; printer, helpers and the order -- a temporary next to its first
-        use, an output stored as soon as it is final -- are the step's; only the states and parameters the selection uses are
-        loaded."""
-        import sympy
+        """``_ode_cxx.monitor_struct`` for ``names`` (at most _hip.MAX_MONITORS), with the BEAT_ODE_* switches as they are now."""
+        from . import _ode_cxx
 
-        repl, red = sympy.cse([self._mon_expr[nm] for nm in names], symbols=sympy.numbered_symbols("x_"), optimizations="basic")
-        body = _Body(self, repl)
-        lines = body.lines
-        for j, e in enumerate(red):
-            lines.append(f"    out.store({j}, {body.pr.doprint(body.expr(e))});  // {names[j]}")
-        loads, pl = body.loads(every_state=False)
-        digest = hashlib.sha1("\n".join(loads + pl + lines).encode()).hexdigest()[:12]
-        name = f"Mon_{self._stem}_{digest}"
-        return name, (f"// generated by beat.models.from_ode from {self.path.name}: {len(names)} monitored values, {len(loads)} of {body.ns + body.nin} "
-                      f"{'state and input rows' if body.nin else 'states'} read\n"
-                      f"struct {name} {{\n"
-                      f"  static constexpr int NS = {body.ns + body.nin}, NP = {max(body.np, 1)}, NM = {len(names)};\n"
-                      "  template <class IO, class P, class OUT>\n"
-                      "  __device__ static __forceinline__ void eval(const IO& io, const P& p, const FastMath& fm, double t, const OUT& out) {\n"
-                      + self._cxx_helpers(body.uses_mod)
-                      + "\n".join(loads + pl + lines) + "\n  }\n};\n")
+        return _ode_cxx.monitor_struct(self._system, names, self._stem, _ode_cxx.CxxOptions.from_environment(self.fast_exp))
 
     def monitor_sources(self, names=None):
         """[(struct name, source, names)] -- one per launch: ``names`` (None: all) in runs of at most _hip.MAX_MONITORS."""
@@ -661,84 +172,16 @@ class OdeFileModel(DeviceModel):
         return [self._monitor_cxx(names[k:k + _hip.MAX_MONITORS]) + (tuple(names[k:k + _hip.MAX_MONITORS]),)
                 for k in range(0, len(names), _hip.MAX_MONITORS)]
 
-    # ------------------------------------------------------------------------------------------------ NumPy
-    def _numpy_args(self, states, t, parameters, missing_variables=None):
-        """(states as (S, N), the arguments of a lambdified function over y + m + p + [t] -- m: the missing variables, none for
-        most models --, whether ``states`` was (S,))."""
-        rows, one_d = self._rows(states, missing_variables)
-        y2, m2 = rows[: rows.shape[0] - self.num_missing_variables], rows[rows.shape[0] - self.num_missing_variables:]
-        p = np.asarray(parameters, dtype=np.float64)  # (P,) or per node (P, N)
-        if p.ndim == 2 and p.shape[1] != y2.shape[1]:
-            raise ValueError(f"per-node parameters must have shape ({len(p)}, {y2.shape[1]}), got {p.shape}")
-        # (every argument an array of the nodes' shape: NumPy's and / or of a condition on parameters alone with one on a state
-        # would otherwise be a reduction over a ragged pair)
-        n = y2.shape[1]
-        pn = [np.broadcast_to(np.asarray(p[k], dtype=np.float64), (n,)) for k in range(len(p))]
-        return y2, [y2[k] for k in range(y2.shape[0])] + [m2[k] for k in range(m2.shape[0])] + pn + [np.full(n, float(t))], one_d
-
-    @staticmethod
-    def _numpy_printer():
-        """lambdify's NumPy printer with every constant at full precision: the stock one writes a Float with 15 significant
-        digits (0.147058823529412 for 1/6.8), which moves exp(c V) by 2e-14 of its value at V = -95 -- the generated C++ has 17."""
-        from sympy.printing.numpy import NumPyPrinter
-
-        class FullPrecision(NumPyPrinter):
-            def _print_Float(self, expr):
-                return repr(float(expr))
-
-        return FullPrecision({"fully_qualified_modules": False, "inline": True, "allow_unknown_functions": True})
-
-    def _numpy_rhs(self):
-        """The lambdified right-hand sides f and self-derivatives J (what numpy_step integrates)."""
-        import sympy
-
-        if self._numpy_fn is None:
-            s = self._sym
-            # (the common subexpressions found at construction are handed to lambdify as they are: local assignments in the generated function)
-            self._numpy_fn = sympy.lambdify(s["y"] + s["m"] + s["p"] + [s["t"]], [s["f"], s["J"]], "numpy", cse=lambda exprs: (s["repl"], exprs),
-                                            printer=self._numpy_printer())
-        return self._numpy_fn
-
     def numpy_step(self, states, t, parameters, dt, missing_variables=None):
         """One step on the HOST with NumPy: the same expressions as the kernel's (the reference's way of evaluating ``fun``).
         ``missing_variables``: (M,) or (M, N), for a model made with ``missing=`` (TypeError where such a model gets none, or
         another model gets some); held at these values through both stages of GRL2.  Returns the S states."""
-        y2, args, one_d = self._numpy_args(states, t, parameters, missing_variables)
-        ns = y2.shape[0]
-        if self.scheme == "generalized_rush_larsen_2":
-            # stage 1 is the GRL1 step over dt / 2 (forward Euler where J_kk is identically zero); stage 2 takes f and J at
-            # (yh, t + dt / 2) and integrates b = f + J (y - yh) from y over dt -- the kernel's two stages, operation by operation
-            hdt = 0.5 * dt
-            yh = self._numpy_update(y2, args, hdt)
-            mid = [yh[k] for k in range(ns)] + args[ns:-1] + [np.full(y2.shape[1], float(t) + hdt)]
-            out = self._numpy_update(y2, mid, dt, about=yh)
-        else:
-            out = self._numpy_update(y2, args, dt)
-        return out[:, 0].copy() if one_d else out
-
-    def _numpy_update(self, y2, args, dt, about=None):
-        """y + phi(J, dt) b per state (y + dt b where J_kk is identically zero), f and J evaluated at ``args``:
-        b = f, or f + J (y - about) for a linearisation about another point than y."""
-        with np.errstate(all="ignore"):
-            f, J = self._numpy_rhs()(*args)
-        out = np.empty_like(y2)
-        for k in range(y2.shape[0]):
-            fk = np.broadcast_to(np.asarray(f[k], dtype=np.float64), y2[k].shape)
-            if self._grl[k]:
-                Jk = np.broadcast_to(np.asarray(J[k], dtype=np.float64), y2[k].shape)
-                with np.errstate(all="ignore"):
-                    if about is not None:
-                        fk = fk + Jk * (y2[k] - about[k])
-                    out[k] = y2[k] + np.where(np.abs(Jk) > 1e-8, fk / np.where(Jk == 0, 1.0, Jk) * (np.exp(Jk * dt) - 1.0), fk * dt)
-            else:
-                out[k] = y2[k] + dt * fk
-        return out
+        return self._twin.step(*self._rows(states, missing_variables), t, parameters, dt)
 
     def monitor_index(self, name: str) -> int:
-        try:
-            return self.monitor_names.index(name)
-        except ValueError:
-            raise KeyError(f"Unknown monitor {name}") from None
+        if name not in self.monitor_names:
+            raise KeyError(f"Unknown monitor {name}")
+        return self.monitor_names.index(name)
 
     def _monitor_selection(self, names):
         """``names`` (None: all) as a list, each one checked."""
@@ -753,30 +196,8 @@ class OdeFileModel(DeviceModel):
 
     def numpy_monitor(self, states, t, parameters, names=None, missing_variables=None):
         """The values of the file's assignments ``names`` (None: all of ``monitor_names``) on the HOST with NumPy: (M,) for (S,)
-        states, (M, N) for (S, N); parameters (P,) or per node (P, N).  What the monitor kernel is compared with, as ``numpy_step``
-        is for the step.  The ``d<state>_dt`` rows are the right-hand sides ``numpy_step`` integrates, bit for bit (the same
-        lambdified function); every other row comes from ONE function over all assignments, so that a selection gives the numbers
-        of the matching rows of ``names=None``.  ``missing_variables``: as for ``numpy_step``."""
-        import sympy
-
-        names = self._monitor_selection(names)
-        y2, args, one_d = self._numpy_args(states, t, parameters, missing_variables)
-        n = y2.shape[1]
-        rhs_row = {f"d{s}_dt": k for k, s in enumerate(self.state_names)}
-        plain = [nm for nm in self.monitor_names if nm not in rhs_row]
-        out = np.empty((len(names), n))
-        with np.errstate(all="ignore"):
-            if any(nm in rhs_row for nm in names):
-                f, _ = self._numpy_rhs()(*args)
-            if any(nm not in rhs_row for nm in names):
-                if self._mon_numpy_fn is None:
-                    s = self._sym
-                    self._mon_numpy_fn = sympy.lambdify(s["y"] + s["m"] + s["p"] + [s["t"]], [self._mon_expr[nm] for nm in plain], "numpy", cse=True,
-                                                        printer=self._numpy_printer())
-                vals = dict(zip(plain, self._mon_numpy_fn(*args)))
-        for j, nm in enumerate(names):
-            out[j] = np.broadcast_to(np.asarray(f[rhs_row[nm]] if nm in rhs_row else vals[nm], dtype=np.float64), (n,))
-        return out[:, 0].copy() if one_d else out
+        states, (M, N) for (S, N); parameters (P,) or (P, N); ``missing_variables`` as for ``numpy_step``.  What the monitor kernel is held to."""
+        return self._twin.monitor(self._monitor_selection(names), *self._rows(states, missing_variables), t, parameters)
 
     # ------------------------------------------------------------------------------------------------ device
     def register(self) -> int:
@@ -786,9 +207,8 @@ class OdeFileModel(DeviceModel):
 
         if self._registered is None:
             if self._library_id is None:
-                lib = _hip.load()
                 mid = C.c_int(-1)
-                _hip.check(lib.beat_ode_model_register(self.cxx_name.encode(), self.source.encode(), self.num_rows,
+                _hip.check(_hip.load().beat_ode_model_register(self.cxx_name.encode(), self.source.encode(), self.num_rows,
                                                        max(self.num_parameters, 1), self.state_index(self.v_name) if self.v_name else 0,
                                                        C.byref(mid)))
                 self._library_id = int(mid.value)
@@ -824,8 +244,7 @@ class OdeFileModel(DeviceModel):
 
     def _split_rows(self, rows):
         """(the S state rows, the M input rows or None) of an (S + M, N) array."""
-        S = self.num_states
-        return rows[:S], (rows[S:] if self.missing_names else None)
+        return rows[: self.num_states], (rows[self.num_states:] if self.missing_names else None)
 
     def _numpy_step_rows(self, rows, t, parameters, dt):
         """``numpy_step`` on the kernel's (S + M, N) rows: the states advanced, the input rows as they were."""
@@ -955,8 +374,7 @@ class OdeFileModel(DeviceModel):
         with np.errstate(all="ignore"):
             scale = np.where(ok, np.abs(ref), 0.0).max(axis=1, keepdims=True)
             err = np.abs(dev - ref) / np.maximum(np.maximum(np.abs(ref), scale), 1e-300)
-        err = np.where(ok, np.where(np.isfinite(dev), err, np.inf), 0.0)
-        return err
+        return np.where(ok, np.where(np.isfinite(dev), err, np.inf), 0.0)
 
     def _monitor_self_check(self, mid: int, names) -> None:
         """A selection's PLAIN kernel instance (uniform parameters) against ``numpy_monitor`` (``_check_against_numpy``), to 1e-6 of

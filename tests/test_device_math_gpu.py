@@ -253,7 +253,7 @@ def test_host_and_device_agree_bit_for_bit(dev, host, fn):
 
 
 def test_generated_model_fexp_against_mpmath(tmp_path):
-    """The exp wrapper generated models call (beat/models/ode_file.py: fexp = FastMath::exp of the clamped argument, NaN kept):
+    """The exp wrapper generated models call (beat/models/_ode_cxx.py: fexp = FastMath::exp of the clamped argument, NaN kept):
     forward Euler on dx/dt = 0, dy/dt = exp(x) from y = 0 with dt = 1 gives y' = fexp(x) exactly.  x over [-1e6, 1e3] and the
     exp edge points: <= 1.5 ulp (1.5 * 2^-1074 subnormal), 0 below -745.13, inf above 709.78, NaN for NaN."""
     from beat.models import from_ode

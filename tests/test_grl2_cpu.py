@@ -2,9 +2,8 @@
 
 The two stages in mpmath (tests/_grl2_ref.py, on the independent evaluation of the file in tests/_ode_mp.py) against the NumPy
 twin (``numpy_step``) and against the generated C++ struct built for the host; closed forms; the cross-compile for gfx950; the
-observed order of the twin on a paced single cell and in a Strang-split cable; and the sources of the existing schemes, which
-this scheme must leave as they were."""
-import hashlib
+observed order of the twin on a paced single cell and in a Strang-split cable.  (The sources of every scheme are pinned in
+tests/test_ode_sources_cpu.py.)"""
 import os
 import shutil
 import subprocess
@@ -104,13 +103,13 @@ def test_first_stage_of_the_twin_is_the_grl1_twin_over_half_a_step(monkeypatch):
     Y = M.language_points(two.state_names, 30, seed=5)
     P = M.language_parameters(two, Y.shape[1], seed=6)
     seen = []
-    real = type(two)._numpy_update
+    real = type(two._twin).update
 
     def spy(self, y2, args, dt, about=None):
         seen.append(about)
         return real(self, y2, args, dt, about=about)
 
-    monkeypatch.setattr(type(two), "_numpy_update", spy)
+    monkeypatch.setattr(type(two._twin), "update", spy)
     with np.errstate(all="ignore"):
         two.numpy_step(Y, 13.7, P, DT)
     assert len(seen) == 2 and seen[0] is None
@@ -261,26 +260,3 @@ def test_order_of_the_twin_in_a_strang_cable():
     ref = run(GRL2, 0.05 / 64)
     errors = {s: [float(np.max(np.abs(run(s, dt) - ref))) for dt in (0.05, 0.025, 0.0125)] for s in (GRL1, GRL2)}
     R.assert_second_against_first_order(errors[GRL1], errors[GRL2], "Strang cable")
-
-
-# (struct name, sha256 of the source) of the existing schemes, computed from the commit before GRL2 was added
-PARENT_SOURCES = {
-    ("small_cell", GRL1, True): ("Ode_small_cell_4a86df8afe8b", "dc7815471a235b46f3c1e2c9a3a8fa7641b056da7c1f57a90c4a44fe016dcbbf"),
-    ("small_cell", GRL1, False): ("Ode_small_cell_d9e4a5c04f23", "a7209c00315f63ddd6063c8dc008815eea6781c40e47fc9b70c279633892358b"),
-    ("small_cell", "forward_euler", True): ("Ode_small_cell_d16b21dfe508", "cc3543851725af9261c76c404a4f3e7e253cf5abeb1513ed648b9582fd2519a0"),
-    ("small_cell", "forward_euler", False): ("Ode_small_cell_7f7373f51d3a", "51729be0c5b314c8ec56154a825377f72575ebef6a49a0afd9d583880f53215e"),
-    ("big_cell", GRL1, True): ("Ode_big_cell_1df4f33e4540", "29511b037644b8919c91051d2310a0fd033f49a371bb815b084a7a9084cabdbc"),
-    ("big_cell", GRL1, False): ("Ode_big_cell_00ab91ead402", "1ab965e184e5988353b7bcae5e801e89544861a998c0dc6f71ee24263a7f1934"),
-    ("big_cell", "forward_euler", True): ("Ode_big_cell_97d90ec5c42e", "bdbf1255da1ed6d58e95a26af6bbe753277ca2d935397ed14cbd8660b5a5e9df"),
-    ("big_cell", "forward_euler", False): ("Ode_big_cell_2d501dcfaf1b", "48dd22524ea05319d60eb019a59e4dd4b4f6c6f40256e26d8e8d9d70876c2c11"),
-}
-
-
-def test_existing_schemes_generate_what_they_generated_before():
-    """``source`` (by its SHA-256) and ``cxx_name`` of small_cell and big_cell under GRL1 and forward Euler, with either exp."""
-    from beat.models import from_ode
-
-    for (stem, scheme, fast), (name, digest) in PARENT_SOURCES.items():
-        model = from_ode(ROOT / "tests" / "data" / f"{stem}.ode", scheme=scheme, fast_exp=fast)
-        assert model.cxx_name == name, (stem, scheme, fast)
-        assert hashlib.sha256(model.source.encode()).hexdigest() == digest, (stem, scheme, fast)

@@ -54,18 +54,18 @@ def _check(got, Y, ref, names, bound_cr, bound_tr, what):
 def test_language_cell_uses_every_construct_the_generator_admits():
     """The coverage guard: every callable and constant of the generator's name table and every node type its expression check
     admits is used in tests/data/language_cell.ode -- a construct added to the generator without a probe fails here."""
-    from beat.models import ode_file
+    from beat.models import _ode_parse, from_ode
 
     tree = ast.parse(M.LANGUAGE_CELL.read_text())
     values = [node.value for node in tree.body if isinstance(node, ast.Assign)]
     used_types = {type(n) for v in values for n in ast.walk(v)}
     used_names = {n.id for v in values for n in ast.walk(v) if isinstance(n, ast.Name)}
-    assert set(ode_file._EXPR_NODES) - used_types == set()
-    assert set(ode_file._FUNCTIONS) - used_names == set()
-    assert set(ode_file._CONSTANTS) - used_names == set()
-    assert set(M.FUNCTIONS) == set(ode_file._FUNCTIONS)  # (the reference knows each of them, and no more)
+    assert set(_ode_parse._EXPR_NODES) - used_types == set()
+    assert set(_ode_parse._FUNCTIONS) - used_names == set()
+    assert set(_ode_parse._CONSTANTS) - used_names == set()
+    assert set(M.FUNCTIONS) == set(_ode_parse._FUNCTIONS)  # (the reference knows each of them, and no more)
     # the parameter given as ScalarParam(value, unit=...) is read as its value
-    model = ode_file.from_ode(M.LANGUAGE_CELL)
+    model = from_ode(M.LANGUAGE_CELL)
     assert model.parameter_defaults["k_dec"] == 2.0 and model.parameter_defaults["period"] == 5.0
 
 
@@ -131,23 +131,15 @@ def test_mod_is_python_and_numpy_mod_bit_for_bit(tmp_path):
     assert got[2][0] == 2.0 and got[2][1] == -2.0
 
 
-def test_parent_sources_of_the_small_and_big_cells_are_unchanged():
-    """The generator's C++ for the existing model files is byte for byte what it was before ``%``, ``==`` / ``!=``, chained
-    comparisons and ``and`` / ``or`` / ``not`` were given their meaning: the digests in the struct names."""
+def test_models_without_percent_get_no_mod_helper():
+    """The small and the big cell use no ``%``: neither scheme's source, with either exp, names the helper.  (That their sources
+    are byte for byte what they were is tests/test_ode_sources_cpu.py's.)"""
     from beat.models import from_ode
 
-    want = {("small_cell", "generalized_rush_larsen", True): "Ode_small_cell_4a86df8afe8b",
-            ("small_cell", "generalized_rush_larsen", False): "Ode_small_cell_d9e4a5c04f23",
-            ("small_cell", "forward_euler", True): "Ode_small_cell_d16b21dfe508",
-            ("small_cell", "forward_euler", False): "Ode_small_cell_7f7373f51d3a",
-            ("big_cell", "generalized_rush_larsen", True): "Ode_big_cell_1df4f33e4540",
-            ("big_cell", "generalized_rush_larsen", False): "Ode_big_cell_00ab91ead402",
-            ("big_cell", "forward_euler", True): "Ode_big_cell_97d90ec5c42e",
-            ("big_cell", "forward_euler", False): "Ode_big_cell_2d501dcfaf1b"}
-    for (stem, scheme, fast), name in want.items():
-        model = from_ode(ROOT / "tests" / "data" / f"{stem}.ode", scheme=scheme, fast_exp=fast)
-        assert model.cxx_name == name, (stem, scheme, fast)
-        assert "beat_mod" not in model.source
+    for path in (SMALL, BIG):
+        for scheme in SCHEMES:
+            for fast in (True, False):
+                assert "beat_mod" not in from_ode(path, scheme=scheme, fast_exp=fast).source, (path.name, scheme, fast)
 
 
 @pytest.mark.parametrize("line, match", [
