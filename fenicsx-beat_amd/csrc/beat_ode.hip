@@ -5,6 +5,7 @@
 // when the transmembrane potential is mirrored into the PDE vector (dev_v_copy).
 #include "beat_ode_kernel.h"
 #include "beat_ode_jit.h"
+#include "beat_ode_grid.h"
 
 #include <functional>
 
@@ -101,20 +102,21 @@ static unsigned ode_grid(int64_t n, int num_states) {
     const char* e = std::getenv("BEAT_ODE_TILE_MIN_STATES");
     return e ? std::atoi(e) : 12;
   }();
-  const int grid_cap = grid_cap_env >= 0 ? grid_cap_env : (num_states >= tile_min_states ? 0 : 24576);
   static const bool balance = [] {  // BEAT_ODE_BALANCE=0: plain cap (A/B runs)
     const char* e = std::getenv("BEAT_ODE_BALANCE");
     return !(e && e[0] == '0');
   }();
-  if (grid_cap > 0 && grid > (unsigned)grid_cap) {
-    // a few tiles per block: give every block the same number (the last one aside).  With 2.67 tiles per block -- 256^3, or
-    // the slab one of 8 ranks owns at 512^3, on 24 576 blocks -- two thirds of the blocks are on a third tile while the
-    // others have finished: 1.36-1.47 ms against 1.25-1.32 with 3 tiles each (A B A B A B on one box, round 3).  With
-    // 21.3 tiles per block (512^3) the plain cap measures the same or better (9.80 against 9.83 ms) and stays.
-    const unsigned per_block = (grid + (unsigned)grid_cap - 1) / (unsigned)grid_cap;
-    grid = (balance && per_block <= 8) ? (grid + per_block - 1) / per_block : (unsigned)grid_cap;
-  }
-  return grid;
+  // (the arithmetic: beat_ode_grid.h)  a few tiles per block: give every block the same number (the last one aside).  With 2.67
+  // tiles per block -- 256^3, or the slab one of 8 ranks owns at 512^3, on 24 576 blocks -- two thirds of the blocks are on a third
+  // tile while the others have finished: 1.36-1.47 ms against 1.25-1.32 with 3 tiles each (A B A B A B on one box, round 3).  With
+  // 21.3 tiles per block (512^3) the plain cap measures the same or better (9.80 against 9.83 ms) and stays.
+  return beat_ode_detail::beat_ode_grid_blocks(grid, num_states, grid_cap_env, tile_min_states, balance);
+}
+
+// What ode_grid gives in this process (host only; tests assert the launch shape they mean to check).
+extern "C" int beat_ode_launch_blocks(int64_t n, int num_states) {
+  BEAT_REQUIRE(n >= 0 && (n + BEAT_BLOCK - 1) / BEAT_BLOCK < (int64_t)0x7fffffff, "bad node count %lld", (long long)n);
+  return (int)ode_grid(n, num_states);
 }
 
 // One parameter route's kernel: the instance that applies a pending update, or the one without.  (`auto`: instantiated where

@@ -93,6 +93,12 @@ int beat_memcpy_d2h(beat_ctx* ctx, void* host_dst, const void* dev_src, size_t b
 int beat_ode_model_register(const char* name, const char* source, int num_states, int num_params, int v_index, int* model_id_out);
 /* Static description of a built-in (or registered) cell model. */
 int beat_ode_model_info(int model_id, int* num_states, int* num_params);
+/* Blocks of 256 threads an ionic launch (beat_ode_step and its kin) over n nodes of a model with num_states states gets in THIS
+ * process: one per tile of 256 nodes for models of 12 states and more, at most 24 576 -- each walking several tiles -- for smaller
+ * ones; BEAT_ODE_GRID=<blocks> caps every model's launch (0: one block per tile), BEAT_ODE_TILE_MIN_STATES moves the 12, and a cap
+ * that leaves at most 8 tiles to a block is lowered until the blocks walk equally many (BEAT_ODE_BALANCE=0: the plain cap).  The
+ * switches are read once per process.  Host only, no launch: tests assert the launch shape they mean to check.  < 0: bad n. */
+int beat_ode_launch_blocks(int64_t n, int num_states);
 /* One explicit / GRL1 update of all num_states states at n nodes.
  *  dev_states : (num_states, ld) row-major ("state-major" SoA as odesolver.py:149-153), updated
  *               in place.
