@@ -11,6 +11,7 @@ from . import (  # noqa: F401
     conductivities,
     ecg,
     events,
+    fibres,
     geometry,
     grid,
     io,
@@ -39,5 +40,5 @@ __program_name__ = "fenicsx-beat-amd"
 __all__ = [
     "monodomain_model", "irksome_model", "IrksomeMonodomainModel", "butcher", "odesolver", "base_model", "MonodomainModel", "monodomain_solver",
     "MonodomainSplittingSolver", "utils", "single_cell", "conductivities", "stimulation", "geometry", "grid", "models",
-    "Stimulus", "io", "ecg", "ECGRecovery", "LeadRecorder", "events", "EventRecorder", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
+    "Stimulus", "io", "ecg", "ECGRecovery", "LeadRecorder", "events", "EventRecorder", "fibres", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
 ]

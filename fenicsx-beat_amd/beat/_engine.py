@@ -226,7 +226,10 @@ class HipOps:
         nvox = int(np.prod(cells))
         c3 = [int(v) for v in cells] + [1] * (3 - dim)
         T, Me = _stencil.voxel_element_tensors(dim, h)
-        M = np.asarray(M, dtype=np.float64)
+        # per-voxel tensors that are on the device already (a torch tensor: grid.DeviceCellField) go to the kernel as they are
+        on_device = dim == 3 and hasattr(M, "data_ptr") and M.ndim == 3
+        if not on_device:
+            M = np.asarray(M.cpu() if hasattr(M, "data_ptr") else M, dtype=np.float64)
         if M.ndim == 3 and M.shape != (nvox, dim, dim):
             raise ValueError(f"per-voxel conductivity has shape {M.shape}, expected ({nvox}, {dim}, {dim})")
         if active is not None:
@@ -247,7 +250,9 @@ class HipOps:
                 c3[2], z0 = hi - lo, z0 - lo
                 nvox = per_layer * c3[2]
         m_dev, m_const = None, None
-        if M.ndim == 3:
+        if on_device:
+            m_dev = M.to(device=ctx.device, dtype=ctx.torch.float64).reshape(nvox, 9).contiguous()  # (no copy when it is all that)
+        elif M.ndim == 3:
             if dim == 3:
                 M9 = M  # already (nvox, 3, 3): no padded copy
             else:
@@ -475,12 +480,18 @@ class HipOps:
 
 
 def conductivity_array(M, mesh) -> np.ndarray:
-    """(dim, dim) for a constant tensor, (ncells, dim, dim) for a per-cell field (grid.CellField or array)."""
+    """(dim, dim) for a constant tensor, (ncells, dim, dim) for a per-cell field (grid.CellField or array); the device tensor
+    itself, of that shape, for a per-voxel field that lives on the device (grid.DeviceCellField)."""
     from . import _stencil, grid
 
     if isinstance(M, (grid.Function, grid.VectorFunction)):
         raise TypeError("the conductivity is a tensor: build it from a fibre field with "
                         "beat.conductivities.define_conductivity_tensor (vector P1 functions and per-cell fields are accepted)")
+    if isinstance(M, grid.DeviceCellField):
+        d = mesh.dim
+        if tuple(M.device_values.shape[1:]) != (d, d):
+            raise ValueError(f"per-cell conductivity has shape {tuple(M.device_values.shape)}, expected (ncells, {d}, {d})")
+        return M.device_values
     if isinstance(M, grid.CellField):
         M = M.values
     if isinstance(M, grid.Constant):
@@ -501,6 +512,11 @@ def build_ops(ctx, mesh, M: np.ndarray) -> "HipOps":
     from . import _stencil
 
     slab = mesh.slab
+    if not isinstance(M, np.ndarray):  # per-voxel tensors on the device: the voxel assembly reads them there, every other route a host copy
+        voxel_route = (not getattr(mesh, "kernel_y_as_z", False) and M.shape[0] == mesh.num_box_cells
+                       and (mesh.active is None or mesh.active_box is not None))
+        if not voxel_route:
+            M = M.cpu().numpy()
     if M.ndim == 2 and mesh.active is None:
         mass_tab, stiff_tab = _stencil.stencil_tables(mesh.dim, mesh.h, M)
         if getattr(mesh, "kernel_y_as_z", False):  # a 2-D mesh cut into slabs of rows: the kernels see (nx, 1, ny_local)

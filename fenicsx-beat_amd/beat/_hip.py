@@ -167,6 +167,9 @@ SIGNATURES = {
     "beat_field_events": (_int, [_vp, _vp, _i64, C.POINTER(EventMaps), _dbl, _dbl]),
     "beat_pde_x_flush_events": (_int, [_vp, _vp, _vp, _vp, _i64, _int, C.POINTER(EventMaps), _dbl, _dbl]),
     "beat_field_leads": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp]),
+    # (cells, h and axis are host arrays, axis may be None; every dev_* is a device address)
+    "beat_fibres_rule": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), _vp, _vp, C.POINTER(_dbl), _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl,
+                                _vp, _vp, _vp, _vp, _vp]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)

@@ -72,6 +72,11 @@ def conductivity_tensor(s_l: float, s_t: float, f0):
         return grid.CellField(mesh, s_t * np.eye(d)[None] + (s_l - s_t) * ff)
     if isinstance(f0, grid.Function):
         raise NotImplementedError("scalar functions are not fibre fields: use a vector P1 function or a grid.CellField")
+    if isinstance(f0, grid.DeviceCellField):  # fibres that were made on the device: the tensors are formed there, no host copy
+        fibres = f0.device_values
+        eye = fibres.new_zeros((fibres.shape[1], fibres.shape[1]))
+        eye.fill_diagonal_(1.0)
+        return grid.DeviceCellField(f0.mesh, s_t * eye[None] + (s_l - s_t) * (fibres[:, :, None] * fibres[:, None, :]))
     if isinstance(f0, grid.CellField):
         fibres = f0.values
         eye = np.eye(fibres.shape[1])

@@ -635,6 +635,27 @@ class CellField:
         self.values = values
 
 
+class DeviceCellField(CellField):
+    """A per-voxel ``CellField`` whose data live on the device (``beat.fibres.rule_based`` makes them there): ``device_values`` is
+    the torch tensor, (num_box_cells, ...).  ``values`` fetches a read-only host copy on first use, so whatever reads a
+    ``CellField`` reads this one too; ``conductivities.conductivity_tensor`` and the operator assembly take the tensor as it is."""
+
+    def __init__(self, mesh: "Mesh", device_values):
+        if device_values.shape[0] != mesh.num_box_cells:
+            raise ValueError(f"cell data has leading size {device_values.shape[0]}; expected one entry per box cell ({mesh.num_box_cells})")
+        self.mesh = mesh
+        self.device_values = device_values
+        self._host_values = None
+
+    @property
+    def values(self) -> np.ndarray:
+        if self._host_values is None:
+            arr = self.device_values.cpu().numpy()
+            arr.setflags(write=False)
+            self._host_values = arr
+        return self._host_values
+
+
 
 def create_unit_interval(comm, nx, **kw):
     return _mesh(comm, (0.0,), (1.0,), (nx,))

@@ -723,6 +723,36 @@ int beat_pde_x_flush_events(beat_pde* pde, const double* dev_st, double* dev_x, 
 #define BEAT_MAX_LEADS 16
 int beat_field_leads(beat_ctx* ctx, const double* dev_v, int64_t n, const double* dev_q, int64_t ldq, int nleads, double* dev_out);
 
+/* ---- rule-based fibre, sheet and sheet-normal fields of a voxel geometry ----------------------------------------------------
+ * The reference's ventricular demos take their fibres from a Laplace-Dirichlet rule-based generator over FEniCSx
+ * (demos/lv_endocardial.py, demos/biv_endocardial.py, demos/ukb_atlas.py: cardiac_geometries(create_fibers=True,
+ * fiber_angle_endo=60, fiber_angle_epi=-60)) and turn them into tensors in src/beat/conductivities.py:107-118.  This is that step
+ * for one ventricle on the voxel grid, from nodal fields that are already on the device (beat.utils.laplace_dirichlet) to the
+ * per-voxel tensors beat_pde_assemble_rows reads, without a host pass.  Per voxel with a non-zero byte in dev_active, corner c
+ * of the voxel at node offsets (c & 1, (c >> 1) & 1, (c >> 2) & 1):
+ *   grad   = gradient of the trilinear field at the voxel centre: per axis the mean of the four edge differences over the spacing
+ *   phi_c  = mean of the 8 corner values of phi, clipped to [0, 1]
+ *   e_l    = grad psi / |grad psi|   (dev_psi NULL: axis / |axis|)
+ *   t      = grad phi / |grad phi|,  r = t - (e_l . t) e_l,  e_t = r / |r|,  e_c = e_l x e_t
+ *   alpha  = alpha_endo (1 - phi_c) + alpha_epi phi_c,  beta likewise   (radians)
+ *   f = cos(alpha) e_c + sin(alpha) e_l,  g = -sin(alpha) e_c + cos(alpha) e_l
+ *   s = sin(beta) g + cos(beta) e_t  (sheet),  n = cos(beta) g - sin(beta) e_t  (sheet normal);  f x n = s
+ *   M = s_t I + (s_l - s_t) f f^T
+ * A voxel is degenerate when |grad phi| = 0, |grad psi| = 0 (|axis| = 0) or |r| <= 1e-12: f = s = n = 0, M = s_t I, and
+ * *dev_degenerate is incremented (the caller zeroes it).  Inactive voxels get zeros in every output and are not counted.
+ *  cells[3], h[3] : voxels per axis and their spacings (host);  dev_phi, dev_psi : DEVICE nodal fields, (cells + 1) nodes per
+ *             axis, x fastest;  axis[3] : host, read when dev_psi is NULL;  dev_active : DEVICE (nvoxels) bytes or NULL (all inside),
+ *             as for beat_pde_assemble_rows
+ *  dev_f, dev_s, dev_n : DEVICE (nvoxels, 3) outputs;  dev_M : DEVICE (nvoxels, 9) row-major, the layout beat_pde_assemble_rows
+ *             reads.  Each may be NULL (not wanted), not all of them.
+ * Enqueued on the context's stream; does not synchronise.  EINVAL (nothing enqueued, nothing touched): a null required argument,
+ * neither dev_psi nor axis, no output, a cell count < 1 or a grid of 2^40 nodes or more, a spacing <= 0, a pointer that is not
+ * 8-byte aligned. */
+int beat_fibres_rule(beat_ctx* ctx, const int64_t cells[3], const double h[3], const double* dev_phi, const double* dev_psi,
+                     const double axis[3], const unsigned char* dev_active, double alpha_endo, double alpha_epi, double beta_endo,
+                     double beta_epi, double s_l, double s_t, double* dev_f, double* dev_s, double* dev_n, double* dev_M,
+                     int64_t* dev_degenerate);
+
 #ifdef __cplusplus
 }
 #endif
