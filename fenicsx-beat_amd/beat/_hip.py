@@ -170,6 +170,8 @@ SIGNATURES = {
     # (cells, h and axis are host arrays, axis may be None; every dev_* is a device address)
     "beat_fibres_rule": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), _vp, _vp, C.POINTER(_dbl), _vp, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl,
                                 _vp, _vp, _vp, _vp, _vp]),
+    "beat_fibres_biv_rule": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp, _dbl, _dbl, _dbl, _dbl,
+                                    _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)

@@ -753,6 +753,62 @@ int beat_fibres_rule(beat_ctx* ctx, const int64_t cells[3], const double h[3], c
                      double beta_epi, double s_l, double s_t, double* dev_f, double* dev_s, double* dev_n, double* dev_M,
                      int64_t* dev_degenerate);
 
+/* ---- the same for two ventricles: Bayer's rule with bislerp --------------------------------------------------------------------
+ * Algorithm 1 of Bayer, Blake, Plank and Trayanova (2012) on the voxel grid: the input the reference's bi-ventricular demos
+ * (demos/biv_endocardial.py, demos/ukb_atlas.py) take from cardiac_geometries(create_fibers=True, ...).  Three transmural harmonic
+ * fields, one frame per surface family, two blends of frames.  csrc/beat_fibres_kernel.h and tests/_fibres_biv_ref.py are both
+ * written from this text.
+ *
+ * Inputs per voxel: the 8 corner values (corner numbering as for beat_fibres_rule) of four nodal P1 fields,
+ *   phi_lv   1 on the LV endocardium, 0 on the RV endocardium and the epicardium
+ *   phi_rv   1 on the RV endocardium, 0 on the LV endocardium and the epicardium
+ *   phi_epi  1 on the epicardium, 0 on both endocardia
+ *   psi      increases from apex to base (dev_psi NULL: the constant axis instead)
+ * and the four angles alpha_endo, alpha_epi, beta_endo, beta_epi in radians.  The gradients g_lv, g_rv, g_epi, g_psi are taken at
+ * the voxel centre as beat_fibres_rule takes them; c_lv, c_rv, c_epi are the means of the 8 corner values, clipped to [0, 1].
+ *
+ * Step 1, one frame.  frame(l, t, alpha, beta) is the rule of beat_fibres_rule with its inputs made explicit:
+ *   e_l = l / |l|,  r = t / |t| - (e_l . t / |t|) e_l,  e_t = r / |r|,  e_c = e_l x e_t
+ *   f = cos(alpha) e_c + sin(alpha) e_l,  g = -sin(alpha) e_c + cos(alpha) e_l
+ *   s = sin(beta) g + cos(beta) e_t,  n = cos(beta) g - sin(beta) e_t;  (f, n, s) is right-handed
+ * The frame is UNDEFINED when |l| = 0, |t| = 0, |r| <= 1e-12, or l or t holds a NaN.
+ *
+ * Step 2, quaternions.  A frame is the rotation matrix R = [f | n | s] (columns).  It becomes a unit quaternion q = (w, x, y, z)
+ * by Shepperd's method (branch on the largest of trace, R00, R11, R22); a quaternion is normalised before it is turned back.
+ *
+ * Step 3, bislerp(Q_a, Q_b, t).
+ *   1. the candidates are q_a (x) {1, i, j, k}, by right multiplication: the frames (f, n, s), (f, -n, -s), (-f, n, -s),
+ *      (-f, -n, s) of Q_a
+ *   2. take the candidate q_c with the largest |<q_c, q_b>|; the earliest in that order wins a tie
+ *   3. negate q_c if the inner product is negative
+ *   4. c = <q_c, q_b>;  the four candidates are an orthonormal basis of R^4, so c >= 1/2
+ *   5. w = q_b - c q_c,  sigma = |w|,  theta = atan2(sigma, c)
+ *   6. the result is cos(t theta) q_c + sin(t theta) w / sigma when sigma > 0, and q_c otherwise
+ * There is no acos and no 1 / sin(theta): near theta = 0 the direction of w is noise, but it is multiplied by sin(t theta) <= sigma.
+ *
+ * Step 4, the voxel.
+ *   d       = c_rv / (c_lv + c_rv), or 0 where the sum is 0
+ *   alpha_s = alpha_endo (1 - 2 d),                          beta_s = beta_endo (1 - 2 d)
+ *   alpha_w = alpha_endo (1 - c_epi) + alpha_epi c_epi,      beta_w = beta_endo (1 - c_epi) + beta_epi c_epi
+ *   Q_lv    = frame(g_psi or axis, -g_lv,  alpha_s, beta_s)
+ *   Q_rv    = frame(g_psi or axis, +g_rv,  alpha_s, beta_s)
+ *   Q_epi   = frame(g_psi or axis, +g_epi, alpha_w, beta_w)
+ *   Q_endo  = bislerp(Q_lv, Q_rv, d) if both are defined; the defined one if only one is; undefined if neither is
+ *   Q       = bislerp(Q_endo, Q_epi, c_epi) if both are defined; the defined one if only one is
+ *   if neither is defined the voxel is DEGENERATE: f = s = n = 0, M = s_t I, and *dev_degenerate is incremented
+ *   M       = s_t I + (s_l - s_t) f f^T
+ * Inactive voxels get zeros in every output and are not counted.  A fibre is a line: bislerp may return a frame with two of its
+ * vectors negated relative to an input, also at t = 0.
+ *
+ * The limit (the rule's own): when the endocardial and the epicardial frame are more than 90 degrees apart, bislerp turns towards
+ * the flipped candidate and the fibre angle jumps: c_epi |alpha_epi - alpha_endo| > 90 degrees for beta = 0.
+ *
+ * Arguments, outputs, enqueueing and the EINVAL cases are those of beat_fibres_rule, with all three transmural fields required. */
+int beat_fibres_biv_rule(beat_ctx* ctx, const int64_t cells[3], const double h[3], const double* dev_phi_lv, const double* dev_phi_rv,
+                         const double* dev_phi_epi, const double* dev_psi, const double axis[3], const unsigned char* dev_active,
+                         double alpha_endo, double alpha_epi, double beta_endo, double beta_epi, double s_l, double s_t, double* dev_f,
+                         double* dev_s, double* dev_n, double* dev_M, int64_t* dev_degenerate);
+
 #ifdef __cplusplus
 }
 #endif
