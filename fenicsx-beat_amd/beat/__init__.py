@@ -20,6 +20,7 @@ from . import (  # noqa: F401
     monodomain_model,
     monodomain_solver,
     odesolver,
+    output,
     single_cell,
     stimulation,
     telemetry,
@@ -31,6 +32,7 @@ from .events import EventRecorder
 from .irksome_model import IrksomeMonodomainModel
 from .monodomain_model import MonodomainModel
 from .monodomain_solver import MonodomainSplittingSolver
+from .output import FieldWriter
 from .stimulation import Stimulus
 from .telemetry import BaseMonitor, NullMonitor, PerformanceMonitor
 
@@ -40,5 +42,5 @@ __program_name__ = "fenicsx-beat-amd"
 __all__ = [
     "monodomain_model", "irksome_model", "IrksomeMonodomainModel", "butcher", "odesolver", "base_model", "MonodomainModel", "monodomain_solver",
     "MonodomainSplittingSolver", "utils", "single_cell", "conductivities", "stimulation", "geometry", "grid", "models",
-    "Stimulus", "io", "ecg", "ECGRecovery", "LeadRecorder", "events", "EventRecorder", "fibres", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
+    "Stimulus", "io", "ecg", "ECGRecovery", "LeadRecorder", "events", "EventRecorder", "fibres", "output", "FieldWriter", "telemetry", "BaseMonitor", "NullMonitor", "PerformanceMonitor", "units",
 ]

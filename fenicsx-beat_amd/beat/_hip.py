@@ -172,6 +172,15 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp, _vp]),
     "beat_fibres_biv_rule": (_int, [_vp, C.POINTER(_i64), C.POINTER(_dbl), _vp, _vp, _vp, _vp, C.POINTER(_dbl), _vp, _dbl, _dbl, _dbl, _dbl,
                                     _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
+    # field snapshots (beat.output): n, lo, hi, stride are host arrays of 3; dev_fields a host array of device addresses; ctypes
+    # releases the GIL for the length of a call, so beat_snap_wait may block in a writer thread
+    "beat_snap_create": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _int, _int, _int, _vp, _dbl, _int,
+                                C.POINTER(_vp)]),
+    "beat_snap_info": (_int, [_vp, C.POINTER(_i64)]),
+    "beat_snap_enqueue": (_int, [_vp, C.POINTER(_vp), C.POINTER(_int)]),
+    "beat_snap_wait": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_dbl)]),
+    "beat_snap_release": (_int, [_vp, _int]),
+    "beat_snap_destroy": (_int, [_vp]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)
@@ -187,6 +196,10 @@ MAX_SPARSE_ROWS_RT = 4  # BEAT_MAX_SPARSE_ROWS_RT: on the shipped kernel
 CUSTOM_MODEL_BASE = 100  # BEAT_MODEL_CUSTOM_BASE: ids of models registered as source (beat_ode_model_register)
 TRANSPORT_NAMES = {0: "callbacks", 1: "rccl", 2: "rccl-serial", 3: "ipc"}
 E_NOT_CONVERGED = -3
+E_BUSY = -5  # BEAT_EBUSY: beat_snap_enqueue with every slot in flight
+SNAP_MAX_FIELDS = 8  # BEAT_SNAP_MAX_FIELDS
+SNAP_MAX_DEPTH = 16  # BEAT_SNAP_MAX_DEPTH
+SNAP_STATS, SNAP_NT_LOADS = 1, 2  # flags of beat_snap_create
 
 SIGNATURES.update({
     "beat_pde_set_ghost_types": (_int, [_vp, _int, _int]),

@@ -90,9 +90,10 @@ class MonodomainSplittingSolver:
     def _can_batch(self, recorder) -> bool:
         from .ecg import LeadRecorder
         from .events import EventRecorder
+        from .output import FieldWriter
 
-        if isinstance(recorder, (EventRecorder, LeadRecorder)):
-            return False  # event maps and lead traces inside the library's step loops: not built
+        if isinstance(recorder, (EventRecorder, LeadRecorder, FieldWriter)):
+            return False  # event maps, lead traces and field snapshots inside the library's step loops: not built
         if not (isinstance(self.ode, DolfinODESolver) and self._can_fuse() and np.isclose(self.theta, 1.0)):
             return False
         ode, pde = self.ode, self.pde

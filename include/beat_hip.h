@@ -37,6 +37,7 @@ extern "C" {
 #define BEAT_EHIP -2        /* a HIP runtime call failed */
 #define BEAT_ENOTCONV -3    /* PCG hit max_it without meeting the tolerance */
 #define BEAT_ENOMEM -4
+#define BEAT_EBUSY -5       /* nothing free to take the request now (beat_snap_enqueue: every slot in flight); nothing was enqueued */
 
 #define BEAT_ABI_VERSION 1
 
@@ -808,6 +809,50 @@ int beat_fibres_biv_rule(beat_ctx* ctx, const int64_t cells[3], const double h[3
                          const double* dev_phi_epi, const double* dev_psi, const double axis[3], const unsigned char* dev_active,
                          double alpha_endo, double alpha_epi, double beta_endo, double beta_epi, double s_l, double s_t, double* dev_f,
                          double* dev_s, double* dev_n, double* dev_M, int64_t* dev_degenerate);
+
+/* ---- field snapshots: frames for ParaView or NumPy, written behind the time loop --------------------------------------------------
+ * Every tissue demo of the reference saves once per millisecond of simulated time, from the host: vtx.write(t),
+ * io4dolfinx.write_function(..., solver.pde.state, time=t, name="v") and print(v.max(), v.min())
+ * (demos/niederer_benchmark.py:226-277, demos/slab.py:284-299, demos/lv_endocardial.py:311-326, demos/biv_endocardial.py:299-314,
+ * demos/ukb_atlas.py:386-418, demos/fitzhughnagumo.py:252-301).  A beat_snap takes the frame on the device instead -- cropped to a
+ * box, down-sampled, converted to fp32 if asked -- and copies it to pinned host memory on a side stream of its own while the
+ * context's stream goes on with the next steps.
+ *
+ * The sample lattice: the nodes lo[a] + k stride[a] < hi[a] per axis a (x, y, z; unused axes: n = 1, lo = 0, hi = 1, stride = 1),
+ * what the slice lo:hi:stride takes; a frame holds them x fastest.  dtype 0: fp64, 1: fp32 (static_cast<float>, round to nearest
+ * even: numpy.float32(x)).  dev_mask: NULL, or a DEVICE byte per node of the grid, 0 = outside the tissue: such a sample gets
+ * `fill`, and the node takes no part in the statistics.  Borrowed for the lifetime of the handle.  flags: BEAT_SNAP_STATS -- every
+ * frame comes with min, max and the number of non-finite values of each field over ALL tissue nodes of the box, on the lattice or
+ * not (the pass then reads every row of the box; without the flag only the lattice's rows); BEAT_SNAP_NT_LOADS -- the pass reads the
+ * fields with non-temporal loads (a choice to measure: the potential is read again by the next launch).
+ * The handle owns depth <= BEAT_SNAP_MAX_DEPTH slots (a device staging buffer and a pinned host buffer each: beat_snap_info's slot
+ * bytes), a non-blocking stream and two events per slot.  A failed allocation frees what was made: BEAT_EHIP. */
+#define BEAT_SNAP_MAX_FIELDS 8
+#define BEAT_SNAP_MAX_DEPTH 16
+#define BEAT_SNAP_STATS 1
+#define BEAT_SNAP_NT_LOADS 2
+typedef struct beat_snap beat_snap;
+int beat_snap_create(beat_ctx* ctx, const int64_t n[3], const int64_t lo[3], const int64_t hi[3], const int64_t stride[3], int dtype,
+                     int nfields, int depth, const unsigned char* dev_mask, double fill, int flags, beat_snap** out);
+/* host_out[6] = {samples along x, y, z, bytes of one field's frame, bytes of a slot, blocks of the pack launch} */
+int beat_snap_info(const beat_snap* snap, int64_t* host_out);
+/* One frame of the nfields fields dev_fields[0..nfields) (host array of DEVICE pointers, 8-byte aligned; laid out as any field, only
+ * the n owned nodes are read -- never a ghost plane): ONE pack launch on the context's stream, ordered behind whatever last wrote
+ * the fields, then the copy to the slot's host buffer on the handle's own stream.  Returns without waiting for the device; the
+ * fields may be overwritten at once.  *slot_out names the slot, which is in flight until beat_snap_release.  BEAT_EBUSY when every
+ * slot is in flight: nothing is enqueued and nothing blocks -- back-pressure is the caller's decision. */
+int beat_snap_enqueue(beat_snap* snap, const double* const* dev_fields, int* slot_out);
+/* Blocks until the slot's copy has arrived (callable from another host thread than the one that enqueues).  *host_ptr: the frames,
+ * field f at f * (bytes of one field's frame); valid until the slot is released.  host_stats (3 * nfields doubles, or NULL): per
+ * field min, max and the count of non-finite values over the tissue nodes of the box, finished here from the pack launch's block
+ * partials in a fixed order (no atomics: the same input gives the same bits).  NaN is counted and takes no part in min and max
+ * (numpy.nanmin / nanmax); an infinity is counted and does; min = max = NaN when there is no tissue node that is not NaN.  Without
+ * BEAT_SNAP_STATS: NaN, NaN, -1. */
+int beat_snap_wait(beat_snap* snap, int slot, void** host_ptr, double* host_stats);
+/* The slot may take the next frame (waits for its copy if nobody has).  wait and release refuse a slot that is not in flight. */
+int beat_snap_release(beat_snap* snap, int slot);
+/* Drains the handle's stream, then frees everything it owns. */
+int beat_snap_destroy(beat_snap* snap);
 
 #ifdef __cplusplus
 }
