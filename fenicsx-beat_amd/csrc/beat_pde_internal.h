@@ -199,6 +199,27 @@ inline int beat_part0_take(beat_pde* pde, int pass, int* blocks) {
   return BEAT_OK;
 }
 
+// a device array with a copy of `host` (one element where `host` is empty: never a null pointer)
+template <class T>
+hipError_t beat_upload(T** dev, const std::vector<T>& host) {
+  hipError_t e = hipMalloc(dev, sizeof(T) * std::max<size_t>(1, host.size()));
+  if (e == hipSuccess && !host.empty()) e = hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice);
+  return e;
+}
+
+// The workgroups of `block` threads of `kernel` the chip holds at once (occupancy x CUs); `on_failure` where it cannot be asked.  Grid-
+// stride and list-walking kernels are launched with at most this many; each caller adds its own cap and rounding.  A failure of any
+// one of the three queries gives `on_failure` as a whole: no product of one answer with a guess at the other (an assumed CU count
+// times the occupancy found, or the CUs found times one block).
+template <class Kernel>
+unsigned beat_resident_blocks(Kernel kernel, int block, unsigned on_failure) {
+  int per_cu = 0, cus = 0, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1)
+    return on_failure;
+  return (unsigned)(per_cu * cus);
+}
+
 inline beat_pde_detail::SlabPart beat_slab_part(const beat_pde* pde, int part) {
   return beat_pde_detail::beat_slab_part(pde->g.nz, pde->g.z_lo_phys != 0, pde->g.z_hi_phys != 0, part);
 }

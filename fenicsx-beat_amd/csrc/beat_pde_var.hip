@@ -2,6 +2,7 @@
 // kernels, device-side assembly of the rows from per-voxel tensors, Dirichlet elimination for the Laplace
 // problems of utils.expand_layer, and the beat_var_* stage functions the C ABI in beat_pde.hip dispatches to.
 #include "beat_pde_internal.h"
+#include "beat_var_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -11,9 +12,8 @@
 namespace {
 using namespace beat_pde_detail;
 
-// Granularity of the tissue bookkeeping: one wavefront's worth of consecutive nodes.  A workgroup takes
-// VAR_SEGS_PER_BLOCK list entries at a time, one per wave.
-constexpr int VAR_SEG = 64;
+// Granularity of the tissue bookkeeping: one wavefront's worth of consecutive nodes (VAR_SEG = 64: beat_var_plan.h).  A workgroup
+// takes VAR_SEGS_PER_BLOCK list entries at a time, one per wave.
 constexpr int VAR_SEGS_PER_BLOCK = BEAT_BLOCK / VAR_SEG;
 
 // ---- variable-coefficient operators (beat_pde_create_var) -----------------------------------------------
@@ -645,12 +645,7 @@ static void var_offsets(const beat_pde* pde, VarArgs& a) {
 // with 4096 workgroups, 610 us with the 1536 resident ones, 687 / 918 us with 1280 / 1792.
 template <class Kernel>
 static unsigned resident_blocks(Kernel kernel) {
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BEAT_BLOCK, 0) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || per_cu < 1 || cus < 1)
-    return 4096;
-  return (unsigned)std::min(per_cu * cus, BEAT_MAX_PARTIALS / 4);
+  return std::min(beat_resident_blocks(kernel, BEAT_BLOCK, 4096u), (unsigned)(BEAT_MAX_PARTIALS / 4));
 }
 
 struct VarRange {
@@ -814,7 +809,7 @@ extern "C" int beat_pde_create_var(beat_ctx* ctx, const int64_t n[3], int z_lo_p
   // list of the segments (VAR_SEG consecutive nodes) that hold tissue nodes
   const int64_t nsegs = (p->n + VAR_SEG - 1) / VAR_SEG;
   unsigned long long* d_flags = nullptr;
-  std::vector<unsigned long long> flags((size_t)nsegs), masks;
+  std::vector<unsigned long long> flags((size_t)nsegs);
   hipError_t e = hipMalloc(&d_flags, sizeof(unsigned long long) * (size_t)nsegs);
   if (e == hipSuccess) {
     BEAT_KERNEL(var_segment_flags_kernel, dim3((unsigned)std::min<int64_t>(4096, (nsegs + VAR_SEGS_PER_BLOCK - 1) / VAR_SEGS_PER_BLOCK)),
@@ -825,43 +820,18 @@ extern "C" int beat_pde_create_var(beat_ctx* ctx, const int64_t n[3], int z_lo_p
                                           ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)hipFree(d_flags);
+  SegList list;
   if (e == hipSuccess) {
-    for (int64_t sidx = 0; sidx < nsegs; ++sidx)
-      if (flags[(size_t)sidx]) {
-        p->h_seg.push_back((int)sidx);
-        masks.push_back(flags[(size_t)sidx]);
-      }
-    e = hipMalloc(&p->v_seg, sizeof(int) * std::max<size_t>(1, p->h_seg.size()));
+    list = var_segments(flags);
+    p->h_seg = list.seg;
+    e = beat_upload(&p->v_seg, list.seg);
   }
-  if (e == hipSuccess) e = hipMalloc(&p->v_segmask, sizeof(unsigned long long) * std::max<size_t>(1, masks.size()));
-  if (e == hipSuccess && !p->h_seg.empty())
-    e = hipMemcpy(p->v_seg, p->h_seg.data(), sizeof(int) * p->h_seg.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !masks.empty())
-    e = hipMemcpy(p->v_segmask, masks.data(), sizeof(unsigned long long) * masks.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = beat_upload(&p->v_segmask, list.mask);
   if (e == hipSuccess && p->g.nz > 1 && !p->h_seg.empty() && var_tile_edge() > 0) {
     // the same list in tile order: tiles of T rows x T planes (keyed by the segment's first node), node order inside
-    const int TY = var_tile_edge(), TZ = var_tile_edge();
-    const int64_t nyb = (p->g.ny + TY - 1) / TY;
-    std::vector<int64_t> key(p->h_seg.size());
-    std::vector<int> order(p->h_seg.size());
-    for (size_t k = 0; k < p->h_seg.size(); ++k) {
-      const int64_t i0 = (int64_t)p->h_seg[k] * VAR_SEG;
-      const int64_t z = i0 / p->g.plane, y = (i0 % p->g.plane) / p->g.nx;
-      key[k] = (z / TZ) * nyb + y / TY;
-      order[k] = (int)k;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int u, int v) { return key[(size_t)u] < key[(size_t)v]; });
-    std::vector<int> seg_t(order.size());
-    std::vector<unsigned long long> mask_t(order.size());
-    for (size_t k = 0; k < order.size(); ++k) {
-      seg_t[k] = p->h_seg[(size_t)order[k]];
-      mask_t[k] = masks[(size_t)order[k]];
-    }
-    e = hipMalloc(&p->v_seg_tiled, sizeof(int) * seg_t.size());
-    if (e == hipSuccess) e = hipMalloc(&p->v_segmask_tiled, sizeof(unsigned long long) * mask_t.size());
-    if (e == hipSuccess) e = hipMemcpy(p->v_seg_tiled, seg_t.data(), sizeof(int) * seg_t.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(p->v_segmask_tiled, mask_t.data(), sizeof(unsigned long long) * mask_t.size(), hipMemcpyHostToDevice);
+    const SegList tiled = var_segments_tiled(list, p->g.nx, p->g.ny, p->g.plane, var_tile_edge());
+    e = beat_upload(&p->v_seg_tiled, tiled.seg);
+    if (e == hipSuccess) e = beat_upload(&p->v_segmask_tiled, tiled.mask);
   }
   if (e != hipSuccess) {
     beat_pde_destroy(p);

@@ -22,6 +22,7 @@
 // from per-cell conductivity tensors (src/beat/conductivities.py:101-118, demos/biv_endocardial.py:187-282).
 #include "beat_pde_internal.h"
 #include "beat_pde_device.h"
+#include "beat_var_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -30,12 +31,8 @@
 namespace {
 using namespace beat_pde_detail;
 
-constexpr int SEG = 62;      // x-nodes computed per wave and row (lanes 1..62)
-constexpr int MAX_RUN = 48;  // planes per work item at most (longer runs of tissue are cut)
-
-struct VrrItem {
-  int seg, rb, zb, ze;  // column (x segment, row block) and the planes [zb, ze) it computes
-};
+// (SEG = 62, the x-nodes computed per wave and row (lanes 1..62), and MAX_RUN = 48, the planes per work item at most: beat_var_plan.h)
+using VrrItem = PlaneRun;  // column (x segment, row block) and the planes [zb, ze) it computes
 
 struct VrrArgs {
   const double* A;  // (15, ld) coefficient rows
@@ -251,11 +248,7 @@ struct VrrData {
 
 template <int RY, bool PF>
 unsigned resident_blocks_of() {
-  int dev = 0, cus = 256, per_cu = 1;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, vrr_spmv_kernel<RY, PF>, BEAT_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  return (unsigned)(cus * per_cu);
+  return beat_resident_blocks(vrr_spmv_kernel<RY, PF>, BEAT_BLOCK, 256u);
 }
 }  // namespace
 
@@ -268,9 +261,9 @@ void beat_vrr_destroy(beat_pde* pde) {
   pde->vrr = nullptr;
 }
 
-// flags: tissue bits per 64-node segment of the slab (host copy).  Builds, per column of the wave decomposition, the
-// runs of planes that hold tissue -- for the whole slab and, for decomposed grids, for the planes that need no ghost
-// data and for the one or two that do.
+// flags: tissue bits per 64-node segment of the slab (host copy).  Reads the switches, has vrr_plan (beat_var_plan.h) build, per
+// column of the wave decomposition, the runs of planes that hold tissue -- for the whole slab and, for decomposed grids, for the
+// planes that need no ghost data and for the one or two that do --, uploads them.
 int beat_vrr_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) {
   // Opt-in (BEAT_VRR=1).  Measured in round 3, same box, against var_spmv_kernel: 401^3 shell (17 M tissue nodes) 0.93
   // against 0.59 ms, dense 257^3 box with a fibre field 0.71 against 0.45 ms -- with 2 or 4 rows per wave, with and
@@ -292,76 +285,30 @@ int beat_vrr_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
   }
   int max_run = MAX_RUN;
   if (const char* e = std::getenv("BEAT_VRR_RUN")) max_run = std::max(1, std::atoi(e));
-  const int RY = d->ry;
-  const int nsegx = (f.nx + SEG - 1) / SEG, nrb = (f.ny + RY - 1) / RY;
-  auto tissue = [&](int64_t i) { return (flags[(size_t)(i >> 6)] >> (i & 63)) & 1ull; };
-  std::vector<VrrItem> lists[3];
-  std::vector<char> act((size_t)f.nz);
-  const SlabPart inner = beat_slab_part(pde, 0), boundary = beat_slab_part(pde, 1);
-  for (int rb = 0; rb < nrb; ++rb)
-    for (int seg = 0; seg < nsegx; ++seg) {
-      const int x0 = seg * SEG, x1 = std::min(f.nx, x0 + SEG), ya = rb * RY, yb = std::min(f.ny, ya + RY);
-      bool any = false;
-      for (int z = 0; z < f.nz; ++z) {
-        char on = 0;
-        for (int y = ya; y < yb && !on; ++y) {
-          const int64_t base = (int64_t)z * f.plane + (int64_t)y * f.nx;
-          for (int x = x0; x < x1; ++x)
-            if (tissue(base + x)) {
-              on = 1;
-              break;
-            }
-        }
-        act[(size_t)z] = on;
-        any |= on != 0;
-      }
-      if (!any) continue;
-      auto runs = [&](int z_lo, int z_hi, std::vector<VrrItem>& out) {
-        int z = z_lo;
-        while (z < z_hi) {
-          if (!act[(size_t)z]) {
-            ++z;
-            continue;
-          }
-          int e = z + 1, last = z + 1;  // grow the run over gaps of up to two planes
-          while (e < z_hi && e - z < max_run && (act[(size_t)e] || e - last < 2)) {
-            if (act[(size_t)e]) last = e + 1;
-            ++e;
-          }
-          out.push_back(VrrItem{seg, rb, z, last});
-          z = last;
-        }
-      };
-      runs(0, f.nz, lists[0]);
-      runs(inner.range[0].z_lo, inner.range[0].z_hi, lists[1]);
-      for (int k = 0; k < boundary.count; ++k) runs(boundary.range[k].z_lo, boundary.range[k].z_hi, lists[2]);
-    }
-  std::vector<VrrItem> all;
+  VrrPlanOptions opt;
+  opt.ry = d->ry;
+  opt.max_run = max_run;
+  const VrrPlan plan = vrr_plan(f.nx, f.ny, f.nz, f.z_lo_phys != 0, f.z_hi_phys != 0, flags, opt);
   for (int k = 0; k < 3; ++k) {
-    // long runs first: the tail of the launch is made of short ones
-    std::stable_sort(lists[k].begin(), lists[k].end(), [](const VrrItem& p, const VrrItem& q) { return p.ze - p.zb > q.ze - q.zb; });
-    d->first[k] = (int)all.size();
-    d->count[k] = (int)lists[k].size();
-    all.insert(all.end(), lists[k].begin(), lists[k].end());
+    d->first[k] = plan.first[k];
+    d->count[k] = plan.count[k];
   }
   pde->vrr = d;
-  hipError_t e = hipMalloc(&d->d_items, sizeof(VrrItem) * std::max<size_t>(1, all.size()));
-  if (e == hipSuccess && !all.empty()) e = hipMemcpy(d->d_items, all.data(), sizeof(VrrItem) * all.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d->d_flags, sizeof(unsigned long long) * std::max<size_t>(1, flags.size()));
-  if (e == hipSuccess && !flags.empty())
-    e = hipMemcpy(d->d_flags, flags.data(), sizeof(unsigned long long) * flags.size(), hipMemcpyHostToDevice);
+  hipError_t e = beat_upload(&d->d_items, plan.items);
+  if (e == hipSuccess) e = beat_upload(&d->d_flags, flags);
   if (e != hipSuccess) {
     beat_vrr_destroy(pde);
     beat_set_error("beat_vrr_setup: %s", hipGetErrorString(e));
     return BEAT_EHIP;
   }
+  const int RY = d->ry;
   d->resident = RY == 4 ? (d->pf ? resident_blocks_of<4, true>() : resident_blocks_of<4, false>())
                         : (d->pf ? resident_blocks_of<2, true>() : resident_blocks_of<2, false>());
   if (std::getenv("BEAT_VRR_VERBOSE")) {
     long planes = 0;
-    for (int i = 0; i < d->count[0]; ++i) planes += all[(size_t)i].ze - all[(size_t)i].zb;
+    for (int i = 0; i < d->count[0]; ++i) planes += plan.items[(size_t)i].ze - plan.items[(size_t)i].zb;
     std::fprintf(stderr, "vrr: RY %d, prefetch %d, %d columns x rows, %d items (whole slab), %.1f planes per item, %u resident blocks\n", RY,
-                 (int)d->pf, nsegx * nrb, d->count[0], d->count[0] ? (double)planes / d->count[0] : 0.0, d->resident);
+                 (int)d->pf, ((f.nx + SEG - 1) / SEG) * ((f.ny + RY - 1) / RY), d->count[0], d->count[0] ? (double)planes / d->count[0] : 0.0, d->resident);
   }
   return BEAT_OK;
 }

@@ -33,6 +33,7 @@
 // from per-cell conductivity tensors (src/beat/conductivities.py:101-118, demos/biv_endocardial.py:187-282).
 #include "beat_pde_internal.h"
 #include "beat_pde_device.h"
+#include "beat_var_plan.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -41,12 +42,8 @@
 namespace {
 using namespace beat_pde_detail;
 
-constexpr int SEG = 62;  // x-nodes computed per wave (lanes 1..62)
-using u64 = unsigned long long;
-
-struct VtlItem {
-  int seg, rb, zb, ze;  // tile column (x segment, row block) and the planes [zb, ze) it computes
-};
+// (SEG = 62, the x-nodes computed per wave (lanes 1..62), and u64: beat_var_plan.h)
+using VtlItem = PlaneRun;  // tile column (x segment, row block) and the planes [zb, ze) it computes
 
 struct VtlArgs {
   int64_t ld;
@@ -552,12 +549,7 @@ struct VtlData {
 
 template <int RY>
 unsigned vtl_resident_blocks() {
-  auto kernel = vtl_spmv_kernel<RY, false, RY == 8 ? 1 : 0>;
-  int dev = 0, cus = 256, per_cu = 1;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, RY * 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-  return (unsigned)std::min(cus * per_cu, BEAT_MAX_PARTIALS) & ~7u;
+  return std::min(beat_resident_blocks(vtl_spmv_kernel<RY, false, RY == 8 ? 1 : 0>, RY * 64, 256u), (unsigned)BEAT_MAX_PARTIALS) & ~7u;
 }
 }  // namespace
 
@@ -571,16 +563,14 @@ void beat_vtl_destroy(beat_pde* pde) {
   pde->vtl = nullptr;
 }
 
-// flags: tissue bits per 64-node segment of the slab (host copy).  Builds the per-row lane masks along z and the list of
-// tiles (column x run of planes with tissue), in (z block, row block, x segment) order, cut into eight equally heavy parts.
+// flags: tissue bits per 64-node segment of the slab (host copy).  Reads the switches, has vtl_plan (beat_var_plan.h) build the per-row
+// lane masks along z and the lists of tiles (column x run of planes with tissue) in their eight equally heavy parts, uploads them.
 int beat_vtl_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) {
   // BEAT_VTL=0 keeps the segment-list kernel (var_spmv_kernel), which also serves every launch over part of a slab
   const char* sw = std::getenv("BEAT_VTL");
   if (sw != nullptr && sw[0] == '0') return BEAT_OK;
   const Geom& f = pde->g;
-  if (f.nz < 2 || f.nx < 2 || f.ny < 2) return BEAT_OK;  // 1-D / 2-D grids and single planes: the segment list
-  if (f.plane >= ((int64_t)1 << 28)) return BEAT_OK;      // 32-bit byte offsets inside a plane
-  if ((int64_t)(f.ny + 2) * ((f.nx + SEG - 1) / SEG) * (f.nz + 6) >= ((int64_t)1 << 31)) return BEAT_OK;  // 32-bit mask offsets
+  if (vtl_sizes_declined(f.nx, f.ny, f.nz)) return BEAT_OK;
   VtlData* d = new VtlData();
   {
     const char* e = std::getenv("BEAT_VTL_RY");
@@ -606,159 +596,46 @@ int beat_vtl_setup(beat_pde* pde, const std::vector<unsigned long long>& flags) 
   }
   int max_run = 16;
   if (const char* e = std::getenv("BEAT_VTL_RUN")) max_run = std::max(1, std::atoi(e));
+  // BEAT_VTL_ALIGN=1: every tile of a z block covers the block's tissue range as a whole, 2: the whole block.  Measured, within
+  // +-2 % of tiles trimmed to their own tissue (the default)
   int aligned = 0;
   if (const char* e = std::getenv("BEAT_VTL_ALIGN")) aligned = std::atoi(e);
-  const int RY = d->ry;
-  const int nsegx = (f.nx + SEG - 1) / SEG, nrb = (f.ny + RY - 1) / RY;
-  const int nzp = f.nz + 6;  // planes -1 .. nz, and what the march reads ahead of its last plane
-  d->nsegx = nsegx;
-  d->nzp = nzp;
-  auto tissue = [&](int64_t i) -> u64 { return (flags[(size_t)(i >> 6)] >> (i & 63)) & 1ull; };
-  // mask[(y + 1) nsegx + seg][z + 1]: bit l = node (62 seg - 1 + l, y, z) is a tissue node of this slab; on a ghost plane
-  // that another rank owns: the node is inside the box (its p is live; which of them are tissue is not known here)
-  std::vector<u64> mask((size_t)(f.ny + 2) * nsegx * nzp, 0ull);
-  for (int y = 0; y < f.ny; ++y)
-    for (int s = 0; s < nsegx; ++s) {
-      u64* row = mask.data() + ((size_t)(y + 1) * nsegx + s) * nzp + 1;
-      u64 box = 0ull;
-      for (int l = 0; l < 64; ++l) {
-        const int gx = s * SEG - 1 + l;
-        if (gx >= 0 && gx < f.nx) box |= 1ull << l;
-      }
-      if (!f.z_lo_phys) row[-1] = box;
-      if (!f.z_hi_phys) row[f.nz] = box;
-      for (int z = 0; z < f.nz; ++z) {
-        const int64_t base = (int64_t)z * f.plane + (int64_t)y * f.nx + (int64_t)s * SEG - 1;
-        u64 m = 0ull;
-        for (int l = 0; l < 64; ++l)
-          if (((box >> l) & 1ull) && tissue(base + l)) m |= 1ull << l;
-        row[z] = m;
-      }
-    }
-  const u64 out_lanes = ((1ull << SEG) - 1ull) << 1;  // lanes 1..62
-  std::vector<char> act((size_t)f.nz);
-  // the tiles of the planes [z_lo, z_hi), in (z block, row block, x segment) order; false if there are more than partial slots
-  auto build = [&](int z_lo, int z_hi, int run, std::vector<VtlItem>& items) -> bool {
-    items.clear();
-    if (z_hi <= z_lo) return true;
-    for (int rb = 0; rb < nrb; ++rb)
-      for (int seg = 0; seg < nsegx; ++seg) {
-        bool any = false;
-        for (int z = z_lo; z < z_hi; ++z) {
-          u64 m = 0ull;
-          for (int y = rb * RY; y < std::min(f.ny, rb * RY + RY); ++y) m |= mask[((size_t)(y + 1) * nsegx + seg) * nzp + 1 + z];
-          act[(size_t)z] = (m & out_lanes) != 0ull;
-          any |= act[(size_t)z] != 0;
-        }
-        if (!any) continue;
-        if (aligned) {
-          // every tile of a z block covers the block's tissue range as a whole (BEAT_VTL_ALIGN=2: the whole block): measured,
-          // within +-2 % of tiles trimmed to their own tissue
-          for (int b0 = (z_lo / run) * run; b0 < z_hi; b0 += run) {
-            const int c0 = std::max(b0, z_lo), c1 = std::min(z_hi, b0 + run);
-            int lo = c1, hi = c0;
-            for (int z = c0; z < c1; ++z)
-              if (act[(size_t)z]) {
-                lo = std::min(lo, z);
-                hi = std::max(hi, z + 1);
-              }
-            if (lo >= hi) continue;
-            items.push_back(aligned == 2 ? VtlItem{seg, rb, c0, c1} : VtlItem{seg, rb, lo, hi});
-          }
-          continue;
-        }
-        int z = z_lo;
-        while (z < z_hi) {
-          if (!act[(size_t)z]) {
-            ++z;
-            continue;
-          }
-          // a run never crosses a multiple of `run`: tiles of one z block are neighbours in the list
-          const int stop = std::min(z_hi, (z / run + 1) * run);
-          int e = z + 1, last = z + 1;  // grow the run over gaps of up to two planes
-          while (e < stop && (act[(size_t)e] || e - last < 2)) {
-            if (act[(size_t)e]) last = e + 1;
-            ++e;
-          }
-          items.push_back(VtlItem{seg, rb, z, last});
-          z = last;
-        }
-      }
-    std::stable_sort(items.begin(), items.end(), [&](const VtlItem& p, const VtlItem& q) {
-      const int zp = p.zb / run, zq = q.zb / run;
-      if (zp != zq) return zp < zq;
-      if (p.rb != q.rb) return p.rb < q.rb;
-      return p.seg < q.seg;
-    });
-    return (int64_t)items.size() <= BEAT_MAX_PARTIALS;
-  };
-  // eight contiguous parts of equal weight (planes + a prologue's worth per tile); indices into the concatenated array
-  auto parts = [&](const std::vector<VtlItem>& items, int base, int (&first)[9]) {
-    std::vector<int64_t> cum(items.size() + 1, 0);
-    for (size_t k = 0; k < items.size(); ++k) cum[k + 1] = cum[k] + (items[k].ze - items[k].zb) + 2;
-    first[0] = 0;
-    for (int x = 1; x < 8; ++x) {
-      const int64_t want = cum.back() * x / 8;
-      first[x] = (int)(std::lower_bound(cum.begin(), cum.end(), want) - cum.begin());
-      first[x] = std::max(first[x - 1], std::min(first[x], (int)items.size()));
-    }
-    first[8] = (int)items.size();
-    for (int x = 0; x < 9; ++x) first[x] += base;
-  };
-  std::vector<VtlItem> items, part_items[2];
-  // (one partial sum of p.q per tile: longer runs if there would be more tiles than partial slots)
-  bool fits = false;
-  for (; !(fits = build(0, f.nz, max_run, items)) && max_run < f.nz; max_run *= 2) {
-  }
-  if (!fits) {  // (a plane of more than 16384 tiles: the segment-list kernel)
+  VtlPlanOptions opt;
+  opt.ry = d->ry;
+  opt.max_run = max_run;
+  opt.aligned = aligned;
+  opt.max_items = BEAT_MAX_PARTIALS;
+  const VtlPlan plan = vtl_plan(f.nx, f.ny, f.nz, f.z_lo_phys != 0, f.z_hi_phys != 0, flags, opt);
+  if (plan.declined) {  // (a plane of more than 16384 tiles: the segment-list kernel)
     delete d;
     return BEAT_OK;
   }
-  if (!(f.z_lo_phys && f.z_hi_phys)) {
-    // a decomposed grid: the planes that need no ghost plane of p (their launch overlaps the exchange), then the one or two
-    // slab-boundary planes (beat_slab_part)
-    const SlabPart inner = beat_slab_part(pde, 0), boundary = beat_slab_part(pde, 1);
-    std::vector<VtlItem> plane_items;
-    bool ok = build(inner.range[0].z_lo, inner.range[0].z_hi, max_run, part_items[0]);
-    for (int k = 0; k < boundary.count; ++k) {
-      ok = build(boundary.range[k].z_lo, boundary.range[k].z_hi, max_run, plane_items) && ok;
-      part_items[1].insert(part_items[1].end(), plane_items.begin(), plane_items.end());
-    }
-    if (!ok || (int64_t)part_items[0].size() + (int64_t)part_items[1].size() > BEAT_MAX_PARTIALS) {
-      part_items[0].clear();  // (the split launches keep the segment-list kernel)
-      part_items[1].clear();
-    }
-  }
-  int first[3][9];
-  d->list_base[0] = 0;
-  d->list_count[0] = (int)items.size();
-  parts(items, 0, first[0]);
-  for (int k = 0; k < 2; ++k) {
-    d->list_base[k + 1] = (int)items.size();
-    d->list_count[k + 1] = (int)part_items[k].size();
-    parts(part_items[k], d->list_base[k + 1], first[k + 1]);
-    items.insert(items.end(), part_items[k].begin(), part_items[k].end());
+  d->nsegx = plan.nsegx;
+  d->nzp = plan.nzp;
+  for (int k = 0; k < 3; ++k) {
+    d->list_base[k] = plan.list_base[k];
+    d->list_count[k] = plan.list_count[k];
   }
   d->nitems = d->list_count[0];
   pde->vtl = d;
-  hipError_t e = hipMalloc(&d->d_items, sizeof(VtlItem) * std::max<size_t>(1, items.size()));
-  if (e == hipSuccess && !items.empty()) e = hipMemcpy(d->d_items, items.data(), sizeof(VtlItem) * items.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d->d_xcd_first, sizeof(first) + 9 * sizeof(int));
-  if (e == hipSuccess) e = hipMemset(d->d_xcd_first, 0, sizeof(first) + 9 * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(d->d_xcd_first, first, sizeof(first), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d->d_mask, sizeof(u64) * mask.size());
-  if (e == hipSuccess) e = hipMemcpy(d->d_mask, mask.data(), sizeof(u64) * mask.size(), hipMemcpyHostToDevice);
+  // per list the 9 entries of its parts, then the 9 counters (zero)
+  std::vector<int> xcd_first(36, 0);
+  for (int k = 0; k < 3; ++k) std::copy(plan.first[k], plan.first[k] + 9, xcd_first.begin() + 9 * k);
+  hipError_t e = beat_upload(&d->d_items, plan.items);
+  if (e == hipSuccess) e = beat_upload(&d->d_xcd_first, xcd_first);
+  if (e == hipSuccess) e = beat_upload(&d->d_mask, plan.mask);
   if (e != hipSuccess) {
     beat_vtl_destroy(pde);
     beat_set_error("beat_vtl_setup: %s", hipGetErrorString(e));
     return BEAT_EHIP;
   }
+  const int RY = d->ry;
   d->resident = RY == 8 ? vtl_resident_blocks<8>() : vtl_resident_blocks<4>();
   if (std::getenv("BEAT_VTL_VERBOSE")) {
     long planes = 0;
-    for (int k = 0; k < d->nitems; ++k) planes += items[(size_t)k].ze - items[(size_t)k].zb;
+    for (int k = 0; k < d->nitems; ++k) planes += plan.items[(size_t)k].ze - plan.items[(size_t)k].zb;
     std::fprintf(stderr, "vtl: RY %d, %d x %d columns, %d tiles (+ %d / %d for the split launches), %.1f planes per tile, %u resident blocks\n", RY,
-                 nsegx, nrb, d->nitems, d->list_count[1], d->list_count[2], d->nitems ? (double)planes / d->nitems : 0.0, d->resident);
+                 plan.nsegx, (f.ny + RY - 1) / RY, d->nitems, d->list_count[1], d->list_count[2], d->nitems ? (double)planes / d->nitems : 0.0, d->resident);
   }
   return BEAT_OK;
 }

@@ -14,8 +14,8 @@ Masks, each a deterministic function of the cell grid (cells are numbered x fast
   cutshell  the ellipsoidal shell 0.6 < r < 1.25 of tests/test_var_gpu.py's _shell_case, scaled so that it cuts every face of the
             box: tissue and tissue-free nodes on each of them;
   layers    single cell layers along z, layer c active where c % 12 is 0, 3 or 7: 2, 3 and 4 inactive layers between them, i.e.
-            1, 2 and 3 node planes without tissue -- beat_vtl_setup grows a run of planes over gaps of up to two and cuts it at
-            three.  A box of fewer than 13 cell layers holds the first gaps only (layers_gaps says which);
+            1, 2 and 3 node planes without tissue -- csrc/beat_var_plan.h (grow_runs) grows a run of planes over gaps of up to two and
+            cuts it at three.  A box of fewer than 13 cell layers holds the first gaps only (layers_gaps says which);
   specks    isolated single cells (an 8-node system of their own each; those at i, j or k = 0 lie on a face), a line of cells along
             x over the cells 58 .. 64, whose nodes cross the end of the first 62-node x-segment (node 61 / 62), a line along y over
             the cells 5 .. 8, whose nodes cross the end of the first 8-row block (row 7 / 8), and every third cell of the last x column
@@ -41,7 +41,7 @@ SHAPES = {
     (3, 70, 3): 3,      # many row blocks, ny % 8 = 6
     (6, 4, 71): 3,      # many runs along z
     (2, 2, 2): 3,       # the smallest box the tiles take
-    (41, 32, 1): 2,     # 2-D and 1-D: beat_vtl_setup declines, the segment-list kernels run
+    (41, 32, 1): 2,     # 2-D and 1-D: the tile plan declines (vtl_sizes_declined, csrc/beat_var_plan.h), the segment-list kernels run
     (65, 1, 1): 1,
 }
 ALL_ROUTE_SHAPES = ((125, 18, 20), (62, 9, 5))  # every route of the GPU test runs on these, with every mask

@@ -22,7 +22,7 @@ Per case, in this process (the switches are read per operator):
            place where the e operand of the tile RES pass and of var_rhs_kernel shows in an iterate;
   routes   each asserted through beat_pde_tile_route (1 tiles | 2 fused PDOT pass | 4 right-hand side on the tiles | 8 ring of 12),
            expected_route below: default 15 on a 3-D box with ny >= 16, 9 on a 3-D box with ny < 16 (tiles of 4 rows carry neither the
-           fused pass nor the right-hand side passes), 8 on 2-D and 1-D boxes (beat_vtl_setup declines);
+           fused pass nor the right-hand side passes), 8 on 2-D and 1-D boxes (the tile plan declines: vtl_sizes_declined, csrc/beat_var_plan.h);
            BEAT_VTL=0 (8: the segment-list kernels), BEAT_VTL_PDOT=0 (the three-kernel iteration), BEAT_VTL_RHS=0 (the gather
            right-hand side), BEAT_VTL_RY=4 (where ny >= 16), BEAT_VTL_RUN=5, BEAT_VTL_DYNAMIC=1, BEAT_VAR_RING=6, and BEAT_VRR=1 with
            BEAT_VRR_RY 2 and 4.  The marching kernel of beat_pde_vrr.hip serves beat_pde_spmv_dot only, which the fused pass

@@ -142,7 +142,7 @@ def test_the_masks_together_hold_every_gap_and_every_line_feature():
     for c in CASES:
         if c[1] == "layers":
             gaps |= gaps_along_z(vr.case(c))
-    assert gaps == {1, 2, 3}  # beat_vtl_setup grows a run over gaps of 1 and 2 planes and cuts it at 3
+    assert gaps == {1, 2, 3}  # csrc/beat_var_plan.h (grow_runs) grows a run over gaps of 1 and 2 planes and cuts it at 3
     assert gaps_along_z(vr.case(((125, 18, 20), "layers"))) == {1, 2, 3}
     feats = [vr.specks_features(s) for s, m in CASES if m == "specks"]
     assert any(f["x_line_crosses_61_62"] for f in feats) and any(f["x_line_ends_at_61"] for f in feats)
