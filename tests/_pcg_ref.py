@@ -74,6 +74,22 @@ SMALL_GUESS_SHAPES = ((41, 15, 7), (129, 7, 6), (64, 32, 1), (32, 16, 16))
 SMALL_THREADS, SMALL_MAX_PER_THREAD, SMALL_TABW, SMALL_LDS_LIMIT = 512, 16, 16, 150 * 1024
 CHUNK_SHAPES = ((130, 6, 9), (129, 7, 6), (63, 5, 4), (1, 1, 7))  # every z-chunk length BEAT_RR_BLOCKS can ask for
 GUESS_SHAPES = ((65, 3, 5), (129, 7, 6), (130, 6, 9), (257, 5, 1))
+# The slab-decomposed solve (tests/test_dist_iterates_gpu.py): shape -> numbers of ranks.  beat._engine.Slab(nz, rank, world) deals
+# the planes evenly, the first ranks take the extra one; tests/test_dist_cases_cpu.py holds what each line is there for to the tables.
+DIST_CASES = {
+    (64, 4, 3): (2, 3),        # one aligned segment; 2 + 1 planes; three one-plane slabs
+    (63, 5, 4): (2, 4),        # second segment of one node; ny % 4 = 1
+    (65, 3, 5): (2, 3, 5),     # halo-lane-only segment; 3 + 2, 2 + 2 + 1, five one-plane slabs
+    (129, 7, 6): (2, 3),       # three segments; ny % 2 = 1
+    (130, 6, 9): (2, 3, 4),    # three segments; 5 + 4, 3 + 3 + 3, 3 + 2 + 2 + 2
+    (3, 70, 2): (2,),          # many row blocks; both slabs one plane, one ghost plane each
+    (125, 4, 2): (2,),         # one-plane slabs
+    (128, 2, 2): (2,),
+    (2, 2, 2): (2,),           # the smallest box that can be cut
+    (1, 1, 7): (2, 7),         # collapsed axes in front of z; seven one-node slabs
+}
+DIST_GUESS_CASES = (((65, 3, 5), 3), ((130, 6, 9), 2))  # (shape, world): the ghost plane of the guess increment travels with v_
+DIST_RY4_MIN_NY = 4        # BEAT_RR_RY=4 runs on the shapes with at least one full block of four rows
 SEED_SHIFT: dict = {}  # shape -> added to its seed, should a seed put a stop within 1e-6 of its threshold (test_pcg_ref_cpu)
 
 
@@ -278,10 +294,30 @@ def guess_increment(order: int, increments) -> np.ndarray:
     return e
 
 
-def pcg_iterates(A, b, x0, dinv, kmax: int, dtype):
+def slab_counts(nz: int, world: int) -> list:
+    """Planes per rank as beat._engine.Slab deals them without weights (tests/test_dist_cases_cpu.py holds the two together)."""
+    base, extra = divmod(nz, world)
+    return [base + (1 if r < extra else 0) for r in range(world)]
+
+
+def slab_dot(bounds):
+    """a . b summed slab by slab (entries [bounds[r], bounds[r + 1]) are rank r's) and the slabs in rank order: the order the
+    decomposed solve reduces in."""
+    def dot(a, b):
+        total = a[bounds[0]:bounds[1]] @ b[bounds[0]:bounds[1]]
+        for lo, hi in zip(bounds[1:-1], bounds[2:]):
+            total = total + a[lo:hi] @ b[lo:hi]
+        return total
+    return dot
+
+
+def pcg_iterates(A, b, x0, dinv, kmax: int, dtype, dot=None):
     """Jacobi-PCG (oracle/fem.pcg_jacobi) in ``dtype`` (np.longdouble or np.float64) without a stopping test:
     ([x_1 .. x_kmax], [||r_1|| .. ||r_kmax||] of the recurrence residual, ||b||).  The single-reduction form of the decomposed
-    solve computes the same iterates in exact arithmetic (Chronopoulos & Gear), so this serves it too."""
+    solve computes the same iterates in exact arithmetic (Chronopoulos & Gear), so this serves it too.  ``dot``: the dot product
+    (default a @ b; slab_dot for the summation order of a decomposition)."""
+    if dot is None:
+        dot = lambda a, b: a @ b  # noqa: E731
     if dtype is np.longdouble:
         assert np.finfo(np.longdouble).nmant >= 63, "np.longdouble has no 64-bit mantissa on this platform"
     else:
@@ -290,21 +326,21 @@ def pcg_iterates(A, b, x0, dinv, kmax: int, dtype):
     r = b - matvec(A, x, dtype)
     z = dinv * r
     p = z.copy()
-    rz = r @ z
+    rz = dot(r, z)
     xs, rnorms = [], []
     for _ in range(kmax):
         q = matvec(A, p, dtype)
-        alpha = rz / (p @ q)
+        alpha = rz / dot(p, q)
         x = x + alpha * p
         r = r - alpha * q
         z = dinv * r
-        rz_new = r @ z
+        rz_new = dot(r, z)
         beta = rz_new / rz
         rz = rz_new
         p = z + beta * p
         xs.append(x)
-        rnorms.append(np.sqrt(r @ r))
-    return xs, rnorms, np.sqrt(b @ b)
+        rnorms.append(np.sqrt(dot(r, r)))
+    return xs, rnorms, np.sqrt(dot(b, b))
 
 
 @dataclass

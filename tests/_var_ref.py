@@ -56,6 +56,19 @@ RING = 12                       # PRING_MAX of csrc/beat_pde_internal.h: the dir
 RING_SHORT = 6                  # PRING: BEAT_VAR_RING=6
 CUTS = (1, 2, 3, RING + 1)      # max_it of the cut solves: 13 = a full ring flushed and the first direction of the second cycle
 CUTS_SHORT = (1, 2, 3, RING_SHORT + 1)
+# The slab-decomposed solve (tests/test_dist_iterates_gpu.py): (case, numbers of ranks); tests/test_dist_cases_cpu.py holds what each
+# line is there for to the masks and to beat._engine.Slab
+DIST_CASES = [(((125, 18, 20), m), (2, 3, 4)) for m in MASKS] + [  # 8-row tiles with a 2-row remainder; runs of planes cut by slab faces
+    (((63, 16, 6), "full"), (2, 3)),       # two full row blocks
+    (((63, 16, 6), "specks"), (2, 3)),
+    (((63, 16, 6), "layers"), (2, 6)),     # 6 ranks: one-plane slabs, ranks 2 and 5 own no tissue node
+    (((62, 9, 5), "full"), (2, 5)),        # 4-row tiles: no fused pass; the gather right-hand side in parts
+    (((62, 9, 5), "layers"), (2, 5)),
+    (((3, 70, 3), "full"), (3,)),          # one-plane slabs; ny % 8 = 6
+    (((6, 4, 71), "layers"), (2, 8)),      # many runs along z, cut at 7 faces
+    (((2, 2, 2), "full"), (2,)),           # the smallest box that can be cut
+]
+DIST_GUESS_CASES = ((((63, 16, 6), "full"), 2), (((125, 18, 20), "cutshell"), 3))  # (case, world)
 SEED_SHIFT: dict = {}           # case -> added to its seed, should a seed put a stop within 1e-6 of its threshold (test_var_ref_cpu)
 
 
