@@ -138,6 +138,36 @@ def guess_solves(make, ctx, sl, fields, weights, res):
         res[f"e/order={order}|tile"] = report(ops, solver.libcomm)["tile"]
 
 
+def retime_solves(make, ctx, sl, fields, weights, cuts, res):
+    """A live handle with a guess of order 3 through ref.RETIME on every rank: the cut sequence (NO guess_reset between the cuts) under
+    cn on the handle as created ("live0"), GUESS_SOLVES converged solves of the moving field, set_timestep(skew) and the cut sequence
+    ("live1"), back to cn ("live2"); and the cut sequence of a fresh handle created under skew ("fresh").  set_timestep is a call of
+    each rank on its own handle, between two collective solves."""
+    def sequence(ops, solver, tag):
+        fv, fx = ops.new_field(), ops.new_field()
+        ws = fields_of(ops, [w[sl] for w in weights])
+        fv.set(fields[0][sl])
+        for k in cuts:
+            fx.fill(float("nan"))
+            r = solver.solve(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP)
+            ctx.synchronize()
+            res[f"retime/{tag}/k={k}"] = (fx.numpy().copy(), rec_of(r))
+        said = report(ops, solver.libcomm)
+        res[f"retime/{tag}|tile"], res[f"retime/{tag}|rr"] = said["tile"], said["rr_route"]
+        return fv, fx, ws
+
+    ops, solver = make(3, ref.RETIME[0])
+    fv, fx, ws = sequence(ops, solver, "live0")
+    for stage, name in enumerate(ref.RETIME[1:], start=1):
+        for j in range(1, ref.GUESS_SOLVES + 1):
+            fv.set(fields[j][sl])
+            r = solver.solve(fv, ws, ref.STIM_AMPS, fx, max_it=MAX_IT, rtol=ref.GUESS_RTOL, atol=1e-300)
+            assert r.converged_reason > 0, (stage, j, r)
+        ops.set_timestep(*ref.opset(name).triple)  # drops the history: no guess_reset here
+        sequence(ops, solver, f"live{stage}")
+    sequence(*make(3, ref.RETIME[1]), "fresh")
+
+
 def gather(base, results, keep=None):
     """The ranks' results under the keys of the parent: x assembled (on the nodes of `keep`), records, reports, directions."""
     for tail in results[0]:
@@ -147,7 +177,7 @@ def gather(base, results, keep=None):
                 slips.append(f"{base}: a solve changed v on rank {vals.index(False)}, or left an update pending")
         elif tail.startswith("|"):
             out[base + tail] = np.array(vals)
-        elif tail.endswith("|tile"):
+        elif tail.endswith("|tile") or tail.endswith("|rr"):
             out[f"{base}/{tail}"] = np.array(vals)
         elif tail.endswith("|p"):
             for rank, p in enumerate(vals):
@@ -167,49 +197,52 @@ def set_switches(switches):
     os.environ.update(switches)
 
 
-def run_const(shape, world, loop, guess):
+def run_const(shape, world, loop, guess, opset="cn", plain=True, retime=False):
     nx, ny, nz = shape
     plane = nx * ny
     mt, kt = ref.tables(3)
     weights = ref.problem(shape).weights
-    fields = [ref.field(shape, j) for j in range(ref.GUESS_SOLVES + 2)] if guess else [ref.field(shape)]
+    fields = [ref.field(shape, j) for j in range(ref.GUESS_SOLVES + 2)] if guess or retime else [ref.field(shape)]
 
     def work(rank, ctx, view):
         slab = Slab(nz, rank, world)
         sl = slice(slab.z0 * plane, slab.z1 * plane)
         comm = LibComm(ctx, slab, view, None, "callbacks")
 
-        def make(order):
+        def make(order, name=opset):
             ops = HipOps(ctx, (nx, ny, slab.nz), slab.lo_phys, slab.hi_phys, mt, kt)
             ops.set_small(False)
             ops.set_guess_order(order)
-            ops.set_timestep(ref.C_M, ref.THETA, ref.DT)
+            ops.set_timestep(*ref.opset(name).triple)
             if loop == "M":
                 ops.set_single_reduction(True)
             return ops, DiffusionSolver(ops, slab, force_distributed=True, libcomm=comm)
 
         res = {}
         try:
-            ops, solver = make(0)
-            plain_solves(ops, solver, ctx, sl, fields[0], weights, ref.CUTS, res)
-            for name, value in report(ops, comm).items():
-                res[f"|{name}"] = value
+            if plain:
+                ops, solver = make(0)
+                plain_solves(ops, solver, ctx, sl, fields[0], weights, ref.CUTS, res)
+                for name, value in report(ops, comm).items():
+                    res[f"|{name}"] = value
             if guess:
                 guess_solves(make, ctx, sl, fields, weights, res)
+            if retime:
+                retime_solves(make, ctx, sl, fields, weights, ref.CUTS, res)
         finally:
             comm.close()
         return res
 
     set_switches(CONST_LOOPS[loop])
-    gather(f"{ref.shape_key(shape)}/w{world}/{loop}", run_world(world, work))
+    gather(f"{ref.case_key(shape, opset)}/w{world}/{loop}", run_world(world, work))
 
 
-def run_var(case, world, route, guess):
+def run_var(case, world, route, guess, opset="cn", plain=True, retime=False):
     cs = vr.case(case)
     nx, ny, nz = cs.shape
     plane = nx * ny
     weights = vr.weights_on_box(cs)
-    fields = [vr.on_box(cs, vr.field(cs, j)) for j in range(ref.GUESS_SOLVES + 2 if guess else 1)]
+    fields = [vr.on_box(cs, vr.field(cs, j)) for j in range(ref.GUESS_SOLVES + 2 if guess or retime else 1)]
     cuts = vr.cuts_of(cs, vr.CUTS_SHORT)
 
     def work(rank, ctx, view):
@@ -219,26 +252,29 @@ def run_var(case, world, route, guess):
         mrows, krows = np.ascontiguousarray(cs.mass_rows[:, sl]), np.ascontiguousarray(cs.stiff_rows[:, sl])
         comm = LibComm(ctx, slab, view, None, "callbacks")
 
-        def make(order):
+        def make(order, name=opset):
             ops = HipOps(ctx, (nx, ny, slab.nz), slab.lo_phys, slab.hi_phys, mrows, krows, per_node=True)
             ops.set_guess_order(order)
-            ops.set_timestep(ref.C_M, ref.THETA, ref.DT)
+            ops.set_timestep(*ref.opset(name).triple)
             return ops, DiffusionSolver(ops, slab, force_distributed=True, libcomm=comm)
 
         res = {}
         try:
-            ops, solver = make(0)
-            plain_solves(ops, solver, ctx, sl, fields[0], weights, cuts, res)
-            for name, value in report(ops, comm).items():
-                res[f"|{name}"] = value
+            if plain:
+                ops, solver = make(0)
+                plain_solves(ops, solver, ctx, sl, fields[0], weights, cuts, res)
+                for name, value in report(ops, comm).items():
+                    res[f"|{name}"] = value
             if guess:
                 guess_solves(make, ctx, sl, fields, weights, res)
+            if retime:
+                retime_solves(make, ctx, sl, fields, weights, cuts, res)
         finally:
             comm.close()
         return res
 
     set_switches(VAR_ROUTES[route])
-    base = f"{vr.case_key(case)}/w{world}/{route}"
+    base = f"{vr.opset_key(case, opset)}/w{world}/{route}"
     gather(base, run_world(world, work), keep=cs.tissue)
     # off the tissue every node holds exactly its v: 1000 + node index (for the guess sequences too: the marks do not move)
     marks = vr.off_tissue_marks(cs)
@@ -260,12 +296,32 @@ def main():
             for world in worlds:
                 for loop in ("R", "M", "T") if child == "rr2" else ("R", "M"):
                     run_const(shape, world, loop, guess=loop in "RM" and (shape, world) in ref.DIST_GUESS_CASES)
+        t1 = time.perf_counter()
+        if child == "rr2":  # off theta = 1/2 (keys shape@set), and the re-timing of live handles on loop R
+            for (shape, world), sets in ref.DIST_OPSET_CASES.items():
+                for name in sets:
+                    for loop in ("R", "M", "T"):
+                        run_const(shape, world, loop, guess=loop in "RM" and name in ref.DIST_OPSET_GUESS.get((shape, world), ()), opset=name)
+            shape, world = next(iter(ref.DIST_OPSET_CASES))
+            run_const(shape, world, "R", guess=False, opset="cn", plain=False, retime=True)
+        out["opsets_seconds"] = np.array(time.perf_counter() - t1)
     else:
         assert child[:3] == "var" and child[3:] in VAR_ROUTES  # one route per child: each stays at a few seconds
         route = child[3:]
         for case, worlds in vr.DIST_CASES:
             for world in worlds:
                 run_var(case, world, route, guess=route in "FS" and (case, world) in vr.DIST_GUESS_CASES)
+        t1 = time.perf_counter()
+        for (case, world), sets in vr.DIST_OPSET_CASES.items():  # off theta = 1/2 (keys case@set)
+            for name in sets:
+                run_var(case, world, route, guess=False, opset=name)
+        for (case, world), sets in vr.DIST_OPSET_GUESS.items():
+            for name in sets:
+                if route in "FS":
+                    run_var(case, world, route, guess=True, opset=name, plain=False)
+        case, world = next(iter(vr.DIST_OPSET_CASES))
+        run_var(case, world, route, guess=False, opset="cn", plain=False, retime=True)  # re-forms v_gc0 on route F
+        out["opsets_seconds"] = np.array(time.perf_counter() - t1)
     set_switches({})
     for ctx in contexts.values():
         ctx.synchronize()

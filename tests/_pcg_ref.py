@@ -11,13 +11,36 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from math import comb
+from typing import NamedTuple
 
 import numpy as np
 import scipy.sparse as sp
 
 from oracle import fem
 
-C_M, THETA, DT, H = 0.01, 0.5, 0.05, 0.1
+
+
+class OpSet(NamedTuple):
+    """(C_m, theta, dt) of A = C_m Mass + theta dt K and B = C_m Mass - (1 - theta) dt K: a property of a case, not of the module."""
+    name: str
+    c_m: float
+    theta: float
+    dt: float
+
+    @property
+    def triple(self) -> tuple:
+        return (self.c_m, self.theta, self.dt)
+
+
+# cn:   Crank-Nicolson, the operator of every case from before the sets had names: the factor of K in A equals the one in B, so a
+#       theta written for 1 - theta, or the reverse, changes nothing there;
+# be:   backward Euler: (1 - theta) dt = 0 exactly, B = C_m Mass, theta dt = dt -- which is why be alone cannot tell theta dt from dt;
+# skew: C_m = 0.013, theta dt = 0.02, (1 - theta) dt = 0.06 and dt = 0.08 are four different numbers: every factor told from every other.
+OPSETS = {"cn": OpSet("cn", 0.01, 0.5, 0.05), "be": OpSet("be", 0.01, 1.0, 0.05), "skew": OpSet("skew", 0.013, 0.25, 0.08)}
+CN = OPSETS["cn"]
+NEW_SETS = ("be", "skew")
+_, C_M, THETA, DT = CN  # the default set, for the modules whose cases are not diffusion cases of this table
+H = 0.1
 STIM_AMPS = (0.3, -0.15)  # dt amp / C_m = 1.5 and -0.75: the stimuli move x by as much as the noise in v does
 CUTS = (1, 2, 3, 7)       # max_it of the cut solves: the ring holds 6 directions, 7 = a full ring flush and a second cycle
 GUESS_CUTS = (1, 3)
@@ -90,12 +113,40 @@ DIST_CASES = {
 }
 DIST_GUESS_CASES = (((65, 3, 5), 3), ((130, 6, 9), 2))  # (shape, world): the ghost plane of the guess increment travels with v_
 DIST_RY4_MIN_NY = 4        # BEAT_RR_RY=4 runs on the shapes with at least one full block of four rows
+# The cases off theta = 1/2: shape -> sets (tests/test_pcg_ref_cpu.py holds every pair to the conditions of a case).  skew on a 1-D row
+# converges by iterate 7 (r_7 / ||b|| = 8.5e-14 on 64 x 1 x 1: no cut at 7), so the rows take be only.
+OPSET_SHAPES = {(65, 3, 5): NEW_SETS, (129, 7, 6): NEW_SETS, (257, 5, 1): NEW_SETS, (64, 1, 1): ("be",)}   # the register-row children
+OPSET_GUESS_SHAPES = ((65, 3, 5), (129, 7, 6))
+SMALL_OPSET_SHAPES = {(41, 15, 7): NEW_SETS, (64, 32, 1): NEW_SETS, (1, 5, 4): NEW_SETS}  # one-launch; 1 x 5 x 4 is declined: multi-launch
+SMALL_OPSET_GUESS_SHAPES = ((41, 15, 7), (64, 32, 1))
+DIST_OPSET_CASES = {((65, 3, 5), 3): NEW_SETS, ((130, 6, 9), 2): NEW_SETS}  # (shape, world) of DIST_CASES; these are DIST_GUESS_CASES too
+DIST_OPSET_GUESS = {((65, 3, 5), 3): ("skew",), ((130, 6, 9), 2): ("skew",)}
+RETIME = ("cn", "skew", "cn")  # a live handle: GUESS_SOLVES solves with a guess of order 3 under cn, set_timestep(skew), the cuts; back
 SEED_SHIFT: dict = {}  # shape -> added to its seed, should a seed put a stop within 1e-6 of its threshold (test_pcg_ref_cpu)
 
 
 def all_shapes() -> list:
     """SHAPES, then what SMALL_SHAPES adds to them."""
     return list(SHAPES) + [s for s in SMALL_SHAPES if s not in SHAPES]
+
+
+def opset(ops) -> OpSet:
+    """An OpSet from its name or itself."""
+    return ops if isinstance(ops, OpSet) else OPSETS[ops]
+
+
+def opset_pairs() -> list:
+    """Every (shape, set name) off cn that a constant-coefficient GPU test runs, each once."""
+    pairs = []
+    for table in (OPSET_SHAPES, SMALL_OPSET_SHAPES, {s: sets for (s, _), sets in DIST_OPSET_CASES.items()}):
+        pairs += [(s, name) for s, sets in table.items() for name in sets if (s, name) not in pairs]
+    return pairs
+
+
+def case_key(shape, ops="cn") -> str:
+    """shape_key for cn (the keys from before the sets had names do not change), shape@set otherwise."""
+    name = opset(ops).name
+    return shape_key(shape) if name == "cn" else f"{shape_key(shape)}@{name}"
 
 
 def dim_of(shape) -> int:
@@ -185,13 +236,30 @@ class Problem:
     A: sp.csr_matrix          # C_m Mass + theta dt K formed in float64
     weights: list             # two stimulus weight vectors (float64)
     n: int
+    ops: OpSet = CN           # the (C_m, theta, dt) A was formed with and the right-hand side is formed with
+
+    def with_ops(self, ops) -> "Problem":
+        """The same matrices, tables and stimuli under another set."""
+        ops = opset(ops)
+        A = sp.csr_matrix((ops.c_m * self.mass.data + ops.theta * ops.dt * self.stiff.data, self.mass.indices, self.mass.indptr), shape=self.mass.shape)
+        return Problem(self.shape, self.dim, self.mass_tab, self.stiff_tab, self.mass, self.stiff, A, self.weights, self.n, ops)
+
+    def rhs_float64(self, v: np.ndarray) -> np.ndarray:
+        """b in float64, the expression of rhs_longdouble written out again (the CPU tests hold the two together)."""
+        o = self.ops
+        return o.c_m * (self.mass @ v) - (1 - o.theta) * o.dt * (self.stiff @ v) + o.dt * sum(a * w for a, w in zip(STIM_AMPS, self.weights))
 
     def operator(self, dtype):
         """A = C_m Mass + theta dt K formed in ``dtype`` from the float64 entries of Mass and K."""
         if dtype is np.float64:
             return self.A
-        L = np.longdouble
-        return Csr(L(C_M) * self.mass.data.astype(L) + L(THETA) * L(DT) * self.stiff.data.astype(L), self.mass.indices, self.mass.indptr)
+        L, o = np.longdouble, self.ops
+        return Csr(L(o.c_m) * self.mass.data.astype(L) + L(o.theta) * L(o.dt) * self.stiff.data.astype(L), self.mass.indices, self.mass.indptr)
+
+    def diagonal(self, dtype) -> np.ndarray:
+        """diag A formed in ``dtype``, as operator forms A."""
+        o = self.ops
+        return dtype(o.c_m) * self.mass.diagonal().astype(dtype) + dtype(o.theta) * dtype(o.dt) * self.stiff.diagonal().astype(dtype)
 
 
 _problems: dict = {}
@@ -203,8 +271,8 @@ def tables(dim: int):
     two cells per axis).  The device is given THESE tables and the host their expansion: the same float64 numbers on both sides.
     (Matrices assembled on the whole mesh differ from them in the last digits, from node to node -- 0.1 is no dyadic spacing --
     and x = A^-1 b moves by ~20 ulp with them, which has nothing to do with the kernels; test_pcg_ref_cpu compares the two.)"""
-    if dim not in _tables:
-        _tables[dim] = fem.stencil_table(dim, (H,) * dim, conductivity(dim), C_M, THETA * DT)
+    if dim not in _tables:  # (C_m and theta dt are not folded into the tables: one pair of tables serves every set)
+        _tables[dim] = fem.stencil_table(dim, (H,) * dim, conductivity(dim), CN.c_m, CN.theta * CN.dt)
     return _tables[dim]
 
 
@@ -253,16 +321,20 @@ def assembled(shape):
     return sub(fem.assemble_mass(mesh)), sub(fem.assemble_stiffness(mesh, conductivity(dim))), weights
 
 
-def problem(shape) -> Problem:
-    shape = tuple(int(s) for s in shape)
+def problem(shape, ops="cn") -> Problem:
+    shape, ops = tuple(int(s) for s in shape), opset(ops)
+    if ops != CN:
+        if (shape, ops) not in _problems:
+            _problems[(shape, ops)] = problem(shape).with_ops(ops)
+        return _problems[(shape, ops)]
     if shape in _problems:
         return _problems[shape]
     dim = dim_of(shape)
     mt, kt = tables(dim)
     mass, stiff = expand(mt, shape), expand(kt, shape)
     assert np.array_equal(mass.indices, stiff.indices) and np.array_equal(mass.indptr, stiff.indptr)
-    A = sp.csr_matrix((C_M * mass.data + THETA * DT * stiff.data, mass.indices, mass.indptr), shape=mass.shape)
-    p = Problem(shape, dim, mt, kt, mass, stiff, A, assembled(shape)[2], mass.shape[0])
+    A = sp.csr_matrix((CN.c_m * mass.data + CN.theta * CN.dt * stiff.data, mass.indices, mass.indptr), shape=mass.shape)
+    p = Problem(shape, dim, mt, kt, mass, stiff, A, assembled(shape)[2], mass.shape[0], CN)
     assert p.n == int(np.prod(shape))
     _problems[shape] = p
     return p
@@ -274,8 +346,9 @@ def matvec(m, x: np.ndarray, dtype) -> np.ndarray:
 
 
 def rhs_longdouble(p: Problem, v: np.ndarray) -> np.ndarray:
-    """b = (C_m Mass - (1 - theta) dt K) v + dt sum amp_j w_j, in longdouble."""
+    """b = (C_m Mass - (1 - theta) dt K) v + dt sum amp_j w_j, in longdouble, under the problem's set."""
     L = np.longdouble
+    C_M, THETA, DT = p.ops.triple
     assert np.finfo(L).nmant >= 63, "np.longdouble has no 64-bit mantissa on this platform"
     vl = v.astype(L)
     b = L(C_M) * matvec(p.mass, vl, L) - (L(1) - L(THETA)) * L(DT) * matvec(p.stiff, vl, L)
@@ -403,10 +476,10 @@ def kmax_of(shape) -> int:
 _plain: dict = {}
 
 
-def plain_reference(shape) -> Reference:
-    """The solve from x0 = v = field(shape), kmax_of(shape) iterations; computed once per shape."""
-    shape = tuple(shape)
-    if shape not in _plain:
-        p, v = problem(shape), field(shape)
-        _plain[shape] = reference(p, rhs_longdouble(p, v), v.astype(np.longdouble), kmax_of(shape))
-    return _plain[shape]
+def plain_reference(shape, ops="cn") -> Reference:
+    """The solve from x0 = v = field(shape), kmax_of(shape) iterations; computed once per shape and set."""
+    key = (tuple(shape), opset(ops))
+    if key not in _plain:
+        p, v = problem(*key), field(shape)
+        _plain[key] = reference(p, rhs_longdouble(p, v), v.astype(np.longdouble), kmax_of(shape))
+    return _plain[key]

@@ -5,7 +5,10 @@ per process, so tests/test_rr_iterates_gpu.py starts one interpreter per setting
 
 Every operator must report (beat_pde_rr_route) the instance of the register-row kernels the environment asked for, and be on the
 register-row loop at all -- or the LDS-tiled loop would be tested in its place without anybody noticing.  Writes, per case key,
-x, the solve's record (iterations, converged_reason, residual_norm, rhs_norm) and the route report.  Computes no reference."""
+x, the solve's record (iterations, converged_reason, residual_norm, rhs_norm) and the route report.  Computes no reference.
+
+The children of (RY 2, PD 1) and (RY 4, PD 1) without BEAT_RR_BY_ROWS also run the pairs of ref.OPSET_SHAPES -- the operator off
+theta = 1/2, keys shape@set -- and the re-timing of a live handle (run_retime)."""
 import os
 import random
 import socket
@@ -43,7 +46,7 @@ def _free_port():
     raise RuntimeError("no free port")
 
 
-def make_ops(ctx, shape, predict=True, order=0):
+def make_ops(ctx, shape, predict=True, order=0, opset="cn"):
     mt, kt = ref.tables(ref.SHAPES[shape])  # the numbers the host reference expands into its matrices
     os.environ["BEAT_PCG_PREDICT_STOP"] = "1" if predict else "0"  # read when the operator is created
     try:
@@ -52,7 +55,7 @@ def make_ops(ctx, shape, predict=True, order=0):
         del os.environ["BEAT_PCG_PREDICT_STOP"]
     ops.set_small(False)  # the one-launch solve of small grids off: the multi-launch loop
     ops.set_guess_order(order)
-    ops.set_timestep(ref.C_M, ref.THETA, ref.DT)
+    ops.set_timestep(*ref.opset(opset).triple)
     return ops
 
 
@@ -91,12 +94,12 @@ def stimuli(ops, shape):
     return ws
 
 
-def run_loops(ctx, shape, key, chunked, expect_zc=None):
+def run_loops(ctx, shape, key, chunked, expect_zc=None, opset="cn"):
     """Loops (a) - (d) of one shape under the BEAT_RR_BLOCKS now in the environment, each on a fresh operator (the predicted stop's
     error constant, which depends on the chunking, is cached on the operator)."""
     v = ref.field(shape)
     for loop in "abcd":
-        ops = make_ops(ctx, shape, predict=loop != "b")
+        ops = make_ops(ctx, shape, predict=loop != "b", opset=opset)
         check_route(ops, f"{key}/{loop}", expect_zc)
         fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
         fv.set(v)
@@ -126,11 +129,11 @@ def chunk_settings(ctx, shape):
     return sorted((blocks, zc, avail) for (zc, avail), blocks in found.items())
 
 
-def run_guess(ctx, shape):
+def run_guess(ctx, shape, opset="cn"):
     """(e): four converged solves of a field that moves between solves, then a cut solve that starts from their extrapolation."""
     for order in ref.GUESS_ORDERS:
-        ops = make_ops(ctx, shape, order=order)
-        key = f"{ref.shape_key(shape)}/default/e/order={order}"
+        ops = make_ops(ctx, shape, order=order, opset=opset)
+        key = f"{ref.case_key(shape, opset)}/default/e/order={order}"
         check_route(ops, key)
         fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
         for k in ref.GUESS_CUTS:
@@ -144,6 +147,49 @@ def run_guess(ctx, shape):
             fv.set(ref.field(shape, ref.GUESS_SOLVES + 1))
             fx.fill(float("nan"))
             record(f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx)
+
+
+def cut_sequence(ops, key, fv, fx, ws):
+    """The cuts one after another with NO guess_reset between them: the first starts from x0 = v_ only if the history is empty."""
+    for k in ref.CUTS:
+        fx.fill(float("nan"))
+        record(f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx)
+
+
+def run_retime(ctx, shape):
+    """A live handle with a guess of order 3 through ref.RETIME: the cut sequence under cn on the handle as created ("live0"),
+    GUESS_SOLVES converged solves of the moving field (the history fills), set_timestep(skew) and the cut sequence ("live1"), back to
+    cn and the cut sequence ("live2"); and the cut sequence of a fresh handle created under skew ("fresh")."""
+    sk = ref.shape_key(shape)
+    ops = make_ops(ctx, shape, order=3, opset=ref.RETIME[0])
+    check_route(ops, f"{sk}/retime/live0")
+    fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
+    v = ref.field(shape)
+    fv.set(v)
+    cut_sequence(ops, f"{sk}/retime/live0", fv, fx, ws)
+    for stage, name in enumerate(ref.RETIME[1:], start=1):
+        for j in range(1, ref.GUESS_SOLVES + 1):
+            fv.set(ref.field(shape, j))
+            res = ops.solve_single(fv, ws, ref.STIM_AMPS, fx, ref.GUESS_RTOL, 1e-300, MAX_IT)
+            assert res.converged_reason > 0, (sk, stage, j, res)
+        fv.set(v)
+        ops.set_timestep(*ref.opset(name).triple)  # re-forms A, B and 1 / diag and drops the history: no guess_reset here
+        check_route(ops, f"{sk}/retime/live{stage}")
+        cut_sequence(ops, f"{sk}/retime/live{stage}", fv, fx, ws)
+    fresh = make_ops(ctx, shape, order=3, opset=ref.RETIME[1])
+    check_route(fresh, f"{sk}/retime/fresh")
+    fv2, fx2, ws2 = fresh.new_field(), fresh.new_field(), stimuli(fresh, shape)
+    fv2.set(v)
+    cut_sequence(fresh, f"{sk}/retime/fresh", fv2, fx2, ws2)
+
+
+def run_opsets(ctx):
+    for shape, sets in ref.OPSET_SHAPES.items():
+        for name in sets:
+            run_loops(ctx, shape, f"{ref.case_key(shape, name)}/default", False, opset=name)
+            if shape in ref.OPSET_GUESS_SHAPES:
+                run_guess(ctx, shape, opset=name)
+    run_retime(ctx, next(iter(ref.OPSET_SHAPES)))
 
 
 def main():
@@ -172,6 +218,12 @@ def main():
                 run_loops(ctx, shape, f"{sk}/default", False)
             if shape in ref.GUESS_SHAPES:
                 run_guess(ctx, shape)
+        out["opsets"] = np.array(WANT["pd"] == 1 and WANT["by_rows_mask"] == 0)
+        if out["opsets"]:
+            t1 = time.perf_counter()
+            run_opsets(ctx)
+            ctx.synchronize()
+            out["opsets_seconds"] = np.array(time.perf_counter() - t1)
         ctx.synchronize()
     finally:
         if shared["libcomm"] is not None:

@@ -69,6 +69,16 @@ DIST_CASES = [(((125, 18, 20), m), (2, 3, 4)) for m in MASKS] + [  # 8-row tiles
     (((2, 2, 2), "full"), (2,)),           # the smallest box that can be cut
 ]
 DIST_GUESS_CASES = ((((63, 16, 6), "full"), 2), (((125, 18, 20), "cutshell"), 3))  # (case, world)
+# The cases off theta = 1/2 (sets of tests/_pcg_ref.py), each at both of ref.NEW_SETS: a dense box whose right-hand side runs on the
+# 8-row tiles (the rows of B var_form_A_kernel forms), a shell on the same box, whose tissue meets across the edges of the x-segments
+# and of the row blocks, and a box of 4-row tiles, whose right-hand side is the gather kernel's on every route.  All three hold every
+# condition of a case under both sets (tests/test_var_ref_cpu.py; no mask or shape had to be moved).  Boxes of a few thousand nodes: the
+# 45 000 nodes of 125 x 18 x 20 add nothing that tells one factor from another.
+OPSET_CASES = (((63, 16, 6), "full"), ((63, 16, 6), "cutshell"), ((62, 9, 5), "layers"))
+OPSET_GUESS_CASES = (((63, 16, 6), "full"), ((62, 9, 5), "layers"))  # of GUESS_CASES
+OPSET_ROUTES = ("default", "three", "rows")  # of tests/test_var_iterates_gpu.py: the tile right-hand side twice, the gather kernel's
+DIST_OPSET_CASES = {(((63, 16, 6), "full"), 3): ref.NEW_SETS}   # (case, world) of DIST_CASES
+DIST_OPSET_GUESS = {(((63, 16, 6), "full"), 2): ("skew",)}      # of DIST_GUESS_CASES, the one of a few thousand nodes
 SEED_SHIFT: dict = {}           # case -> added to its seed, should a seed put a stop within 1e-6 of its threshold (test_var_ref_cpu)
 
 
@@ -244,14 +254,14 @@ def case(c) -> Case:
     tissue = mf[0] != 0.0
     mass, stiff = expand_rows(mf, shape, tissue), expand_rows(kf, shape, tissue)
     assert np.array_equal(mass.indices, stiff.indices) and np.array_equal(mass.indptr, stiff.indptr)
-    A = sp.csr_matrix((ref.C_M * mass.data + ref.THETA * ref.DT * stiff.data, mass.indices, mass.indptr), shape=mass.shape)
+    A = sp.csr_matrix((ref.CN.c_m * mass.data + ref.CN.theta * ref.CN.dt * stiff.data, mass.indices, mass.indptr), shape=mass.shape)
     # two stimuli over subsets of the active simplices: the first third, and every third of the second half
     act_s = np.nonzero(np.repeat(active, simplices_per_cell(dim)))[0]
     na = len(act_s)
     sets = (act_s[: max(1, na // 3)], act_s[na // 2:][1::3] if na >= 6 else act_s[-1:])
     mesh = mesh_of(cells)
     weights = [fem.stimulus_weights(mesh, s)[tissue] for s in sets]
-    p = ref.Problem(shape, dim, mf, kf, mass, stiff, A, weights, mass.shape[0])
+    p = ref.Problem(shape, dim, mf, kf, mass, stiff, A, weights, mass.shape[0], ref.CN)
     _cases[key] = Case(shape, mask, dim, cells, active, M, mf, kf, tissue, p, sets)
     return _cases[key]
 
@@ -309,13 +319,31 @@ def cuts_of(cs: Case, cuts=CUTS) -> tuple:
 
 
 _plain: dict = {}
+_problems: dict = {}
 
 
-def plain_reference(c) -> ref.Reference:
-    """The solve from x0 = v = field(case), kmax_of iterations; computed once per case."""
-    cs = case(c)
-    key = (cs.shape, cs.mask)
+def problem_of(c, ops="cn") -> ref.Problem:
+    """The case's matrices under a set of ref.OPSETS (case(c).problem is the one under cn)."""
+    cs, ops = case(c), ref.opset(ops)
+    if ops == ref.CN:
+        return cs.problem
+    key = (cs.shape, cs.mask, ops)
+    if key not in _problems:
+        _problems[key] = cs.problem.with_ops(ops)
+    return _problems[key]
+
+
+def opset_key(c, ops="cn") -> str:
+    """case_key for cn (the keys from before the sets had names do not change), case@set otherwise."""
+    name = ref.opset(ops).name
+    return case_key(c) if name == "cn" else f"{case_key(c)}@{name}"
+
+
+def plain_reference(c, ops="cn") -> ref.Reference:
+    """The solve from x0 = v = field(case), kmax_of iterations; computed once per case and set."""
+    cs, ops = case(c), ref.opset(ops)
+    key = (cs.shape, cs.mask) if ops == ref.CN else (cs.shape, cs.mask, ops)
     if key not in _plain:
-        v = field(cs)
-        _plain[key] = ref.reference(cs.problem, ref.rhs_longdouble(cs.problem, v), v.astype(np.longdouble), kmax_of(cs))
+        v, p = field(cs), problem_of(c, ops)
+        _plain[key] = ref.reference(p, ref.rhs_longdouble(p, v), v.astype(np.longdouble), kmax_of(cs))
     return _plain[key]

@@ -18,6 +18,10 @@ from _pcg_check import Check
 
 CONST = [(s, w) for s, worlds in ref.DIST_CASES.items() for w in worlds]
 VAR = [(c, w) for c, worlds in vr.DIST_CASES for w in worlds]
+# the worlds off theta = 1/2: (shape or case, world, set)
+CONST_SETS = [(s, w, name) for (s, w), sets in ref.DIST_OPSET_CASES.items() for name in sets]
+VAR_SETS = [(c, w, name) for (c, w), sets in vr.DIST_OPSET_CASES.items() for name in sets] + \
+    [(c, w, name) for (c, w), sets in vr.DIST_OPSET_GUESS.items() for name in sets if (c, w) not in vr.DIST_OPSET_CASES]
 # planes per rank the tables claim
 COUNTS = {
     ((64, 4, 3), 2): (2, 1), ((64, 4, 3), 3): (1, 1, 1),
@@ -50,6 +54,8 @@ def test_tables_are_consistent():
         assert (shape, world) in COUNTS
     assert all((s, w) in CONST for s, w in ref.DIST_GUESS_CASES) and all((c, w) in VAR for c, w in vr.DIST_GUESS_CASES)
     assert all(s in ref.GUESS_SHAPES for s, _ in ref.DIST_GUESS_CASES)
+    assert all((s, w) in CONST for s, w, _ in CONST_SETS) and all((c, w) in VAR for c, w, _ in VAR_SETS)
+    assert {(s, w) for s, w, _ in CONST_SETS} == {((65, 3, 5), 3), ((130, 6, 9), 2)} and any(w == 3 for _, w, _ in VAR_SETS)
     # BEAT_RR_RY=4 runs on the shapes with a full block of four rows, and those keep a one-plane slab and a middle slab
     ry4 = [(s, w) for s, w in CONST if s[1] >= ref.DIST_RY4_MIN_NY]
     assert {s for s, _ in ry4} == {(64, 4, 3), (63, 5, 4), (129, 7, 6), (130, 6, 9), (3, 70, 2), (125, 4, 2)}
@@ -142,18 +148,28 @@ def r_rhs(p, v):
 
 
 @pytest.mark.parametrize("shape,world", CONST, ids=lambda v: ref.shape_key(v) if isinstance(v, tuple) else f"w{v}")
-def test_bound_admits_the_decomposition_constant_coefficients(shape, world):
-    p, r = ref.problem(shape), ref.plain_reference(shape)
+def test_bound_admits_the_decomposition_constant_coefficients(shape, world, ops="cn"):
+    p, r = ref.problem(shape, ops), ref.plain_reference(shape, ops)
     plane = shape[0] * shape[1]
     bounds = [0] + [int(z) * plane for z in np.cumsum(ref.slab_counts(shape[2], world))]
-    slab_ordered_run_passes("const", f"{ref.shape_key(shape)}/w{world}", p, r, bounds, ref.field(shape), ref.CUTS)
+    slab_ordered_run_passes("const", f"{ref.case_key(shape, ops)}/w{world}", p, r, bounds, ref.field(shape), ref.CUTS)
+
+
+@pytest.mark.parametrize("shape,world,ops", CONST_SETS, ids=lambda v: v if isinstance(v, str) else ref.shape_key(v) if isinstance(v, tuple) else f"w{v}")
+def test_bound_admits_the_decomposition_off_theta_one_half_constant_coefficients(shape, world, ops):
+    test_bound_admits_the_decomposition_constant_coefficients(shape, world, ops)
 
 
 @pytest.mark.parametrize("case,world", VAR, ids=lambda v: vr.case_key(v) if isinstance(v, tuple) else f"w{v}")
-def test_bound_admits_the_decomposition_per_node_rows(case, world):
-    cs, r = vr.case(case), vr.plain_reference(case)
+def test_bound_admits_the_decomposition_per_node_rows(case, world, ops="cn"):
+    cs, r = vr.case(case), vr.plain_reference(case, ops)
     plane = cs.shape[0] * cs.shape[1]
     before = np.concatenate([[0], np.cumsum(cs.tissue)])  # tissue nodes in front of a node
     bounds = [0] + [int(before[int(z) * plane]) for z in np.cumsum(ref.slab_counts(cs.shape[2], world))]
     assert bounds[-1] == cs.n
-    slab_ordered_run_passes("var", f"{vr.case_key(case)}/w{world}", cs.problem, r, bounds, vr.field(cs), vr.cuts_of(cs, vr.CUTS_SHORT))
+    slab_ordered_run_passes("var", f"{vr.opset_key(case, ops)}/w{world}", vr.problem_of(case, ops), r, bounds, vr.field(cs), vr.cuts_of(cs, vr.CUTS_SHORT))
+
+
+@pytest.mark.parametrize("case,world,ops", VAR_SETS, ids=lambda v: v if isinstance(v, str) else vr.case_key(v) if isinstance(v, tuple) else f"w{v}")
+def test_bound_admits_the_decomposition_off_theta_one_half_per_node_rows(case, world, ops):
+    test_bound_admits_the_decomposition_per_node_rows(case, world, ops)

@@ -78,6 +78,22 @@ flag changed), and, once per build, the thread tests of tests/test_distributed_g
       two ranks that hold it breaks the recurrence for good.
 So slips 1 to 3 are too coarse to pass the thread tests either; what those let through is an error of the size of slip 4 in a
 dot product, which costs an iteration at most and leaves the converged x alone.
+
+Off theta = 1/2 (ref.DIST_OPSET_CASES on loops R, M, T in child rr2, vr.DIST_OPSET_CASES on F, Q, S, the guess sequences of
+DIST_OPSET_GUESS at skew, keys case@set; tests/test_rr_iterates_gpu.py says why, and holds the record of the builds with a deliberate
+slip), and handles re-timed on every rank while their guess history is full (retime_solves of the child: cn, skew, cn; loop R, and
+each per-node route -- on F beat_pde_set_timestep invalidates the neighbours' centre coefficients, which the next solve exchanges
+again).  The 45 000-node guess case of vr.DIST_GUESS_CASES is not run off cn: a few thousand nodes tell the factors apart.
+Measured on an MI355X, same run (the child's time without the new cases is the earlier commit's child):
+
+    child   solves more   seconds, of the child's   worst err / yardstick: be, skew, re-timed             worst norm / yardstick
+    rr2        192          1.78 of 7.55            R 1.28, 1.71, 1.58;  M 1.28, 1.58;  T 1.15, 1.57         0.21, 0.18, 0.16
+    varF        52          0.64 of 7.12            0.95, 1.77, 1.79                                        0.08, 0.14, 0.14
+    varQ        32          0.45 of 5.93            0.95, 1.77, 1.79                                        0.08, 0.14, 0.14
+    varS        52          0.52 of 6.77            0.95, 1.77, 1.79                                        0.08, 0.14, 0.14
+
+rr4 is unchanged (3.4 s).  Under cn every loop reports what it did before.  The module: 40.4 s (36.6 s for the earlier commit's, same
+session).  What it found: nothing.
 """
 import os
 import subprocess
@@ -269,9 +285,10 @@ def check_const(data, child):
     ry = int(CHILDREN[child]["BEAT_RR_RY"])
     routes, figures = [], {}
     cases = const_cases(child)
-    for shape, world in cases:
+    off_cn = [(shape, world, name) for (shape, world), sets in ref.DIST_OPSET_CASES.items() for name in sets] if child == "rr2" else []
+    for shape, world, name in [(s, w, "cn") for s, w in cases] + off_cn:
         for loop in CONST_LOOPS[child]:
-            base = f"{ref.shape_key(shape)}/w{world}/{loop}"
+            base = f"{ref.case_key(shape, name)}/w{world}/{loop}"
             want, merged = expected_const(loop, ry)
             for rank in range(world):
                 got = dict(zip(ROUTE_KEYS, (int(v) for v in data[f"{base}|rr_route"][rank])))
@@ -281,6 +298,14 @@ def check_const(data, child):
                     routes.append(f"{base} rank {rank}: tile route {data[f'{base}|tile'][rank]} on constant coefficients")
                 if int(data[f"{base}|merged"][rank][0]) != (int(data[f"{base}|nsolves"][rank]) if merged else 0):
                     routes.append(f"{base} rank {rank}: {int(data[f'{base}|merged'][rank][0])} single-reduction solves of {int(data[f'{base}|nsolves'][rank])}")
+    if off_cn:
+        shape, world = next(iter(ref.DIST_OPSET_CASES))
+        for tag in ("live0", "live1", "live2", "fresh"):
+            key = f"{ref.shape_key(shape)}/w{world}/R/retime/{tag}"
+            for rank in range(world):
+                got = dict(zip(ROUTE_KEYS, (int(v) for v in data[f"{key}|rr"][rank])))
+                if tuple(got[k] for k in ("available", "ry", "pd", "by_rows_mask", "guess_ry")) != expected_const("R", ry)[0] or tuple(data[f"{key}|tile"][rank]) != (0, 0):
+                    routes.append(f"{key} rank {rank}: beat_pde_rr_route {got}, tile route {data[f'{key}|tile'][rank]}")
     if routes:
         return routes, [], figures
     c = Check(data)
@@ -294,19 +319,57 @@ def check_const(data, child):
             if loop in "RM" and (shape, world) in ref.DIST_GUESS_CASES:
                 check_guess(c, data, base, ref.problem(shape), lambda j, s=shape: ref.field(s, j))
         figures[loop] = (c.worst, c.worst_norm)
+    for name in ref.NEW_SETS if off_cn else ():
+        for loop in CONST_LOOPS[child]:
+            c.worst, c.worst_norm = (0.0, None), (0.0, None)
+            for shape, world, _ in [t for t in off_cn if t[2] == name]:
+                base = f"{ref.case_key(shape, name)}/w{world}/{loop}"
+                check_solves(c, data, base, ref.plain_reference(shape, name), ref.CUTS)
+                check_ghost_planes(c, data, base, shape, world)
+                if loop in "RM" and name in ref.DIST_OPSET_GUESS.get((shape, world), ()):
+                    check_guess(c, data, base, ref.problem(shape, name), lambda j, s=shape: ref.field(s, j))
+            figures[f"{name}/{loop}"] = (c.worst, c.worst_norm)
+    if off_cn:
+        shape, world = next(iter(ref.DIST_OPSET_CASES))
+        c.worst, c.worst_norm = (0.0, None), (0.0, None)
+        check_retime(c, data, f"{ref.shape_key(shape)}/w{world}/R", lambda name, s=shape: ref.plain_reference(s, name), ref.CUTS)
+        figures["retime"] = (c.worst, c.worst_norm)
+        figures["off theta = 1/2: seconds, solves"] = (float(data["opsets_seconds"]), sum(k.endswith("|x") and ("@" in k or "/retime/" in k) for k in data))
     return [], c.failures, figures
+
+
+def check_retime(c, data, base, reference_of, cuts):
+    """The re-timed handles of one world (retime_solves of the child): the first cut of every stage from x0 = v_ -- the plain
+    reference's iterate: the history was dropped --, re-timed to skew a handle created under skew bit for bit, and back under cn what
+    the handles gave before; every rank's record alike."""
+    for stage, name in enumerate(ref.RETIME):
+        c.cut(f"{base}/retime/live{stage}/k={cuts[0]}", reference_of(name), cuts[0])
+    c.cut(f"{base}/retime/fresh/k={cuts[0]}", reference_of(ref.RETIME[1]), cuts[0])
+    for k in cuts:
+        for mine, other in ((f"{base}/retime/live1/k={k}", f"{base}/retime/fresh/k={k}"), (f"{base}/retime/live2/k={k}", f"{base}/retime/live0/k={k}")):
+            c.same_bits(other, mine, True)
+            c.that(data[f"{mine}|recs"].tobytes() == data[f"{other}|recs"].tobytes(), mine, f"records {data[f'{mine}|recs'].tolist()}, {other} {data[f'{other}|recs'].tolist()}")
+            same_records(c, data, mine)
+        c.that(not np.array_equal(data[f"{base}/retime/live0/k={k}|x"], data[f"{base}/retime/live1/k={k}|x"]), f"{base}/retime/live1/k={k}", "the re-timing changed nothing")
 
 
 def check_var(data, var_routes=VAR_ROUTES):
     """(route failures, value failures, figures per route) of the per-node children of the routes given."""
     routes, figures = [], {}
     cases = var_cases()
-    for case, world in cases:
+    off_cn = [(case, world, name) for (case, world), sets in vr.DIST_OPSET_CASES.items() for name in sets]
+    off_cn_guess = [(case, world, name) for (case, world), sets in vr.DIST_OPSET_GUESS.items() for name in sets]
+    retime_case, retime_world = next(iter(vr.DIST_OPSET_CASES))
+    for case, world, name in [(c, w, "cn") for c, w in cases] + off_cn:
         cs = vr.case(case)
         for route in var_routes:
-            base = f"{vr.case_key(case)}/w{world}/{route}"
+            base = f"{vr.opset_key(case, name)}/w{world}/{route}"
             want = expected_var(cs, world, route)
-            keys = [f"{base}|tile"] + ([f"{base}/e/order={o}|tile" for o in ref.GUESS_ORDERS] if route in "FS" and (case, world) in vr.DIST_GUESS_CASES else [])
+            keys = [f"{base}|tile"] + ([f"{base}/e/order={o}|tile" for o in ref.GUESS_ORDERS] if name == "cn" and route in "FS" and (case, world) in vr.DIST_GUESS_CASES else [])
+            if name == "cn" and (case, world) == (retime_case, retime_world):
+                keys += [f"{base}/retime/{tag}|tile" for tag in ("live0", "live1", "live2", "fresh")]
+            if name == "cn" and route in "FS":
+                keys += [f"{vr.opset_key(case, g)}/w{world}/{route}/e/order={o}|tile" for c2, w2, g in off_cn_guess if (c2, w2) == (case, world) for o in ref.GUESS_ORDERS]
             for key in keys:
                 got = [tuple(int(v) for v in row) for row in data[key]]
                 if got != want:
@@ -330,6 +393,23 @@ def check_var(data, var_routes=VAR_ROUTES):
             if route in "FS" and (case, world) in vr.DIST_GUESS_CASES:
                 check_guess(c, data, base, cs.problem, lambda j, s=cs: vr.field(s, j))
         figures[route] = (c.worst, c.worst_norm)
+    for route in var_routes:
+        for name in ref.NEW_SETS:
+            c.worst, c.worst_norm = (0.0, None), (0.0, None)
+            for case, world, _ in [t for t in off_cn if t[2] == name]:
+                cs = vr.case(case)
+                base = f"{vr.opset_key(case, name)}/w{world}/{route}"
+                check_solves(c, data, base, vr.plain_reference(case, name), vr.cuts_of(cs, vr.CUTS_SHORT))
+                check_ghost_planes(c, data, base, cs.shape, world, coupled=coupled_nodes(cs))
+            for case, world, _ in [t for t in off_cn_guess if t[2] == name and route in "FS"]:
+                cs = vr.case(case)
+                check_guess(c, data, f"{vr.opset_key(case, name)}/w{world}/{route}", vr.problem_of(case, name), lambda j, s=cs: vr.field(s, j))
+            figures[f"{name}/{route}"] = (c.worst, c.worst_norm)
+        c.worst, c.worst_norm = (0.0, None), (0.0, None)
+        cs = vr.case(retime_case)
+        check_retime(c, data, f"{vr.case_key(retime_case)}/w{retime_world}/{route}", lambda name: vr.plain_reference(retime_case, name), vr.cuts_of(cs, vr.CUTS_SHORT))
+        figures[f"retime/{route}"] = (c.worst, c.worst_norm)
+    figures["off theta = 1/2: seconds, solves"] = (float(data["opsets_seconds"]), sum(k.endswith("|x") and ("@" in k or "/retime/" in k) for k in data))
     return [], c.failures, figures
 
 

@@ -306,8 +306,13 @@ def _make_pde(ctx, cells, L, Mk, z_lo_phys=1, z_hi_phys=1):
     return handle, nn, mt, kt
 
 
+# (C_m, theta, dt) of the diffusion operator: Crank-Nicolson, backward Euler, and a set in which C_m, theta dt, (1 - theta) dt and dt
+# are four different numbers (tests/_pcg_ref.py says what each is for).  At theta = 1/2 A and B have the same factor of K.
+OPSETS = {"cn": (0.01, 0.5, 0.05), "be": (0.01, 1.0, 0.05), "skew": (0.013, 0.25, 0.08)}
+
+
 @pytest.mark.parametrize("cells,L,Mk", GRIDS)
-def test_stencil_operators_match_assembled_matrices(hip_ctx, cells, L, Mk):
+def test_stencil_operators_match_assembled_matrices(hip_ctx, cells, L, Mk, opset="cn"):
     """y = Mass x, K x, A x, B x from the LDS-tiled stencil vs the oracle's literally assembled
     sparse matrices: <= 1e-13 relative to ||row||_1 * max|x| (15-term fp64 sums)."""
     from beat import _hip
@@ -320,7 +325,7 @@ def test_stencil_operators_match_assembled_matrices(hip_ctx, cells, L, Mk):
     handle, nn, _, _ = _make_pde(ctx, cells, L, Mk)
     Mass = fem.assemble_mass(mesh)
     K = fem.assemble_stiffness(mesh, _conductivity(Mk, dim))
-    C_m, theta, dt = 0.01, 0.5, 0.05
+    C_m, theta, dt = OPSETS[opset]
     _hip.check(ctx.lib.beat_pde_set_timestep(handle, C_m, theta, dt))
     mats = {0: C_m * Mass + theta * dt * K, 1: C_m * Mass - (1 - theta) * dt * K, 2: Mass, 3: K}
     n = mesh.num_nodes
@@ -339,6 +344,13 @@ def test_stencil_operators_match_assembled_matrices(hip_ctx, cells, L, Mk):
         scale = (abs(mat) @ np.ones(n)).max() * np.abs(x).max()
         assert np.abs(fy.numpy() - ref).max() <= 1e-13 * scale, which
     _hip.check(ctx.lib.beat_pde_destroy(handle))
+
+
+@pytest.mark.parametrize("opset", ("be", "skew"))
+@pytest.mark.parametrize("cells,L,Mk", GRIDS)
+def test_stencil_operators_match_assembled_matrices_off_theta_one_half(hip_ctx, cells, L, Mk, opset):
+    """The test above with A and B two different matrices."""
+    test_stencil_operators_match_assembled_matrices(hip_ctx, cells, L, Mk, opset)
 
 
 def test_stencil_slab_ghost_planes(hip_ctx):
@@ -382,7 +394,7 @@ def test_stencil_slab_ghost_planes(hip_ctx):
 
 
 @pytest.mark.parametrize("cells,L,Mk", GRIDS[:2] + GRIDS[3:])  # (all but the 5 x 2 x 3-node grid)
-def test_pde_solve_matches_direct_solve(hip_ctx, cells, L, Mk):
+def test_pde_solve_matches_direct_solve(hip_ctx, cells, L, Mk, opset="cn"):
     """One theta-step: rhs build + Jacobi-PCG (rtol 1e-12) vs the oracle's sparse-LU solve of
     (C_m Mass + theta dt K) v = (C_m Mass - (1-theta) dt K) v_ + dt b_stim: <= 1e-9 * max|v|."""
     from beat import _hip
@@ -393,7 +405,7 @@ def test_pde_solve_matches_direct_solve(hip_ctx, cells, L, Mk):
     dim = len(cells)
     mesh = fem.BoxMesh(cells, L)
     Mten = _conductivity(Mk, dim)
-    C_m, theta, dt = 0.01, 0.5, 0.05
+    C_m, theta, dt = OPSETS[opset]
     if Mk == "aniso2" or Mk == 1.0:
         C_m, dt = 1.0, 1e-3
     handle, nn, _, _ = _make_pde(ctx, cells, L, Mk)
@@ -426,6 +438,13 @@ def test_pde_solve_matches_direct_solve(hip_ctx, cells, L, Mk):
     _, its, _ = fem.pcg_jacobi(A, model.rhs(theta * dt, dt), v_prev, rtol=1e-12)
     assert abs(its - info.iterations) <= 1
     _hip.check(ctx.lib.beat_pde_destroy(handle))
+
+
+@pytest.mark.parametrize("opset", ("be", "skew"))
+@pytest.mark.parametrize("cells,L,Mk", GRIDS[:2] + GRIDS[3:])
+def test_pde_solve_matches_direct_solve_off_theta_one_half(hip_ctx, cells, L, Mk, opset):
+    """The test above with theta = 1 and theta = 1/4: the right-hand side's factor of K is not the matrix's."""
+    test_pde_solve_matches_direct_solve(hip_ctx, cells, L, Mk, opset)
 
 
 def test_pde_solve_zero_rhs_and_latch(hip_ctx):

@@ -11,6 +11,15 @@ from oracle import fem
 
 SHAPES = ref.all_shapes()  # the register-row cases, then what the one-launch cases add
 GUESS_SHAPES = list(ref.GUESS_SHAPES) + [s for s in ref.SMALL_GUESS_SHAPES if s not in ref.GUESS_SHAPES]
+# (shape, set): every shape under cn, as before the sets had names (and under the same test ids), then the pairs off theta = 1/2
+PAIRS = [(s, "cn") for s in SHAPES] + ref.opset_pairs()
+GUESS_PAIRS = [(s, "cn") for s in GUESS_SHAPES] + [(s, name) for s in ref.OPSET_GUESS_SHAPES + ref.SMALL_OPSET_GUESS_SHAPES for name in ref.NEW_SETS] + \
+    [(s, name) for (s, _), sets in ref.DIST_OPSET_GUESS.items() for name in sets]
+GUESS_PAIRS = list(dict.fromkeys(GUESS_PAIRS))
+
+
+def pair_id(pair) -> str:
+    return ref.case_key(*pair)
 
 
 def test_longdouble_has_a_64_bit_mantissa():
@@ -24,6 +33,22 @@ def test_case_table_is_consistent():
     assert len(SHAPES) == len(set(SHAPES)) == len(set(ref.SHAPES) | set(ref.SMALL_SHAPES))
     assert len({ref.seed_of(s) for s in SHAPES}) == len(SHAPES)
     assert max(int(np.prod(s)) for s in SHAPES) <= 8192  # a few thousand nodes: where the index arithmetic branches, not the workload
+    # the sets: cn is the operator of every case from before the sets had names; skew tells every factor from every other
+    assert ref.OPSETS["cn"].triple == (0.01, 0.5, 0.05) == (ref.C_M, ref.THETA, ref.DT) and ref.OPSETS["be"].triple == (0.01, 1.0, 0.05)
+    assert ref.OPSETS["skew"].triple == (0.013, 0.25, 0.08) and all(o.name == name for name, o in ref.OPSETS.items())
+    be, skew = ref.OPSETS["be"], ref.OPSETS["skew"]
+    assert (1 - be.theta) * be.dt == 0.0 and be.theta * be.dt == be.dt
+    assert len({skew.c_m, skew.theta * skew.dt, (1 - skew.theta) * skew.dt, skew.dt, skew.theta, 1 - skew.theta}) == 6
+    assert set(ref.OPSET_SHAPES) <= set(ref.SHAPES) and set(ref.OPSET_GUESS_SHAPES) <= set(ref.OPSET_SHAPES) & set(ref.GUESS_SHAPES)
+    assert set(ref.SMALL_OPSET_SHAPES) <= set(ref.SMALL_SHAPES) and set(ref.SMALL_OPSET_GUESS_SHAPES) <= set(ref.SMALL_OPSET_SHAPES) & set(ref.SMALL_GUESS_SHAPES)
+    assert sorted(s for s in ref.SMALL_OPSET_SHAPES if not ref.small_takes(s)) == [(1, 5, 4)]  # the fallback under the one-launch solve
+    assert all(s in ref.DIST_CASES and w in ref.DIST_CASES[s] for s, w in ref.DIST_OPSET_CASES) and set(ref.DIST_OPSET_GUESS) <= set(ref.DIST_GUESS_CASES)
+    for table in (ref.OPSET_SHAPES, ref.SMALL_OPSET_SHAPES, ref.DIST_OPSET_CASES):
+        assert all(set(sets) <= set(ref.NEW_SETS) and "be" in sets for sets in table.values())
+        assert all("skew" in sets or ref.dim_of(k if len(k) == 3 else k[0]) == 1 for k, sets in table.items())  # 1-D rows take be only
+    assert ref.RETIME == ("cn", "skew", "cn")
+    assert len(PAIRS) == len(set(PAIRS)) and max(int(np.prod(s)) for s, _ in PAIRS) <= 8192
+    assert ref.problem((65, 3, 5), "be").mass is ref.problem((65, 3, 5)).mass and ref.problem((65, 3, 5), "be").ops == be
     for s in SHAPES:
         v = ref.field(s)
         assert abs(v.mean()) < 1e-12 and 0.1 < np.abs(v).max() < 10.0
@@ -118,13 +143,20 @@ def test_expanded_tables_are_the_assembled_matrices(shape):
     assert (p.A != p.A.T).nnz == 0 or abs(p.A - p.A.T).max() <= 8 * 2.0**-53 * abs(p.A).max()
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=ref.shape_key)
-def test_reference_is_right_and_no_stop_is_a_near_tie(shape):
-    p, r = ref.problem(shape), ref.plain_reference(shape)
+@pytest.mark.parametrize("pair", PAIRS, ids=pair_id)
+def test_reference_is_right_and_no_stop_is_a_near_tie(pair):
+    shape, ops = pair[0], ref.opset(pair[1])
+    p, r = ref.problem(shape, ops), ref.plain_reference(shape, ops)
+    assert p.ops == ops
     v = ref.field(shape)
     bL = ref.rhs_longdouble(p, v)
-    # the right-hand side: the float64 form of the same expression
-    b64 = ref.C_M * (p.mass @ v) - (1 - ref.THETA) * ref.DT * (p.stiff @ v) + ref.DT * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights))
+    # the right-hand side: the float64 form of the same expression, the set's numbers written where they belong
+    C_m, theta, dt = ops.triple
+    b64 = C_m * (p.mass @ v) - (1 - theta) * dt * (p.stiff @ v) + dt * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights))
+    assert np.array_equal(b64, p.rhs_float64(v))
+    assert abs(p.A - (C_m * p.mass + theta * dt * p.stiff)).max() <= 2 * 2.0**-53 * abs(p.A).max()
+    if ops.name == "be":  # B = C_m Mass: K has no part in b
+        assert np.array_equal(b64, C_m * (p.mass @ v) + dt * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights)))
     assert np.abs(bL.astype(np.float64) - b64).max() <= 16 * 2.0**-53 * np.abs(b64).max()
     assert float(r.bL) == pytest.approx(np.linalg.norm(b64), rel=1e-14)
     # converged: the direct solve
@@ -155,11 +187,12 @@ def test_reference_is_right_and_no_stop_is_a_near_tie(shape):
     assert r.rhs_norm_bound() > 0.0
 
 
-@pytest.mark.parametrize("shape", GUESS_SHAPES, ids=ref.shape_key)
-def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(shape):
+@pytest.mark.parametrize("pair", GUESS_PAIRS, ids=pair_id)
+def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(pair):
     """The fields of the guess cases with exact increments in place of the device's: the extrapolated start is still O(1) wrong, so
     the cut iterates (k = 1, 3) are far from converged."""
-    p = ref.problem(shape)
+    shape = pair[0]
+    p = ref.problem(*pair)
     solve = spla.factorized(p.A.tocsc())
     incs = []
     for j in range(1, ref.GUESS_SOLVES + 1):
@@ -186,7 +219,7 @@ def test_single_reduction_recurrence_gives_the_same_iterates():
     v = ref.field(shape).astype(L)
     b = ref.rhs_longdouble(p, ref.field(shape))
     A = p.operator(L)
-    dinv = L(1) / (L(ref.C_M) * p.mass.diagonal().astype(L) + L(ref.THETA) * L(ref.DT) * p.stiff.diagonal().astype(L))
+    dinv = L(1) / p.diagonal(L)
     x, res = v.copy(), b - ref.matvec(A, v, L)
     pdir, alpha, g_old = np.zeros_like(x), L(0), L(0)
     for k in range(1, 9):

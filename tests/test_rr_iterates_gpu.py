@@ -35,6 +35,50 @@ The worst cases: 65 x 3 x 5 at the stop of rtol 1e-6 (RY = 2), 64 x 4 x 3 at k =
 yardstick (1 x 1 x 7, single-reduction loop, k = 1).  Chunk lengths run: 130 x 6 x 9: 1, 2, 3, 5, 9; 129 x 7 x 6: 1, 2, 3, 6;
 63 x 5 x 4: 1, 2, 4; 1 x 1 x 7: 1, 2, 3, 4, 7 -- chunks of one plane stay below the limit on block partials at these sizes, so no
 operator declined the register-row loop.  The right-hand side with a guess reported 2 rows per wave in every configuration.
+
+Off theta = 1/2 (ref.OPSET_SHAPES under be and skew, keys shape@set; the children of (RY 2, PD 1) and (RY 4, PD 1) without
+BEAT_RR_BY_ROWS): at (C_m, theta, dt) = (0.01, 0.5, 0.05), the operator of every case above, A and B have the same factor of K,
+and a theta written for 1 - theta, theta dt for dt or a ||b|| formed with the wrong factor passes all of it.  Loops (a) - (d),
+both stops and the guess sequences as above, plus a handle re-timed while its guess history is full (run_retime of the child:
+cn, skew, cn): the cuts behind set_timestep equal those of a handle created under the set bit for bit, records included, and
+their first iterate is the plain reference's.  Measured on an MI355X, same run, same machine (250 solves more per child; the
+child's time without them is the earlier commit's child):
+
+    child          set      solves   worst err / yardstick                     worst norm / yardstick    seconds, of the child's
+    RY 2, PD 1     be        128     1.49  (65 x 3 x 5, guess order 1, k = 1)   0.35  (64 x 1 x 1, k = 1)
+                   skew      106     2.24  (257 x 5 x 1, k = 1)                 0.22  (65 x 3 x 5, k = 1)
+                   re-timed   16     1.58  (skew, k = 1)                        0.22                      0.09 of 5.34 (first child)
+    RY 4, PD 1     be        128     1.50  (129 x 7 x 6, guess order 1, k = 1)  0.35  (64 x 1 x 1, k = 1)
+                   skew      106     1.63  (257 x 5 x 1, k = 1)                 0.21  (129 x 7 x 6, guess order 3, k = 3)
+                   re-timed   16     1.12  (skew, k = 1)                        0.11                      0.09 of 2.72
+
+Under cn both children report what they did before: 1.99 / 2.40 and 0.46.  The tests take 9.2 s and 6.3 s with the host's
+references (the first took 5.5 and 6.2 s at the earlier commit in two runs of the same session): the device's share of the new cases is 0.1 s, the
+rest their longdouble references.  What it found: nothing -- the library is right off theta = 1/2.
+
+The same cases against builds of the library with one arithmetic slip each (a wrong number only; no address, bound, barrier,
+exchange or flag changed), and the modules of the commit before these cases (the four iterate modules, tests/test_gpu_kernels.py,
+tests/test_var_gpu.py, tests/test_guess_gpu.py; for slip 1 tests/test_distributed_gpu.py as well) against the same builds:
+  1 theta for 1 - theta in h_B of upload_tables (csrc/beat_pde.hip) -- the table of B is read by beat_pde_apply(which = 1), by the
+      one-launch kernel and by the register-row right-hand side WITH a guess.  Fail: every one-launch pair of
+      tests/test_small_iterates_gpu.py (41 x 15 x 7 at be: iterate 1 off by 2.1, at skew by 3.0) and its re-timed handle; the guess
+      sequences of the register-row children (65 x 3 x 5 at be, order 1: iterate 1 off by 3.4, rhs_norm by 55 %) and of loops R and M
+      on slabs at skew (4.8, 5.1); 24 + 16 cases of tests/test_gpu_kernels.py.  Pass: the plain solves of the register-row kernels,
+      loop T, the per-node rows.  The earlier modules: all pass (76 + 163 + 42 + 22 tests and the four iterate modules);
+  2 tdt for omt_dt in the rows of B in var_form_A_kernel (csrc/beat_pde_var.hip) -- read by the right-hand side on 8-row tiles
+      of a single slab.  Fail: 63 x 16 x 6 full and cutshell at both sets on the default route and under BEAT_VTL_PDOT=0 (full at be:
+      iterate 1 off by 2.3, at skew by 3.9, the stop of rtol 1e-9 one iteration early) and their re-timed handles;
+      test_per_node_theta_step_matches_direct_solve at both sets.  Pass: BEAT_VTL=0, 62 x 9 x 5 (the gather kernel forms b), and the
+      slabs of tests/test_dist_iterates_gpu.py on F, Q and S (a slab with a live face takes the split right-hand side, which does
+      not read those rows).  The earlier modules: the iterate modules pass; test_expand_layer_and_surface_stimulus_on_voxel_shell
+      of tests/test_var_gpu.py FAILS (its Laplace solve sets (0, 1, 1): u off by 1.0) -- this slip was caught before, by a
+      converged solution at theta = 1;
+  3 omt_dt taken as theta dt in beat_rr_launch of csrc/beat_pde_rr.hip, where the kernel without a guess uses it for ||b|| only.
+      Every iterate and residual_norm of every cut passes; rhs_norm fails in every plain solve on the register-row kernels (65 x 3 x 5
+      at be: 1.97e-4 for 1.47e-4), in loops (a) - (d), R and M, on the multi-launch route of tests/test_small_iterates_gpu.py and
+      behind the re-timing; 129 x 7 x 6 and 130 x 6 x 9 at be stop one iteration early (12 for 13 at rtol 1e-6), 64 x 32 x 1 at skew
+      one late (9 for 8): nothing else moves, and only off theta = 1/2.  Solves with a guess, loop T and the
+      one-launch kernel pass.  The earlier modules: all pass.
 """
 import os
 import subprocess
@@ -127,11 +171,73 @@ def check_results(npz_path, ry, pd, mask):
                     c.that(all(c.rec(f"{key}/solve={j}")[1] > 0 for j in range(1, ref.GUESS_SOLVES + 1)), key, "a solve in front of the cut did not converge")
                     x0 = v.astype(np.longdouble) + ref.guess_increment(order, incs)
                     c.cut(key, ref.reference(p, bL, x0, k), k)
+    cn_worst, cn_worst_norm = c.worst, c.worst_norm
+    off_cn = {}
+    c.that(bool(data["opsets"]) == (pd == 1 and mask is None), "opsets", f"the cases off theta = 1/2 {'ran' if data['opsets'] else 'did not run'}")
+    if pd == 1 and mask is None and bool(data["opsets"]):
+        off_cn = check_opsets(c, data, routes)
+        off_cn["seconds"] = float(data["opsets_seconds"])
+    c.worst, c.worst_norm = cn_worst, cn_worst_norm
     figures = {"worst err/max(delta_k, floor)": c.worst, "worst norm err/bound*16": c.worst_norm, "child seconds": float(data["seconds"]),
+               "off theta = 1/2": off_cn,
                "solves": sum(k.endswith("|x") for k in data), "route 130x6x9 one chunk": routes.get("130x6x9/zc=9/a"),
                "route 3x70x2": routes.get("3x70x2/default/a"),
                "chunk lengths": {ref.shape_key(s): sorted({routes[k]["zc"] for k in routes if k.startswith(ref.shape_key(s) + "/zc=")}) for s in ref.CHUNK_SHAPES}}
     return c.failures, figures
+
+
+def check_opsets(c, data, routes):
+    """The pairs of ref.OPSET_SHAPES (keys shape@set) with the checks of the cn cases, and the re-timed handle; per set (solves, worst
+    err / yardstick, worst norm / yardstick)."""
+    figures = {}
+    for name in ref.NEW_SETS:
+        c.worst, c.worst_norm = (0.0, None), (0.0, None)
+        for shape, sets in ref.OPSET_SHAPES.items():
+            if name not in sets:
+                continue
+            ck = ref.case_key(shape, name)
+            r = ref.plain_reference(shape, name)
+            for loop in "abcd":
+                base = f"{ck}/default/{loop}"
+                c.that(base in routes, base, "no route report")
+                for k in ref.CUTS:
+                    c.cut(f"{base}/k={k}", r, k)
+                if loop != "b":
+                    for rtol in ref.RTOLS:
+                        c.uncut(f"{base}/rtol={rtol:g}", r, rtol)
+            for tail in [f"k={k}" for k in ref.CUTS]:
+                c.same_bits(f"{ck}/default/a/{tail}", f"{ck}/default/b/{tail}", True)
+            for tail in [f"k={k}" for k in ref.CUTS] + [f"rtol={rtol:g}" for rtol in ref.RTOLS]:
+                c.same_bits(f"{ck}/default/a/{tail}", f"{ck}/default/c/{tail}", False)
+            if shape in ref.OPSET_GUESS_SHAPES:
+                p = ref.problem(shape, name)
+                v = ref.field(shape, ref.GUESS_SOLVES + 1)
+                bL = ref.rhs_longdouble(p, v)
+                for order in ref.GUESS_ORDERS:
+                    for k in ref.GUESS_CUTS:
+                        key = f"{ck}/default/e/order={order}/k={k}"
+                        incs = [data[f"{key}/solve={j}|x"] - ref.field(shape, j) for j in range(ref.GUESS_SOLVES, 0, -1)]
+                        c.that(all(c.rec(f"{key}/solve={j}")[1] > 0 for j in range(1, ref.GUESS_SOLVES + 1)), key, "a solve in front of the cut did not converge")
+                        c.cut(key, ref.reference(p, bL, v.astype(np.longdouble) + ref.guess_increment(order, incs), k), k)
+        figures[name] = (sum(k.endswith("|x") and f"@{name}/" in k for k in data), c.worst, c.worst_norm)
+    # the re-timed handle: first cut of every stage from x0 = v_ (the history was dropped), the stages equal fresh handles bit for bit
+    c.worst, c.worst_norm = (0.0, None), (0.0, None)
+    shape = next(iter(ref.OPSET_SHAPES))
+    base = f"{ref.shape_key(shape)}/retime"
+    for stage, name in enumerate(ref.RETIME):
+        c.that(f"{base}/live{stage}" in routes, f"{base}/live{stage}", "no route report")
+        c.cut(f"{base}/live{stage}/k={ref.CUTS[0]}", ref.plain_reference(shape, name), ref.CUTS[0])
+    c.cut(f"{base}/fresh/k={ref.CUTS[0]}", ref.plain_reference(shape, ref.RETIME[1]), ref.CUTS[0])
+    for k in ref.CUTS:
+        c.same_bits(f"{base}/fresh/k={k}", f"{base}/live1/k={k}", True)   # re-timed to skew: a handle created under skew
+        c.same_bits(f"{base}/live0/k={k}", f"{base}/live2/k={k}", True)   # and back: what the handle gave before
+        for stage in (1, 2):
+            other = "fresh" if stage == 1 else "live0"
+            c.that(data[f"{base}/live{stage}/k={k}|rec"].tobytes() == data[f"{base}/{other}/k={k}|rec"].tobytes(), f"{base}/live{stage}/k={k}",
+                   f"record {data[f'{base}/live{stage}/k={k}|rec'].tolist()}, {other} {data[f'{base}/{other}/k={k}|rec'].tolist()}")
+        c.that(not np.array_equal(data[f"{base}/live0/k={k}|x"], data[f"{base}/live1/k={k}|x"]), f"{base}/live1/k={k}", "the re-timing changed nothing")
+    figures["retime"] = (sum(k.endswith("|x") and "/retime/" in k for k in data), c.worst, c.worst_norm)
+    return figures
 
 
 @pytest.mark.parametrize("ry,pd,mask", CONFIGS, ids=[f"ry{ry}-pd{pd}" + (f"-rows{mask}" if mask else "") for ry, pd, mask in CONFIGS])

@@ -38,6 +38,17 @@ Per instance, one-launch: <2> 2.15, <4> 1.82, <6> 1.46, <8> 1.75, <10> 1.80, <12
 The same test against builds with one deliberate slip each in the kernel: the last node counted twice in p.Ap -- the 13 one-launch
 boxes fail (128 x 2 x 2: iterate 1 off by 8e-3); node 0 counted twice in r.r -- the same 13 fail (residual_norm); e not added to
 the start at the last node -- the four guess boxes fail, nothing else.
+
+Off theta = 1/2 (ref.SMALL_OPSET_SHAPES under be and skew; tests/test_rr_iterates_gpu.py says why, and holds the record of the
+builds with a deliberate slip): the kernel forms b, ||b|| and A from its own LDS copies of tables A and B.  Measured on an MI355X
+(worst err / yardstick, worst norm / yardstick; one-launch | multi-launch):
+
+    41 x 15 x 7 <10>    be    1.74, 0.28 | 1.53, 0.19    skew  2.05, 0.22 | 1.90, 0.19     56 solves each, 22 - 25 ms
+    64 x 32 x 1 <4>     be    1.96, 0.16 | 1.27, 0.14    skew  1.67, 0.28 | 1.53, 0.12     56 solves each, 17 - 24 ms
+    1 x 5 x 4 declined  be    1.22, 0.16 on both         skew  2.36, 0.09 on both          16 solves each, 4 ms
+    re-timed handle (cn, skew, cn) on 41 x 15 x 7: 2.05, 0.22 one-launch; 1.85, 0.12 multi-launch
+
+The module: 4.0 s with the 8 new tests, 3.5 s for the 18 before them, same session.  What it found: nothing.
 """
 import time
 
@@ -54,7 +65,7 @@ MAX_IT = 500
 IN_PLACE = ("k=3", "rtol=1e-09")
 
 
-def make_ops(ctx, shape, small, order=0):
+def make_ops(ctx, shape, small, order=0, opset="cn"):
     from beat._engine import HipOps
 
     mt, kt = ref.tables(ref.dim_of(shape))  # the numbers the host reference expands into its matrices
@@ -62,7 +73,7 @@ def make_ops(ctx, shape, small, order=0):
     if not small:
         ops.set_small(False)
     ops.set_guess_order(order)
-    ops.set_timestep(ref.C_M, ref.THETA, ref.DT)
+    ops.set_timestep(*ref.opset(opset).triple)
     return ops
 
 
@@ -80,10 +91,10 @@ def record(data, key, res, fx):
     data[f"{key}|rec"] = np.array([res.iterations, res.converged_reason, res.residual_norm, res.rhs_norm], dtype=np.float64)
 
 
-def run_plain(ctx, shape, route, data):
-    ops = make_ops(ctx, shape, route == "one")
+def run_plain(ctx, shape, route, data, opset="cn"):
+    ops = make_ops(ctx, shape, route == "one", opset=opset)
     assert ops.small_active() == (route == "one" and ref.small_takes(shape)), (shape, route, ops.small_active())
-    base = f"{ref.shape_key(shape)}/{route}"
+    base = f"{ref.case_key(shape, opset)}/{route}"
     v = ref.field(shape)
     fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
     fv.set(v)
@@ -101,12 +112,12 @@ def run_plain(ctx, shape, route, data):
     assert ops.pending is None
 
 
-def run_guess(ctx, shape, route, data):
+def run_guess(ctx, shape, route, data, opset="cn"):
     """(e): four converged solves of a field that moves between solves, then a cut solve that starts from their extrapolation."""
     for order in ref.GUESS_ORDERS:
-        ops = make_ops(ctx, shape, route == "one", order=order)
+        ops = make_ops(ctx, shape, route == "one", order=order, opset=opset)
         assert ops.small_active() == (route == "one")
-        key = f"{ref.shape_key(shape)}/{route}/e/order={order}"
+        key = f"{ref.case_key(shape, opset)}/{route}/e/order={order}"
         fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
         for k in ref.GUESS_CUTS:
             ops.guess_reset()
@@ -119,8 +130,8 @@ def run_guess(ctx, shape, route, data):
             record(data, f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx)
 
 
-def check_plain(c, shape, route):
-    base, r = f"{ref.shape_key(shape)}/{route}", ref.plain_reference(shape)
+def check_plain(c, shape, route, opset="cn"):
+    base, r = f"{ref.case_key(shape, opset)}/{route}", ref.plain_reference(shape, opset)
     for k in ref.CUTS:
         c.cut(f"{base}/k={k}", r, k)
     for rtol in ref.RTOLS:
@@ -129,15 +140,15 @@ def check_plain(c, shape, route):
         c.same_bits(f"{base}/{tail}", f"{base}/inplace/{tail}", True)
 
 
-def check_guess(c, shape, route):
+def check_guess(c, shape, route, opset="cn"):
     """As check_results of tests/test_rr_iterates_gpu.py: the device's own earlier, converged solves of the sequence supply the
     increments; they are not what is compared."""
-    p = ref.problem(shape)
+    p = ref.problem(shape, opset)
     v = ref.field(shape, ref.GUESS_SOLVES + 1)
     bL = ref.rhs_longdouble(p, v)
     for order in ref.GUESS_ORDERS:
         for k in ref.GUESS_CUTS:
-            key = f"{ref.shape_key(shape)}/{route}/e/order={order}/k={k}"
+            key = f"{ref.case_key(shape, opset)}/{route}/e/order={order}/k={k}"
             incs = [c.data[f"{key}/solve={j}|x"] - ref.field(shape, j) for j in range(ref.GUESS_SOLVES, 0, -1)]
             c.that(all(c.rec(f"{key}/solve={j}")[1] > 0 for j in range(1, ref.GUESS_SOLVES + 1)), key, "a solve in front of the cut did not converge")
             x0 = v.astype(np.longdouble) + ref.guess_increment(order, incs)
@@ -168,3 +179,81 @@ def test_small_iterates_match_host_pcg(hip_ctx, shape):
           f"{sum(k.endswith('|x') for k in data)} solves in {1e3 * seconds:.1f} ms; err / max(delta_k, floor) and norm err / yardstick: "
           + "; ".join(f"{route} {worst[route][0][0]:.2f} ({worst[route][0][1]}), {worst[route][1][0]:.2f} ({worst[route][1][1]})" for route in worst))
     assert not c.failures, f"{len(c.failures)} failures on {ref.shape_key(shape)}, the first:\n" + "\n".join(c.failures[:40])
+
+
+OFF_CN = [(shape, name) for shape, sets in ref.SMALL_OPSET_SHAPES.items() for name in sets]
+
+
+@pytest.mark.parametrize("pair", OFF_CN, ids=lambda pair: ref.case_key(*pair))
+def test_small_iterates_match_host_pcg_off_theta_one_half(hip_ctx, pair):
+    """The test above on the pairs of ref.SMALL_OPSET_SHAPES: the one-launch kernel forms b, ||b|| and A from its own copies of the
+    two tables, and 1 x 5 x 4, which it declines, runs the multi-launch kernels on both routes."""
+    shape, name = pair
+    data: dict = {}
+    ref.plain_reference(shape, name)  # (not part of the device's time)
+    guess = shape in ref.SMALL_OPSET_GUESS_SHAPES
+    t0 = time.perf_counter()
+    for route in ("one", "multi"):
+        run_plain(hip_ctx, shape, route, data, name)
+        if guess:
+            run_guess(hip_ctx, shape, route, data, name)
+    hip_ctx.synchronize()
+    seconds = time.perf_counter() - t0
+    c = Check(data)
+    worst = {}
+    for route in ("one", "multi"):
+        c.worst, c.worst_norm = (0.0, None), (0.0, None)
+        check_plain(c, shape, route, name)
+        if guess:
+            check_guess(c, shape, route, name)
+        worst[route] = (c.worst, c.worst_norm)
+    print(f"small iterates {ref.case_key(shape, name)}: {'<%d>' % ref.small_instance(shape) if ref.small_takes(shape) else 'declined'}, "
+          f"{sum(k.endswith('|x') for k in data)} solves in {1e3 * seconds:.1f} ms; err / max(delta_k, floor) and norm err / yardstick: "
+          + "; ".join(f"{route} {worst[route][0][0]:.2f} ({worst[route][0][1]}), {worst[route][1][0]:.2f} ({worst[route][1][1]})" for route in worst))
+    assert not c.failures, f"{len(c.failures)} failures on {ref.case_key(shape, name)}, the first:\n" + "\n".join(c.failures[:40])
+
+
+def cut_sequence(ops, data, key, fv, fx, ws):
+    """The cuts one after another with NO guess_reset between them: the first starts from x0 = v_ only if the history is empty."""
+    for k in ref.CUTS:
+        fx.fill(float("nan"))
+        record(data, f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx)
+
+
+@pytest.mark.parametrize("route", ("one", "multi"))
+def test_retimed_handle_equals_a_fresh_one(hip_ctx, route):
+    """beat_pde_set_timestep on a live handle (ref.RETIME: cn, skew, cn) with a guess of order 3 and a full history: the cut sequence
+    behind each re-timing starts from x0 = v_ (its first iterate is the plain reference's), equals that of a handle created under the
+    set bit for bit, and back under cn what the handle gave before."""
+    shape = next(iter(ref.SMALL_OPSET_SHAPES))
+    small = route == "one"
+    data: dict = {}
+    v = ref.field(shape)
+    ops = make_ops(hip_ctx, shape, small, order=3, opset=ref.RETIME[0])
+    assert ops.small_active() == small
+    fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, shape)
+    fv.set(v)
+    cut_sequence(ops, data, "live0", fv, fx, ws)
+    for stage, name in enumerate(ref.RETIME[1:], start=1):
+        for j in range(1, ref.GUESS_SOLVES + 1):
+            fv.set(ref.field(shape, j))
+            assert ops.solve_single(fv, ws, ref.STIM_AMPS, fx, ref.GUESS_RTOL, 1e-300, MAX_IT).converged_reason > 0
+        fv.set(v)
+        ops.set_timestep(*ref.opset(name).triple)  # drops the history: no guess_reset here
+        assert ops.small_active() == small
+        cut_sequence(ops, data, f"live{stage}", fv, fx, ws)
+    fresh = make_ops(hip_ctx, shape, small, order=3, opset=ref.RETIME[1])
+    fv2, fx2, ws2 = fresh.new_field(), fresh.new_field(), stimuli(fresh, shape)
+    fv2.set(v)
+    cut_sequence(fresh, data, "fresh", fv2, fx2, ws2)
+    c = Check(data)
+    for stage, name in enumerate(ref.RETIME):
+        c.cut(f"live{stage}/k={ref.CUTS[0]}", ref.plain_reference(shape, name), ref.CUTS[0])
+    c.cut(f"fresh/k={ref.CUTS[0]}", ref.plain_reference(shape, ref.RETIME[1]), ref.CUTS[0])
+    for k in ref.CUTS:
+        for mine, other in ((f"live1/k={k}", f"fresh/k={k}"), (f"live2/k={k}", f"live0/k={k}")):
+            c.same_bits(other, mine, True)
+            c.that(data[f"{mine}|rec"].tobytes() == data[f"{other}|rec"].tobytes(), mine, f"record {data[f'{mine}|rec'].tolist()}, {other} {data[f'{other}|rec'].tolist()}")
+        c.that(not np.array_equal(data[f"live0/k={k}|x"], data[f"live1/k={k}|x"]), f"live1/k={k}", "the re-timing changed nothing")
+    print(f"small retime {route}: err / yardstick {c.worst}, norm {c.worst_norm}")
+    assert not c.failures, f"{len(c.failures)} failures, the first:\n" + "\n".join(c.failures[:40])

@@ -55,8 +55,12 @@ def _oracle_matrices(cells, L, active, M):
     return mesh, fem.assemble_mass(mesh, np.nonzero(act_s)[0]), fem.assemble_stiffness(mesh, Ms)
 
 
+# (C_m, theta, dt) of the diffusion operator, as in tests/test_gpu_kernels.py: at theta = 1/2 A and B have the same factor of K
+OPSETS = {"cn": (0.01, 0.5, 0.05), "be": (0.01, 1.0, 0.05), "skew": (0.013, 0.25, 0.08)}
+
+
 @pytest.mark.parametrize("cells,L", CASES)
-def test_per_node_operators_match_assembled_matrices(hip_ctx, cells, L):
+def test_per_node_operators_match_assembled_matrices(hip_ctx, cells, L, opset="cn"):
     """A, B, Mass, K applied by the per-node kernels vs scipy CSR matrices assembled cell by cell over the
     active cells with per-cell tensors: <= 1e-13 * ||row||_1 * max|x|.  Rows of untouched nodes are identity
     for A and zero for Mass / K.  Ghost planes are poisoned with NaN."""
@@ -71,7 +75,7 @@ def test_per_node_operators_match_assembled_matrices(hip_ctx, cells, L):
     mf, kf = _stencil.stencil_fields(dim, cells, h, M, active)
     nn = [c + 1 for c in cells] + [1] * (3 - dim)
     ops = HipOps(ctx, nn, True, True, mf, kf, per_node=True)
-    C_m, theta, dt = 0.01, 0.5, 0.05
+    C_m, theta, dt = OPSETS[opset]
     ops.set_timestep(C_m, theta, dt)
     n = mesh.num_nodes
     touched = Mass.diagonal() > 0
@@ -92,6 +96,13 @@ def test_per_node_operators_match_assembled_matrices(hip_ctx, cells, L):
         ref = mat @ x
         scale = max((abs(mat) @ np.ones(n)).max(), 1.0) * np.abs(x).max()
         assert np.abs(fy.numpy() - ref).max() <= 1e-13 * scale, which
+
+
+@pytest.mark.parametrize("opset", ("be", "skew"))
+@pytest.mark.parametrize("cells,L", CASES)
+def test_per_node_operators_match_assembled_matrices_off_theta_one_half(hip_ctx, cells, L, opset):
+    """The test above with A and B two different matrices."""
+    test_per_node_operators_match_assembled_matrices(hip_ctx, cells, L, opset)
 
 
 def test_per_node_rows_reproduce_the_table_path(hip_ctx):
@@ -129,7 +140,7 @@ def test_per_node_rows_reproduce_the_table_path(hip_ctx):
 
 
 @pytest.mark.parametrize("cells,L", CASES[:2])
-def test_per_node_theta_step_matches_direct_solve(hip_ctx, cells, L):
+def test_per_node_theta_step_matches_direct_solve(hip_ctx, cells, L, opset="cn"):
     """One theta-step on the masked shell with a fibre field and a stimulus: rhs build + Jacobi-PCG
     (rtol 1e-12) vs sparse LU on the active sub-system: <= 1e-9 * max|v|; inactive nodes keep their value;
     same iteration count (+-1) as the oracle's restatement of the PCG."""
@@ -145,7 +156,7 @@ def test_per_node_theta_step_matches_direct_solve(hip_ctx, cells, L):
     h = tuple(l / c for l, c in zip(L, cells))
     active, M = _shell_case(cells, L, 9)
     mesh, Mass, K = _oracle_matrices(cells, L, active, M)
-    C_m, theta, dt = 0.01, 0.5, 0.05
+    C_m, theta, dt = OPSETS[opset]
     n = mesh.num_nodes
     touched = Mass.diagonal() > 0
     A = (C_m * Mass + theta * dt * K + sp.diags(np.where(touched, 0.0, 1.0))).tocsc()
@@ -177,6 +188,13 @@ def test_per_node_theta_step_matches_direct_solve(hip_ctx, cells, L):
     res2 = ops.solve_single(fv, [fw], [amp], fv, 1e-12, 1e-50, 1000)
     assert res2.iterations == res.iterations
     np.testing.assert_allclose(fv.numpy(), out, rtol=0, atol=1e-12 * np.abs(ref).max())
+
+
+@pytest.mark.parametrize("opset", ("be", "skew"))
+@pytest.mark.parametrize("cells,L", CASES[:2])
+def test_per_node_theta_step_matches_direct_solve_off_theta_one_half(hip_ctx, cells, L, opset):
+    """The test above with theta = 1 and theta = 1/4: the right-hand side's factor of K is not the matrix's."""
+    test_per_node_theta_step_matches_direct_solve(hip_ctx, cells, L, opset)
 
 
 def test_row_shifting_rhs_kernel_equals_the_gather_kernel_bit_for_bit():

@@ -62,6 +62,19 @@ The same test against builds with one deliberate arithmetic slip each (wrong num
       every route with the tile right-hand side; 62 x 9 x 5 layers (gather kernel) and everything without a guess pass;
   the flush of a full ring skipping its oldest direction (var_flush_kernel) -- 20 cases fail at k = 13 (k = 7 under BEAT_VAR_RING=6)
       and at both stops, off by 5 - 6; 2 x 2 x 2, which is never cut behind a flush, passes.
+
+Off theta = 1/2 (vr.OPSET_CASES under be and skew on vr.OPSET_ROUTES; tests/test_rr_iterates_gpu.py says why, and holds the
+record of the builds with a deliberate slip): var_form_A_kernel forms the rows of A with theta dt and those of B with
+(1 - theta) dt; beat_vtl_rhs reads the rows of B on 8-row tiles, the gather kernel takes c1 / c2.  Measured on an MI355X, the worst
+over the three cases (err / yardstick, norm / yardstick):
+
+    route                  be                                                   skew
+    default [15 / 9]       2.55 (62 x 9 x 5 layers, guess order 3, k = 1), 0.36   2.29 (62 x 9 x 5 layers, k = 1), 0.14
+    BEAT_VTL_PDOT=0        2.55, 0.36                                           2.29, 0.14
+    BEAT_VTL=0 [8]         2.01 (62 x 9 x 5 layers, guess order 3, k = 3), 0.14   2.29, 0.14
+    re-timed handle (cn, skew, cn) on 63 x 16 x 6 full: 2.01, 0.15 on the tile routes; 1.79, 0.14 under BEAT_VTL=0
+
+The module: 8.7 s with the 9 new tests, 7.8 s for the 21 before them, same session.  What it found: nothing.
 """
 import time
 
@@ -113,7 +126,7 @@ def cuts_of(cs, route: str) -> tuple:
     return vr.cuts_of(cs, vr.CUTS_SHORT if route == "ring6" else vr.CUTS)
 
 
-def make_ops(ctx, cs, route, monkeypatch, order=0):
+def make_ops(ctx, cs, route, monkeypatch, order=0, opset="cn"):
     from beat._engine import HipOps
 
     for name in SWITCHES:
@@ -122,7 +135,7 @@ def make_ops(ctx, cs, route, monkeypatch, order=0):
         monkeypatch.setenv(name, value)
     ops = HipOps(ctx, cs.shape, True, True, cs.mass_rows, cs.stiff_rows, per_node=True)  # the rows the host reference expands
     ops.set_guess_order(order)
-    ops.set_timestep(ref.C_M, ref.THETA, ref.DT)
+    ops.set_timestep(*ref.opset(opset).triple)
     got, want = int(ctx.lib.beat_pde_tile_route(ops.handle)), expected_route(cs.shape, route)
     assert got == want, f"{vr.case_key((cs.shape, cs.mask))}/{route}: beat_pde_tile_route {got}, expected {want}"
     assert not ops.small_active()
@@ -149,9 +162,9 @@ def record(data, slips, cs, key, res, fx, v_box):
     data[f"{key}|rec"] = np.array([res.iterations, res.converged_reason, res.residual_norm, res.rhs_norm], dtype=np.float64)
 
 
-def run_plain(ctx, cs, route, data, slips, monkeypatch):
-    ops = make_ops(ctx, cs, route, monkeypatch)
-    base = f"{vr.case_key((cs.shape, cs.mask))}/{route}"
+def run_plain(ctx, cs, route, data, slips, monkeypatch, opset="cn"):
+    ops = make_ops(ctx, cs, route, monkeypatch, opset=opset)
+    base = f"{vr.opset_key((cs.shape, cs.mask), opset)}/{route}"
     v_box = vr.on_box(cs, vr.field(cs))
     fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, cs)
     fv.set(v_box)
@@ -170,11 +183,11 @@ def run_plain(ctx, cs, route, data, slips, monkeypatch):
     assert ops.pending is None
 
 
-def run_guess(ctx, cs, route, data, slips, monkeypatch):
+def run_guess(ctx, cs, route, data, slips, monkeypatch, opset="cn"):
     """Four converged solves of a field that moves between solves, then a cut solve that starts from their extrapolation."""
     for order in ref.GUESS_ORDERS:
-        ops = make_ops(ctx, cs, route, monkeypatch, order=order)
-        key = f"{vr.case_key((cs.shape, cs.mask))}/{route}/e/order={order}"
+        ops = make_ops(ctx, cs, route, monkeypatch, order=order, opset=opset)
+        key = f"{vr.opset_key((cs.shape, cs.mask), opset)}/{route}/e/order={order}"
         fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, cs)
         for k in ref.GUESS_CUTS:
             ops.guess_reset()
@@ -189,8 +202,8 @@ def run_guess(ctx, cs, route, data, slips, monkeypatch):
             record(data, slips, cs, f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx, v_box)
 
 
-def check_plain(c, cs, route):
-    base, r = f"{vr.case_key((cs.shape, cs.mask))}/{route}", vr.plain_reference((cs.shape, cs.mask))
+def check_plain(c, cs, route, opset="cn"):
+    base, r = f"{vr.opset_key((cs.shape, cs.mask), opset)}/{route}", vr.plain_reference((cs.shape, cs.mask), opset)
     for k in cuts_of(cs, route):
         c.cut(f"{base}/k={k}", r, k)
     for rtol in ref.RTOLS:
@@ -199,14 +212,14 @@ def check_plain(c, cs, route):
         c.same_bits(f"{base}/{tail}", f"{base}/inplace/{tail}", True)
 
 
-def check_guess(c, cs, route, references):
+def check_guess(c, cs, route, references, opset="cn"):
     """As check_guess of tests/test_small_iterates_gpu.py: the device's own earlier, converged solves of the sequence supply the
     increments; they are not what is compared.  Routes whose earlier solves are the same bits share a reference."""
-    p = cs.problem
+    p = vr.problem_of((cs.shape, cs.mask), opset)
     v = vr.field(cs, ref.GUESS_SOLVES + 1)
     for order in ref.GUESS_ORDERS:
         for k in ref.GUESS_CUTS:
-            key = f"{vr.case_key((cs.shape, cs.mask))}/{route}/e/order={order}/k={k}"
+            key = f"{vr.opset_key((cs.shape, cs.mask), opset)}/{route}/e/order={order}/k={k}"
             incs = [c.data[f"{key}/solve={j}|x"] - vr.field(cs, j) for j in range(ref.GUESS_SOLVES, 0, -1)]
             c.that(all(c.rec(f"{key}/solve={j}")[1] > 0 for j in range(1, ref.GUESS_SOLVES + 1)), key, "a solve in front of the cut did not converge")
             if not all(np.isfinite(i).all() for i in incs):
@@ -253,3 +266,89 @@ def test_per_node_iterates_match_host_pcg(hip_ctx, case, monkeypatch):
           "route [beat_pde_tile_route] err / max(delta_k, floor) and norm err / yardstick:\n  " + "\n  ".join(lines))
     print("  so far, per route: " + "; ".join(f"{r} {w[0][0]:.2f} ({w[0][1]}), {w[1][0]:.2f} ({w[1][1]})" for r, w in WORST.items()))
     assert not c.failures, f"{len(c.failures)} failures on {vr.case_key(case)}, the first:\n" + "\n".join(c.failures[:40])
+
+
+OFF_CN = [(case, name) for case in vr.OPSET_CASES for name in ref.NEW_SETS]
+WORST_OFF_CN: dict = {}  # (set, route) -> as WORST
+
+
+@pytest.mark.parametrize("pair", OFF_CN, ids=lambda pair: vr.opset_key(*pair))
+def test_per_node_iterates_match_host_pcg_off_theta_one_half(hip_ctx, pair, monkeypatch):
+    """The test above on vr.OPSET_CASES under be and skew, on vr.OPSET_ROUTES: the default route and BEAT_VTL_PDOT=0 form b on the
+    8-row tiles from the rows of B that var_form_A_kernel wrote (beat_vtl_rhs), BEAT_VTL=0 -- and every route of a box with ny < 16 --
+    by the gather kernel from c1 / c2 (beat_var_rhs).  The route is asserted (make_ops) before any value."""
+    case, name = pair
+    cs = vr.case(case)
+    vr.plain_reference(case, name)  # (not part of the device's time)
+    data, slips = {}, []
+    guess = case in vr.OPSET_GUESS_CASES
+    t0 = time.perf_counter()
+    for route in vr.OPSET_ROUTES:
+        run_plain(hip_ctx, cs, route, data, slips, monkeypatch, name)
+        if guess:
+            run_guess(hip_ctx, cs, route, data, slips, monkeypatch, name)
+    hip_ctx.synchronize()
+    seconds = time.perf_counter() - t0
+    c = Check(data)
+    c.failures.extend(slips)
+    references: dict = {}
+    lines = []
+    for route in vr.OPSET_ROUTES:
+        c.worst, c.worst_norm = (0.0, None), (0.0, None)
+        check_plain(c, cs, route, name)
+        if guess:
+            check_guess(c, cs, route, references, name)
+        lines.append(f"{route} [{expected_route(cs.shape, route)}] {c.worst[0]:.2f} ({c.worst[1]}), {c.worst_norm[0]:.2f} ({c.worst_norm[1]})")
+        old = WORST_OFF_CN.get((name, route), ((0.0, None), (0.0, None)))
+        WORST_OFF_CN[(name, route)] = (max(old[0], c.worst, key=lambda w: w[0]), max(old[1], c.worst_norm, key=lambda w: w[0]))
+    print(f"var iterates {vr.opset_key(case, name)}: {cs.n} of {cs.n_nodes} nodes, {sum(k.endswith('|x') for k in data)} solves in {1e3 * seconds:.1f} ms; "
+          "route [beat_pde_tile_route] err / max(delta_k, floor) and norm err / yardstick:\n  " + "\n  ".join(lines))
+    print("  so far, per set and route: " + "; ".join(f"{r} {w[0][0]:.2f} ({w[0][1]}), {w[1][0]:.2f} ({w[1][1]})" for r, w in WORST_OFF_CN.items()))
+    assert not c.failures, f"{len(c.failures)} failures on {vr.opset_key(case, name)}, the first:\n" + "\n".join(c.failures[:40])
+
+
+def cut_sequence(ops, data, slips, cs, key, fv, fx, ws, v_box):
+    """The cuts one after another with NO guess_reset between them: the first starts from x0 = v_ only if the history is empty."""
+    for k in vr.cuts_of(cs, vr.CUTS):
+        fx.fill(float("nan"))
+        record(data, slips, cs, f"{key}/k={k}", ops.solve_single(fv, ws, ref.STIM_AMPS, fx, max_it=k, **NO_STOP), fx, v_box)
+
+
+@pytest.mark.parametrize("route", vr.OPSET_ROUTES)
+def test_retimed_handle_equals_a_fresh_one(hip_ctx, route, monkeypatch):
+    """beat_pde_set_timestep on a live per-node handle (ref.RETIME: cn, skew, cn) with a guess of order 3 and a full history:
+    var_form_A_kernel runs again.  The cut sequence behind each re-timing starts from x0 = v_ (its first iterate is the plain
+    reference's), equals that of a handle created under the set bit for bit, and back under cn what the handle gave before."""
+    case = vr.OPSET_CASES[0]
+    cs = vr.case(case)
+    data, slips = {}, []
+    v_box = vr.on_box(cs, vr.field(cs))
+    ops = make_ops(hip_ctx, cs, route, monkeypatch, order=3, opset=ref.RETIME[0])
+    fv, fx, ws = ops.new_field(), ops.new_field(), stimuli(ops, cs)
+    fv.set(v_box)
+    cut_sequence(ops, data, slips, cs, "live0", fv, fx, ws, v_box)
+    for stage, name in enumerate(ref.RETIME[1:], start=1):
+        for j in range(1, ref.GUESS_SOLVES + 1):
+            fv.set(vr.on_box(cs, vr.field(cs, j)))
+            assert ops.solve_single(fv, ws, ref.STIM_AMPS, fx, ref.GUESS_RTOL, 1e-300, MAX_IT).converged_reason > 0
+        fv.set(v_box)
+        ops.set_timestep(*ref.opset(name).triple)  # drops the history: no guess_reset here
+        assert int(hip_ctx.lib.beat_pde_tile_route(ops.handle)) == expected_route(cs.shape, route)
+        cut_sequence(ops, data, slips, cs, f"live{stage}", fv, fx, ws, v_box)
+    fresh = make_ops(hip_ctx, cs, route, monkeypatch, order=3, opset=ref.RETIME[1])
+    fv2, fx2, ws2 = fresh.new_field(), fresh.new_field(), stimuli(fresh, cs)
+    fv2.set(v_box)
+    cut_sequence(fresh, data, slips, cs, "fresh", fv2, fx2, ws2, v_box)
+    c = Check(data)
+    c.failures.extend(slips)
+    k0 = vr.CUTS[0]
+    for stage, name in enumerate(ref.RETIME):
+        c.cut(f"live{stage}/k={k0}", vr.plain_reference(case, name), k0)
+    c.cut(f"fresh/k={k0}", vr.plain_reference(case, ref.RETIME[1]), k0)
+    for k in vr.cuts_of(cs, vr.CUTS):
+        for mine, other in ((f"live1/k={k}", f"fresh/k={k}"), (f"live2/k={k}", f"live0/k={k}")):
+            c.same_bits(other, mine, True)
+            c.that(data[f"{mine}|rec"].tobytes() == data[f"{other}|rec"].tobytes(), mine, f"record {data[f'{mine}|rec'].tolist()}, {other} {data[f'{other}|rec'].tolist()}")
+        c.that(not np.array_equal(data[f"live0/k={k}|x"], data[f"live1/k={k}|x"]), f"live1/k={k}", "the re-timing changed nothing")
+    print(f"var retime {route}: err / yardstick {c.worst}, norm {c.worst_norm}")
+    assert not c.failures, f"{len(c.failures)} failures, the first:\n" + "\n".join(c.failures[:40])

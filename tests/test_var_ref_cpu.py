@@ -13,6 +13,9 @@ import _pcg_ref as ref
 import _var_ref as vr
 
 CASES = list(vr.CASES)
+# (case, set): every case under cn, as before the sets had names (and under the same test ids), then the pairs off theta = 1/2
+PAIRS = [(c, "cn") for c in CASES] + [(c, name) for c in vr.OPSET_CASES for name in ref.NEW_SETS]
+GUESS_PAIRS = [(c, "cn") for c in vr.GUESS_CASES] + [(c, name) for c in vr.OPSET_GUESS_CASES for name in ref.NEW_SETS]
 SEG = 62  # x-nodes per segment of the tile kernels (csrc/beat_pde_vtl.hip, csrc/beat_pde_vrr.hip)
 
 
@@ -36,6 +39,12 @@ def test_case_table_is_consistent():
     assert all((s, m) in CASES for s in vr.ALL_ROUTE_SHAPES for m in vr.MASKS)  # every route meets every mask
     assert set(vr.GUESS_CASES) <= set(CASES)
     assert max(int(np.prod(s)) for s in vr.SHAPES) <= 45_000  # the sizes at which the tiling branches, not the workload
+    # off theta = 1/2: a few thousand nodes; a dense and a masked box on 8-row tiles, one on 4-row tiles; guess cases of GUESS_CASES
+    assert set(vr.OPSET_CASES) <= set(CASES) and set(vr.OPSET_GUESS_CASES) <= set(vr.OPSET_CASES) & set(vr.GUESS_CASES)
+    assert max(int(np.prod(s)) for s, _ in vr.OPSET_CASES) <= 8192
+    assert any(m == "full" and s[1] >= 16 for s, m in vr.OPSET_CASES) and any(m != "full" and s[1] >= 16 for s, m in vr.OPSET_CASES)
+    assert any(s[1] < 16 for s, _ in vr.OPSET_CASES)
+    assert all(c in dict(vr.DIST_CASES) and w in dict(vr.DIST_CASES)[c] for c, w in vr.DIST_OPSET_CASES) and set(vr.DIST_OPSET_GUESS) <= set(vr.DIST_GUESS_CASES)
     src = (Path(__file__).resolve().parents[1] / "fenicsx-beat_amd" / "csrc" / "beat_pde_internal.h").read_text()
     assert f"constexpr int PRING_MAX = {vr.RING};" in src and f"constexpr int PRING = {vr.RING_SHORT};" in src
     assert vr.CUTS[-1] == vr.RING + 1 and vr.CUTS_SHORT[-1] == vr.RING_SHORT + 1
@@ -148,16 +157,38 @@ def test_the_masks_together_hold_every_gap_and_every_line_feature():
     assert any(f["x_line_crosses_61_62"] for f in feats) and any(f["x_line_ends_at_61"] for f in feats)
 
 
-@pytest.mark.parametrize("c", CASES, ids=vr.case_key)
-def test_reference_converges_and_no_stop_is_a_near_tie(c):
-    cs, r = vr.case(c), vr.plain_reference(c)
-    p = cs.problem
+def test_masked_case_off_cn_has_tissue_meeting_across_tile_edges():
+    """63 x 16 x 6 cutshell: tissue on both sides of the edge between the x-segments (nodes 61 | 62) and between the two 8-row blocks
+    (rows 7 | 8), coupled across them by rows of K."""
+    cs = vr.case(((63, 16, 6), "cutshell"))
+    t = grid(cs, cs.tissue)
+    assert (t[:, :, 61] & t[:, :, 62]).any() and (t[:, 7, :] & t[:, 8, :]).any() and not t.all()
+    kx = [k for k, o in enumerate(fem_offsets()) if o == (1, 0, 0)][0]
+    ky = [k for k, o in enumerate(fem_offsets()) if o == (0, 1, 0)][0]
+    assert (grid(cs, cs.stiff_rows[kx])[:, :, 61] != 0).any() and (grid(cs, cs.stiff_rows[ky])[:, 7, :] != 0).any()
+
+
+def fem_offsets():
+    from oracle import fem
+
+    return [tuple(o) for o in fem.STENCIL_OFFSETS]
+
+
+@pytest.mark.parametrize("pair", PAIRS, ids=lambda pair: vr.opset_key(*pair))
+def test_reference_converges_and_no_stop_is_a_near_tie(pair):
+    c, ops = pair[0], ref.opset(pair[1])
+    cs, r = vr.case(c), vr.plain_reference(c, ops)
+    p = vr.problem_of(c, ops)
+    assert p.ops == ops and p.mass is cs.problem.mass
     v = vr.field(cs)
     assert abs(v.mean()) < 1e-12 and 0.1 < np.abs(v).max() < 10.0 and np.array_equal(v, vr.field(cs))
     box = vr.on_box(cs, v)
     assert np.array_equal(box[cs.tissue], v) and (box[~cs.tissue] >= 1000.0).all()
     bL = ref.rhs_longdouble(p, v)
-    b64 = ref.C_M * (p.mass @ v) - (1 - ref.THETA) * ref.DT * (p.stiff @ v) + ref.DT * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights))
+    C_m, theta, dt = ops.triple
+    b64 = C_m * (p.mass @ v) - (1 - theta) * dt * (p.stiff @ v) + dt * sum(a * w for a, w in zip(ref.STIM_AMPS, p.weights))
+    assert np.array_equal(b64, p.rhs_float64(v))
+    assert abs(p.A - (C_m * p.mass + theta * dt * p.stiff)).max() <= 2 * 2.0**-53 * abs(p.A).max()
     assert np.abs(bL.astype(np.float64) - b64).max() <= 16 * 2.0**-53 * np.abs(b64).max()
     assert r.kmax == vr.kmax_of(cs) <= ref.KMAX
     assert r.rL[r.kmax] <= np.longdouble(1e-9) * r.bL
@@ -180,6 +211,9 @@ def test_reference_converges_and_no_stop_is_a_near_tie(c):
     assert r.rhs_norm_bound() > 0.0
     if cs.n > 100:  # the cut behind the ring flush happens while the iterate still moves
         assert r.rL[vr.RING + 1] > np.longdouble(1e-9) * r.bL and r.stop(ref.RTOLS[0]) >= vr.RING
+    if ops != ref.CN:  # the conditions of tests/test_pcg_ref_cpu.py, in full: converged to 1e-12 at KMAX, a cut at 7 is a cut
+        assert r.rL[r.kmax] <= np.longdouble(1e-12) * r.bL and r.rL[7] > np.longdouble(1e-12) * r.bL
+        assert r.rL[max(vr.CUTS)] > np.longdouble(1e-12) * r.bL
 
 
 @pytest.mark.parametrize("c", CASES, ids=vr.case_key)
@@ -194,7 +228,7 @@ def test_yardstick_sees_a_partial_sum_counted_twice(c):
     A = p.operator(L)
     v = vr.field(cs).astype(L)
     b = ref.rhs_longdouble(p, vr.field(cs))
-    dinv = L(1) / (L(ref.C_M) * p.mass.diagonal().astype(L) + L(ref.THETA) * L(ref.DT) * p.stiff.diagonal().astype(L))
+    dinv = L(1) / p.diagonal(L)
     res = b - ref.matvec(A, v, L)
     z = dinv * res
     q = ref.matvec(A, z, L)
@@ -220,12 +254,13 @@ def test_yardstick_sees_a_partial_sum_counted_twice(c):
         assert float(np.abs(slipped - r.xL[2]).max()) > 1e3 * r.x_bound(2)
 
 
-@pytest.mark.parametrize("c", vr.GUESS_CASES, ids=vr.case_key)
-def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(c):
+@pytest.mark.parametrize("pair", GUESS_PAIRS, ids=lambda pair: vr.opset_key(*pair))
+def test_guess_sequence_moves_and_its_cuts_happen_before_convergence(pair):
     """The fields of the guess cases with the host's own converged solves in place of the device's: the extrapolated start is still
     O(1) wrong, so the cut iterates (k = 1, 3) are far from converged."""
+    c = pair[0]
     cs = vr.case(c)
-    p = cs.problem
+    p = vr.problem_of(*pair)
     incs = []
     for j in range(1, ref.GUESS_SOLVES + 1):
         v = vr.field(cs, j)
