@@ -181,6 +181,12 @@ SIGNATURES = {
     "beat_snap_wait": (_int, [_vp, _int, C.POINTER(_vp), C.POINTER(_dbl)]),
     "beat_snap_release": (_int, [_vp, _int]),
     "beat_snap_destroy": (_int, [_vp]),
+    # state rows as grid fields (beat.odesolver.DolfinMultiODESolver): class_base .. class_rows, rows and the fields are host arrays
+    "beat_rows_plan_create": (_int, [_vp, _i64, _vp, _vp, _int, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_int),
+                                     C.POINTER(_vp)]),
+    "beat_rows_to_fields": (_int, [_vp, _int, C.POINTER(_int), C.POINTER(_vp), _int, _dbl, _int]),
+    "beat_fields_to_rows": (_int, [_vp, _int, C.POINTER(_int), C.POINTER(_vp), _int]),
+    "beat_rows_plan_destroy": (_int, [_vp]),
 }
 
 # callbacks of a beat_comm whose transport is supplied by the caller (include/beat_hip.h)
@@ -200,6 +206,8 @@ E_BUSY = -5  # BEAT_EBUSY: beat_snap_enqueue with every slot in flight
 SNAP_MAX_FIELDS = 8  # BEAT_SNAP_MAX_FIELDS
 SNAP_MAX_DEPTH = 16  # BEAT_SNAP_MAX_DEPTH
 SNAP_STATS, SNAP_NT_LOADS = 1, 2  # flags of beat_snap_create
+ROWS_MAX_FIELDS = 8  # BEAT_ROWS_MAX_FIELDS
+ROWS_KEEP, ROWS_FILL, ROWS_NT_LOADS = 0, 1, 4  # mode of beat_rows_to_fields
 
 SIGNATURES.update({
     "beat_pde_set_ghost_types": (_int, [_vp, _int, _int]),

@@ -225,6 +225,53 @@ class _DeviceODE:
                 pass  # updated in place by the kernel
 
 
+ROWS_NONTEMPORAL = False  # beat_rows_to_fields reads the rows with plain loads (profiles/multi_state_fields.md has both)
+
+
+class _RowsPlan:
+    """A ``beat_rows_plan`` (include/beat_hip.h) over the state arrays of a ``DolfinMultiODESolver``: where every node's states
+    live (``layout``: beat._rows_layout), each class's array (``bases``: device addresses, ``lds``).  Moves up to 8 rows per launch
+    between the arrays and fields of the grid, on the context's stream, without waiting."""
+
+    def __init__(self, ctx, layout, bases, lds, cls_dev=None):
+        k = len(bases)
+        self.ctx, self.n, self.num_classes, self.bases, self.lds = ctx, int(layout.cls.size), k, tuple(bases), tuple(lds)
+        self._cls = ctx.from_numpy(layout.cls) if cls_dev is None else cls_dev  # (borrowed by the plan: kept alive here)
+        self._pos = None if layout.pos is None else ctx.from_numpy(layout.pos)
+        self.handle = C.c_void_p()
+        _hip.check(ctx.lib.beat_rows_plan_create(
+            ctx.handle, self.n, self._cls.data_ptr(), None if self._pos is None else self._pos.data_ptr(), k, (C.c_void_p * k)(*bases),
+            (C.c_int64 * k)(*lds), (C.c_int64 * k)(*layout.class_n), (C.c_int * k)(*layout.class_rows), C.byref(self.handle)))
+
+    def _args(self, rows, fields):
+        for fld in fields:
+            if fld.n != self.n:
+                raise ValueError(f"expected a field of {self.n} values, got {fld.n}")
+        flat = [int(r) for rows_f in rows for r in rows_f]
+        return len(fields), (C.c_int * len(flat))(*flat), (C.c_void_p * len(fields))(*[f.ptr.value for f in fields])
+
+    def expand(self, rows, fields, fill=None, nontemporal=None) -> None:
+        """fields[f][i] = row rows[f][c] of node i's class c at the node's column; a node without a class keeps its value (``fill``
+        None) or gets ``fill``.  More than 8 fields go in chunks."""
+        nt = ROWS_NONTEMPORAL if nontemporal is None else nontemporal
+        mode = (_hip.ROWS_KEEP if fill is None else _hip.ROWS_FILL) | (_hip.ROWS_NT_LOADS if nt else 0)
+        for a in range(0, len(fields), _hip.ROWS_MAX_FIELDS):
+            nf, flat, ptrs = self._args(rows[a : a + _hip.ROWS_MAX_FIELDS], fields[a : a + _hip.ROWS_MAX_FIELDS])
+            _hip.check(self.ctx.lib.beat_rows_to_fields(self.handle, nf, flat, ptrs, mode, 0.0 if fill is None else float(fill), 0))
+
+    def collapse(self, rows, fields) -> None:
+        """The other way: the nodes with a class write fields[f][i] into their class's row."""
+        for a in range(0, len(fields), _hip.ROWS_MAX_FIELDS):
+            nf, flat, ptrs = self._args(rows[a : a + _hip.ROWS_MAX_FIELDS], fields[a : a + _hip.ROWS_MAX_FIELDS])
+            _hip.check(self.ctx.lib.beat_fields_to_rows(self.handle, nf, flat, ptrs, 0))
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.ctx.lib.beat_rows_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
 class BaseDolfinODESolver(abc.ABC):
     v_ode: grid.Function
     v_pde: grid.Function
@@ -816,9 +863,129 @@ class DolfinMultiODESolver(BaseDolfinODESolver):
     def monitor_values(self, names, t: float, out=None):
         raise NotImplementedError("monitor() is not available for DolfinMultiODESolver: use DolfinODESolver with one beat.models.from_ode model")
 
+    # ---- state rows as functions of the grid, on the device -----------------------------------------------------------------
+    def _rows_plan(self) -> _RowsPlan:
+        """The rows plan over the state arrays as they lie now: built on first use, again if an array has moved."""
+        from . import _rows_layout
+
+        ms = self._marker_values
+        if self._marked:
+            states = self._dev.states
+            bases, lds = (states.ptr.value,) * len(ms), (states.ld,) * len(ms)
+        else:
+            bases, lds = tuple(self._odes[m].states.ptr.value for m in ms), tuple(self._odes[m].states.ld for m in ms)
+        plan = getattr(self, "_rows", None)
+        if plan is not None and (plan.bases, plan.lds) == (bases, lds):
+            return plan
+        n = self.markers.x.array.size
+        rows = [int(self.num_states[m]) for m in ms]
+        if not self._marked:  # one array per marker
+            layout, cls_dev = _rows_layout.marker_layout(n, [np.nonzero(self._inds[m])[0] for m in ms], rows), None
+        elif self._node_idx is None:  # one array over the grid: its class bytes are the plan's
+            cls_full = np.full(n, _rows_layout.NO_MODEL, dtype=np.uint8)
+            for k, m in enumerate(ms):
+                cls_full[self._inds[m]] = k
+            layout, cls_dev = _rows_layout.grid_layout(cls_full, len(ms), rows), self._cls_dev
+        else:  # one compact array: the node map and class bytes the ionic kernel reads
+            layout, cls_dev = _rows_layout.compact_layout(n, self._dev.node_map[0].cpu().numpy(), self._cls_dev.cpu().numpy(), len(ms),
+                                                          rows), None
+        self._rows = _RowsPlan(self._ctx, layout, bases, lds, cls_dev)
+        return self._rows
+
+    def _key_rows(self, key) -> list[int]:
+        """The row of every marker's states that ``key`` names: an int (the same row for every marker), a state name (each model's
+        own row of it) or a dict marker -> int | name."""
+        if isinstance(key, dict):
+            if set(key) != set(self._marker_values):
+                raise ValueError(f"a key per marker {self._marker_values} expected, got {tuple(key)}")
+            per_marker = key
+        else:
+            per_marker = {m: key for m in self._marker_values}
+        rows = []
+        for m in self._marker_values:
+            k, fun = per_marker[m], self.fun[m]
+            if isinstance(k, str):
+                if k not in fun.state_names:
+                    raise ValueError(f"marker {m}: {fun.name} has no state {k!r} (it has {', '.join(fun.state_names)})")
+                k = fun.state_index(k)
+            k = int(k)
+            if not 0 <= k < int(self.num_states[m]):
+                raise IndexError(f"marker {m}: state {k} of {self.num_states[m]}")
+            rows.append(k)
+        return rows
+
+    def _rows_device_only(self, what: str) -> None:
+        if not self.on_device:
+            raise NotImplementedError(f"{what} moves rows of the device's state arrays: fun is a host callable")
+        if self.v_ode.function_space.mesh.comm.size > 1:
+            raise NotImplementedError(f"{what} is not available on a decomposed mesh")
+
+    def _is_v(self, rows) -> list[bool]:
+        return [r == int(self.v_index[m]) for r, m in zip(rows, self._marker_values)]
+
+    def _expand_rows(self, rows, fields, fill=None) -> None:
+        """``fields[f]`` (device fields of the grid) from the rows ``rows[f]`` (one per marker) in as few launches as 8 fields each
+        allow; a node without a marker keeps its value or gets ``fill``.  A potential row is completed first.  Does not wait."""
+        if any(any(self._is_v(r)) for r in rows):
+            self._sync_v()  # finish the open solve, apply what it deferred
+            self._refresh_compact_v()  # (compact layout: the row mirrors the potential's home field as of the last ionic launch)
+        self._rows_plan().expand(rows, fields, fill)
+
+    def states_to_functions(self, keys, out: list[grid.Function] | None = None, outside: float | None = None) -> list[grid.Function]:
+        """Row ``key`` of whatever model each node runs, as a function on ``v_ode``'s space, for every ``key`` in ``keys``: an int
+        (the same row for every marker), a state name (``"V"`` may be a different row in each model) or a dict marker -> int |
+        name.  One launch per 8 keys, on the device; returns without waiting.  ``out``: functions to write into instead of new
+        ones.  A node outside every marker keeps what ``out`` holds (``outside=None``; a new function holds 0) or is set to
+        ``outside``.  Equals ``values(marker)[row]`` on every marker's nodes."""
+        self._rows_device_only("states_to_functions()")
+        keys = list(keys)
+        rows = [self._key_rows(k) for k in keys]
+        if out is None:
+            V = self.v_ode.function_space
+            out = [grid.Function(V, name=k if isinstance(k, str) else f"state_{k}" if isinstance(k, int) else "state") for k in keys]
+        elif len(out) != len(keys):
+            raise ValueError(f"{len(keys)} keys, {len(out)} functions")
+        n = self.markers.x.array.size
+        for f in out:
+            if f.num_values != n:
+                raise ValueError(f"expected a function of {n} values, got {f.num_values}")
+        if not keys:
+            return out
+        self._expand_rows(rows, [f.writable_field(overwrite_all=outside is not None) for f in out], outside)
+        for f in out:
+            f._touch()
+        return out
+
+    def state_to_function(self, key, out: grid.Function, outside: float | None = None) -> grid.Function:
+        """``states_to_functions([key], [out], outside)[0]`` (the name ``DolfinODESolver`` has for it)."""
+        return self.states_to_functions([key], [out], outside)[0]
+
+    def function_to_state(self, key, src: grid.Function) -> None:
+        """``src`` -> row ``key`` (see ``states_to_functions``) on the nodes that carry a marker, on the device: a restart from saved
+        frames, a calcium field or a block region put into one state.  A potential row is written as ``from_dolfin`` writes it
+        from ``v_ode``; in the compact layout a key that names the potential for some markers only is refused.  Returns without
+        waiting."""
+        self._rows_device_only("function_to_state()")
+        rows = self._key_rows(key)
+        if src.num_values != self.markers.x.array.size:
+            raise ValueError(f"expected a function of {self.markers.x.array.size} values, got {src.num_values}")
+        is_v = self._is_v(rows)
+        compact = self._marked and self._node_idx is not None  # the potential's home is a field of the grid, not the row
+        if compact and any(is_v) and not all(is_v):
+            raise NotImplementedError("function_to_state() in the compact layout: a key that names the potential for some markers only")
+        self._release_aliases()  # (a function that aliases the potential row -- src itself, maybe -- gets its own copy first)
+        fld = src.field
+        self._rows_plan().collapse([rows], [fld])
+        if compact and all(is_v):
+            self._masked_copy(self._v_row, fld)
+
     def assign_all_states(self, functions: list[grid.Function]) -> None:
         num_states = self.num_states[self._marker_values[0]]
         assert len(functions) == num_states, "Number of functions must match number of states"
+        if self.on_device and self.v_ode.function_space.mesh.comm.size == 1:
+            # one pass over the grid per 8 states (odesolver.py:312-339 pulls every marker's whole array through the host per state)
+            self.states_to_functions(list(range(num_states)), functions)
+            return
         for index, f in enumerate(functions):
             arr = np.asarray(f.x.array).copy()
             for marker in self._marker_values:

@@ -179,8 +179,11 @@ class FieldWriter:
     every=1)``
 
     ``fields``: name -> a scalar P1 ``grid.Function`` (the potential ``pde.state``, an event map ``rec.activation``, ...) or
-    ``(DolfinODESolver, state name or index)`` for a row of a device model's state array that spans the grid, read in place.  All on
-    one undivided mesh; at most 8.  ``stride`` (an int or one per axis) and ``box`` (a (lo, hi) range of node indices per axis)
+    ``(DolfinODESolver, state name or index)`` for a row of a device model's state array that spans the grid, read in place, or
+    ``(DolfinMultiODESolver, key)`` -- ``key`` an int, a state name or a dict marker -> int | name, as ``states_to_functions`` takes
+    it: the row of whatever model a node runs, expanded per frame into a staging field the writer owns (all such sources of a solver
+    in one launch, ahead of the frame's).  A node without a cell model gets ``outside`` there -- a TISSUE node without a model too,
+    which then counts as non-finite in the statistics when ``outside`` is NaN.  All on one undivided mesh; at most 8.  ``stride`` (an int or one per axis) and ``box`` (a (lo, hi) range of node indices per axis)
     choose the nodes ``lo:hi:stride``; on a voxel mesh a sample outside the tissue gets ``outside``.  ``dtype``: ``"float32"`` (rounded
     to nearest even, as ``numpy.float32``) or ``"float64"``.  ``format``: see ``FrameFiles``.  Origin = mesh.lower + lo h, spacing = h
     stride.
@@ -229,21 +232,27 @@ class FieldWriter:
                 m, entry = src.function_space.mesh, ("function", src)
             elif isinstance(src, tuple) and len(src) == 2 and isinstance(src[0], BaseDolfinODESolver):
                 ode, key = src
-                if not isinstance(ode, DolfinODESolver):
-                    raise NotImplementedError(f"field {name!r}: DolfinMultiODESolver keeps its states compactly per marker, not over "
-                                              "the grid; write a function the states are copied into")
                 if not ode.on_device:
                     raise NotImplementedError(f"field {name!r}: the ODE solver runs a host callable; its states are not on the device")
                 if not ode.v_ode.function_space.is_p1:
                     raise NotImplementedError(f"field {name!r}: the ODE solver's space is not P1, its rows do not span the grid's nodes")
-                if isinstance(key, str):
-                    if key not in ode.fun.state_names:
-                        raise ValueError(f"field {name!r}: {ode.fun.name} has no state {key!r} (it has {', '.join(ode.fun.state_names)})")
-                    key = ode.fun.state_index(key)
-                k = int(key)
-                if not 0 <= k < ode.num_states:
-                    raise ValueError(f"field {name!r}: state {key!r} of {ode.num_states}")
-                m, entry = ode.v_ode.function_space.mesh, ("row", ode, k, ode._dev.states.row_field(k))
+                m = ode.v_ode.function_space.mesh
+                if isinstance(ode, DolfinODESolver):  # a row of the one state array, read in place
+                    if isinstance(key, str):
+                        if key not in ode.fun.state_names:
+                            raise ValueError(f"field {name!r}: {ode.fun.name} has no state {key!r} (it has {', '.join(ode.fun.state_names)})")
+                        key = ode.fun.state_index(key)
+                    k = int(key)
+                    if not 0 <= k < ode.num_states:
+                        raise ValueError(f"field {name!r}: state {key!r} of {ode.num_states}")
+                    entry = ("row", ode, k, ode._dev.states.row_field(k))
+                else:  # a multi-model solver: the rows are expanded per frame into a staging field, made below behind the checks
+                    try:
+                        rows = ode._key_rows(key)
+                    except (ValueError, IndexError) as exc:
+                        raise ValueError(f"field {name!r}: {exc}") from None
+                    ode._rows_device_only("FieldWriter")
+                    entry = ("multi", ode, rows)
             else:
                 raise ValueError(f"field {name!r}: a scalar P1 grid.Function or (DolfinODESolver, state) expected, got {type(src).__name__}")
             if mesh is not None and m is not mesh:
@@ -265,8 +274,11 @@ class FieldWriter:
         self.frames = []
         self._files = FrameFiles(path, self.names, format, origin=[l + a * h for l, a, h in zip(mesh.lower, lo, mesh.h)],
                                  spacing=[h * s for h, s in zip(mesh.h, strides)], stride=strides, box=list(zip(lo, hi)))
-        ctx = sources[0][1]._ctx if sources[0][0] == "function" else sources[0][3].ctx
+        ctx = (sources[0][1] if sources[0][0] == "function" else sources[0][1].v_ode)._ctx
         self._ctx = ctx
+        # one staging field of the grid per source of a multi-model solver
+        self._sources = sources = [src + (ctx.field(mesh.num_nodes, mesh.plane),) if src[0] == "multi" else src for src in sources]
+        self._outside = float(outside)
         self._mask = None
         if mesh.active is not None:  # a voxel mesh: uploaded once
             self._mask = ctx.from_numpy(mesh.node_active().astype(np.uint8))
@@ -292,9 +304,21 @@ class FieldWriter:
     # ---- the loop's side ---------------------------------------------------------------------------------------------------------
     def _pointers(self):
         ptrs = (C.c_void_p * len(self._sources))()
+        # rows of multi-model solvers: every solver's are expanded into their staging fields in ONE launch, ahead of the pack launch
+        # on the same stream -- so the staging fields are free again for the next frame at once
+        multi = {}
+        for src in self._sources:
+            if src[0] == "multi":
+                multi.setdefault(id(src[1]), (src[1], [], []))
+                multi[id(src[1])][1].append(src[2])
+                multi[id(src[1])][2].append(src[3])
+        for ode, rows, staging in multi.values():
+            ode._expand_rows(rows, staging, self._outside)
         for j, src in enumerate(self._sources):
             if src[0] == "function":
                 fld = src[1].field  # (applies what is pending on the potential)
+            elif src[0] == "multi":
+                fld = src[3]
             else:
                 _, ode, k, fld = src
                 if k == ode.v_index:

@@ -854,6 +854,45 @@ int beat_snap_release(beat_snap* snap, int slot);
 /* Drains the handle's stream, then frees everything it owns. */
 int beat_snap_destroy(beat_snap* snap);
 
+/* ---- state rows of per-class arrays as fields of the grid, and back ----------------------------------------------------------------
+ * The reference's DolfinMultiODESolver keeps one (S_m, N_m) state array per marker and moves rows between them and functions of
+ * the grid on the host: assign_all_states / states_to_dolfin (src/beat/odesolver.py:312-339) do, for every state and every marker,
+ * arr[inds[marker]] = values(marker)[index, :]; to_dolfin / from_dolfin (odesolver.py:280-292) do the same for the potential row in
+ * both directions.  A beat_rows_plan says once where every node's states live, and one launch over the n nodes of the grid then
+ * moves up to BEAT_ROWS_MAX_FIELDS rows at a time.
+ *
+ * Node i has the class dev_cls[i] (a DEVICE byte per node).  A class at or above num_classes has no source (255: tissue without a
+ * cell model, 254: a padding entry).  Its position is dev_pos[i] (a DEVICE int32 per node, 4-byte aligned), or i with dev_pos NULL:
+ * the arrays span the grid.  Class c is an array of host_class_rows[c] rows of host_class_n[c] doubles that lie host_class_ld[c]
+ * >= class_n[c] doubles apart from the DEVICE address host_class_base[c] on (8-byte aligned; several classes may share one array).
+ * A position outside [0, class_n[c]) is never addressed: such a node has no source either.  All five host arrays are copied;
+ * dev_cls, dev_pos and the arrays behind host_class_base are borrowed for the lifetime of the plan.  n and every class_n must be
+ * below 2^31.  Nothing is allocated on the device and nothing is launched.  BEAT_EINVAL: num_classes outside 1..BEAT_MAX_CLASSES,
+ * a null or misaligned pointer, n or a class_n outside [0, 2^31), a class without rows or with class_ld < class_n. */
+#define BEAT_ROWS_MAX_FIELDS 8
+#define BEAT_ROWS_KEEP 0     /* mode: a node without a source keeps what the output holds (assign_all_states' semantics) */
+#define BEAT_ROWS_FILL 1     /* mode: such a node is set to `fill` */
+#define BEAT_ROWS_NT_LOADS 4 /* mode, or-ed in: the rows are read with non-temporal loads (a choice to measure) */
+typedef struct beat_rows_plan beat_rows_plan;
+int beat_rows_plan_create(beat_ctx* ctx, int64_t n, const unsigned char* dev_cls, const int32_t* dev_pos, int num_classes,
+                          double* const* host_class_base, const int64_t* host_class_ld, const int64_t* host_class_n,
+                          const int* host_class_rows, beat_rows_plan** out);
+/* Expand (odesolver.py:312-339, assign_all_states): host_dev_out[f][i] = class_base[c] + host_rows[f * num_classes + c] * class_ld[c]
+ * + pos[i] for every field f < nfields and node i with a source, c its class: field f may be a different row in every class
+ * ("V" of two models).  host_dev_out: host array of DEVICE pointers, 8-byte aligned, n doubles each; nothing outside [0, n) of an
+ * output is written.  mode BEAT_ROWS_KEEP or BEAT_ROWS_FILL says what a node without a source gets.  One launch on the context's
+ * stream -- every element written once, no atomics, the same input gives the same bits -- that is not waited for.  max_blocks: 0,
+ * or a cap on the blocks of the launch (a test makes one block walk the grid).  BEAT_EINVAL, with nothing launched: nfields outside
+ * 1..BEAT_ROWS_MAX_FIELDS, a null or misaligned pointer, a row outside [0, class_rows[c]), unknown mode bits. */
+int beat_rows_to_fields(beat_rows_plan* plan, int nfields, const int* host_rows, double* const* host_dev_out, int mode, double fill,
+                        int max_blocks);
+/* Collapse (odesolver.py:280-292, from_dolfin, for any rows): the same addressing with the store on the source side; a node without
+ * a source writes nothing, so padding entries and the columns of other nodes stay as they are.  Two fields that name the same row
+ * of a class are refused (BEAT_EINVAL) beside the cases of beat_rows_to_fields.  Enqueued, not waited for. */
+int beat_fields_to_rows(beat_rows_plan* plan, int nfields, const int* host_rows, const double* const* host_dev_in, int max_blocks);
+/* Frees the plan (host memory only).  NULL is fine. */
+int beat_rows_plan_destroy(beat_rows_plan* plan);
+
 #ifdef __cplusplus
 }
 #endif
